@@ -18,12 +18,14 @@ Workloads are BASELINE.json's configs, all through the C-ABI (inc
   --config 4 SYN-4K (4,096 states / 256 classes, 2 MiB table in L2) or --dfa uri_v6,
              65,536 inputs x 64 KiB = 4 GiB.
 
-Prints ONE JSON line on rank 0: the driver's contract plus `roofline` (dominant kernel: algorithmic
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes the last
+step's outputs if --dump-outputs DIR is given, and prints the driver's contract (`value`,
+`ms_per_step`, ...).  With --full the line also carries `roofline` (dominant kernel: algorithmic
 bytes per launch / its average launch duration, HIP events on the launch stream, against the
 8 TB/s HBM peak; every other number in it is measured by THIS run - the read ceiling and the
 LDS gather roof by calibration kernels - except `traffic`, which is null unless a PMC summary
 of the same command is on disk, and then says where it comes from) and `cpu_baseline` (the
-reference's own CPU matcher on this box's host cores, rank 0, N = 1 only).  After the timed
+reference's own CPU matcher on this box's host cores, rank 0, N = 1 only), and after the timed
 region the last output of every stream is checked against the CPU oracle (bit-exact or the
 run is invalid).
 """
@@ -57,12 +59,17 @@ def parse_args():
     ap.add_argument("--rehearse-gather", action="store_true",
                     help="one GPU: run the N > 1 loop (every step's records packed, gathered over "
                          "a ONE-rank RCCL group and widened on the root) to price the root's share")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the outputs against the CPU oracle and "
+                         "measure the roofline, the calibrations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as float64 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-tune", action="store_true",
                     help="hot-row DFAs: keep the static choice of LDS-resident rows (default: "
                          "redgpu_dfa_tune on a 4 MiB sample of the input, outside the timed region)")
-    ap.add_argument("--no-calibration", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--no-calibration", action="store_true", help="--full: skip the calibrations")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline duration")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams the steps are issued on round-robin (1 = one stream; more "
                          "is a diagnostic, not the default: overlap of consecutive batches is the "
@@ -327,6 +334,29 @@ def cpu_identity():
     return model, phys, logical
 
 
+DUMP_ALL_LINES = 1 << 21     # up to here every line is written: 3 x 2^21 float64 = 48 MiB
+DUMP_SAMPLE_LINES = 1 << 20  # a longer output: this many of its lines (4 x 8 MiB with index.npy)
+
+
+def dump_outputs(path, outputs, torch):
+    """Writes one step's Outcome arrays (result, start, end) as float64 `path`/<name>.npy.  An
+    output of more than DUMP_ALL_LINES lines is represented by DUMP_SAMPLE_LINES of them, picked
+    with a fixed seed and listed in index.npy, so the same arguments always write the same lines."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = outputs[0].numel()
+    pick = None
+    if n > DUMP_ALL_LINES:
+        pick = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE_LINES, replace=False))
+        np.save(os.path.join(path, "index.npy"), pick.astype(np.float64))
+    for name, t in zip(("result", "start", "end"), outputs):
+        if t is None:
+            continue
+        if pick is not None:
+            t = t[torch.from_numpy(pick).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float64))
+
+
 # ------------------------------------------------------------------------------------------------
 def main():
     args = parse_args()
@@ -381,13 +411,17 @@ def main():
         args.steps = {1: 300, 2: 20, 3: 40, 4: 5}[args.config]
     if args.warmup is None:
         args.warmup = {1: 30, 2: 3, 3: 5, 4: 1}[args.config]
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.per_call is None:
         args.per_call = min(max(1, args.steps), 32) if (args.config == 1 and not multi) else 1
     if multi or args.streams > 1:
         args.per_call = 1
     per_call = args.per_call
 
-    import oracle  # checker and CPU baseline only - never inside a timed region
+    oracle = None
+    if args.full:
+        import oracle  # checker and CPU baseline only - never inside a timed region
     wl = Workload(args, rank, torch, W, one_amd, oracle)
     info, n = wl.info, wl.n
 
@@ -491,7 +525,7 @@ def main():
     # rank 0 alone, untimed: the same per-GPU workload on ONE GPU, so that the weak-scaling
     # reference of a multi-GPU line is this workload and not another config
     solo = None
-    if multi:
+    if multi and args.full:
         if rank == 0:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -530,7 +564,7 @@ def main():
 
     ev0.record()           # (asynchronous: the idle GPU stamps it at once; its host cost is not a step's)
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last = run_steps(args.steps)
     if streams is not None:
         for st in streams:
             torch.cuda.current_stream().wait_stream(st)
@@ -556,6 +590,66 @@ def main():
                          device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    # ---- what a caller of the timed path received from its last step (N > 1: the root's gather) --
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gather.last if gather is not None else last, torch)
+
+    # ---- the line ---------------------------------------------------------------------------------
+    value = world * args.steps * wl.in_bytes / elapsed / 1e9
+    shape = ("%d ragged lines of 32..256 B (%.2f GiB)" % (n, wl.in_bytes / 2**30) if wl.ragged else
+             "%d lines x %d B" % (n, wl.L))
+    line = {
+        "metric": "GB/s input scanned (and Minput/s) for fixed DFA",
+        "value": round(value, 2),
+        "unit": "GB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {
+            "workload": "%s: %s DFA (%d states used / %d classes, REDA fmtDirect%d), %s per GPU, "
+                        "match<styLast,%s> -> %s" %
+                        (wl.label, wl.dfa_name, info["states_used"], info["n_classes"],
+                         info["format"], shape, "true" if wl.lead else "false",
+                         "result+start+end" if wl.want_start else "result+end"),
+            "input": "text (47-character alphabet, planted matches)" if wl.text else "uniformly random bytes",
+            "lines_per_gpu": n, "line_len": wl.L if not wl.ragged else "32..256",
+            "rotating_input_buffers": len(wl.bufs),
+            "hot_rows": wl.tuned or ("static choice" if info["table_kind"] == 6 else None),
+            "working_set_bytes": len(wl.bufs) * wl.in_bytes,
+            "streams": args.streams,
+            "steps_per_call": per_call,
+            "value_is": ("steps issued round-robin on %d HIP streams: up to %d independent batches in "
+                         "flight" % (args.streams, args.streams)) if args.streams > 1 else
+                        ("one stream; the steps handed to redgpu_match_batches_dev %d at a time (one "
+                         "launch per call: table staged once, tiles handed out across the batches)"
+                         % per_call) if per_call > 1 else
+                        "steps back to back on one stream, one redgpu_match_batch_dev call each",
+            "sharding": "contiguous shard per GPU, no data-path collective" +
+                        ("; EVERY step's Outcomes gathered to rank 0 over %s as compact records "
+                         "(pipelined, 2 in flight)" % ("RCCL" if backend == "nccl" else "gloo")
+                         if multi else "") +
+                        (" - REHEARSAL on one GPU: a one-rank RCCL group, so the pack / collective "
+                         "call / widen-on-root cost of a step is in the number but no bytes cross "
+                         "xGMI" if rehearse else ""),
+        },
+        "minputs_per_s": round(world * args.steps * n / elapsed / 1e6, 1),
+        "kernel": kernel_name,
+    }
+    if gather is not None:
+        line["gathered_steps"] = gather.finished
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
 
     # ---- bit-exact gate: the last output each stream produced inside the timed loop -----------
     bit_exact, matches = True, 0
@@ -834,8 +928,7 @@ def main():
             torch.cuda.synchronize()
             walked = int(w.item())
 
-    # ---- the line ---------------------------------------------------------------------------------
-    value = world * args.steps * wl.in_bytes / elapsed / 1e9
+    # ---- the roofline ------------------------------------------------------------------------------
     l2_bound = info["table_kind"] in (4, 5)  # REDGPU_TAB_GLOBAL_*: one L2 gather per byte
     algo_bytes = (walked if walked is not None else wl.in_bytes) * batches_per_launch
     # kernel_ms = the measured back-to-back loop of the timed path's own launches (it counts the
@@ -916,62 +1009,19 @@ def main():
         roofline["algorithmic_note"] = ("achieved counts the bytes the reference's loop consumes "
                                         "(k_walked); scanned_GBps counts whole lines")
     roofline.update(calib)
-    shape = ("%d ragged lines of 32..256 B (%.2f GiB)" % (n, wl.in_bytes / 2**30) if wl.ragged else
-             "%d lines x %d B" % (n, wl.L))
-    line = {
-        "metric": "GB/s input scanned (and Minput/s) for fixed DFA",
-        "value": round(value, 2),
-        "unit": "GB/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
-        "config": {
-            "workload": "%s: %s DFA (%d states used / %d classes, REDA fmtDirect%d), %s per GPU, "
-                        "match<styLast,%s> -> %s" %
-                        (wl.label, wl.dfa_name, info["states_used"], info["n_classes"],
-                         info["format"], shape, "true" if wl.lead else "false",
-                         "result+start+end" if wl.want_start else "result+end"),
-            "input": "text (47-character alphabet, planted matches)" if wl.text else "uniformly random bytes",
-            "lines_per_gpu": n, "line_len": wl.L if not wl.ragged else "32..256",
-            "rotating_input_buffers": len(wl.bufs),
-            "hot_rows": wl.tuned or ("static choice" if info["table_kind"] == 6 else None),
-            "working_set_bytes": len(wl.bufs) * wl.in_bytes,
-            "streams": args.streams,
-            "steps_per_call": per_call,
-            "value_is": ("steps issued round-robin on %d HIP streams: up to %d independent batches in "
-                         "flight" % (args.streams, args.streams)) if args.streams > 1 else
-                        ("one stream; the steps handed to redgpu_match_batches_dev %d at a time (one "
-                         "launch per call: table staged once, tiles handed out across the batches)"
-                         % per_call) if per_call > 1 else
-                        "steps back to back on one stream, one redgpu_match_batch_dev call each",
-            "sharding": "contiguous shard per GPU, no data-path collective" +
-                        ("; EVERY step's Outcomes gathered to rank 0 over %s as compact records "
-                         "(pipelined, 2 in flight)" % ("RCCL" if backend == "nccl" else "gloo")
-                         if multi else "") +
-                        (" - REHEARSAL on one GPU: a one-rank RCCL group, so the pack / collective "
-                         "call / widen-on-root cost of a step is in the number but no bytes cross "
-                         "xGMI" if rehearse else ""),
-        },
-        "minputs_per_s": round(world * args.steps * n / elapsed / 1e6, 1),
+    line.update({
         "bit_exact": bit_exact,
         "bit_exact_how": wl.verify_note(),
         "checked": checked,
         "matches_in_checked": matches,
         "kernel": kernel_name,
         "roofline": roofline,
-    }
+    })
     if solo is not None:
         line["single_gpu_same_workload_GBps"] = round(solo, 1)
         line["single_gpu_note"] = ("rank 0 alone, untimed phase, same per-GPU workload, no gather: the "
                                    "weak-scaling reference for this line")
     if gather is not None:
-        line["gathered_steps"] = gather.finished
         line["gathered_matches_ranks"] = gathered_ok
         line["gathered_check"] = ("last step: per-rank sums of result / start / end vs the sums of the "
                                   "matching slices on the root; the root's own slice element for element")

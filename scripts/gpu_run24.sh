@@ -5,8 +5,8 @@ set -u
 mkdir -p gpurun_out
 L=gpurun_out/r2_rehearse.log
 : > $L
-timeout -k 10 400 python3 bench.py --config 2 --no-cpu-baseline --no-calibration >> $L 2>&1 || { tail -20 $L; exit 1; }
-timeout -k 10 400 python3 bench.py --rehearse-gather --no-cpu-baseline --no-calibration >> $L 2>&1 || { tail -20 $L; exit 1; }
+timeout -k 10 400 python3 bench.py --full --config 2 --no-cpu-baseline --no-calibration >> $L 2>&1 || { tail -20 $L; exit 1; }
+timeout -k 10 400 python3 bench.py --full --rehearse-gather --no-cpu-baseline --no-calibration >> $L 2>&1 || { tail -20 $L; exit 1; }
 python3 - <<'PY'
 import json
 for line in open('gpurun_out/r2_rehearse.log'):

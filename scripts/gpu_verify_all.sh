@@ -7,15 +7,15 @@ timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | gre
 L=gpurun_out/r2_bench_final.log
 : > $L
 run() { echo "### $*" >> $L; timeout -k 10 500 "$@" >> $L 2>&1 || { echo "FAILED: $*"; tail -30 $L; exit 1; }; }
-run python3 bench.py --steps 20 --warmup 5
-run python3 bench.py --steps 300 --warmup 30
-run python3 bench.py --dfa uri --steps 300 --warmup 30 --cpu-seconds 6
-run python3 bench.py --config 2 --cpu-seconds 6
-run python3 bench.py --config 2 --dfa uri --cpu-seconds 6
-run python3 bench.py --config 3 --cpu-seconds 6
-run python3 bench.py --config 4 --cpu-seconds 6
-run python3 bench.py --config 4 --dfa uri_v6 --cpu-seconds 6
-BENCH_BACKEND=gloo run python3 bench.py --gpus 2 --lines 65536 --steps 6 --warmup 2
+run python3 bench.py --full --steps 20 --warmup 5
+run python3 bench.py --full --steps 300 --warmup 30
+run python3 bench.py --full --dfa uri --steps 300 --warmup 30 --cpu-seconds 6
+run python3 bench.py --full --config 2 --cpu-seconds 6
+run python3 bench.py --full --config 2 --dfa uri --cpu-seconds 6
+run python3 bench.py --full --config 3 --cpu-seconds 6
+run python3 bench.py --full --config 4 --cpu-seconds 6
+run python3 bench.py --full --config 4 --dfa uri_v6 --cpu-seconds 6
+BENCH_BACKEND=gloo run python3 bench.py --full --gpus 2 --lines 65536 --steps 6 --warmup 2
 python3 - <<'PY'
 import json
 for line in open('gpurun_out/r2_bench_final.log'):

@@ -9,7 +9,7 @@ for v in "$@"; do
   envs="${v%%;*}"; args="${v#*;}"
   [ "$envs" == "-" ] && envs="X_=1"
   i=$((i+1))
-  env ${envs//,/ } timeout -k 10 300 python bench.py --gpus 1 --no-cpu-baseline --no-calibration $args > $O/v$i.log 2>&1 || { echo "FAILED $v"; tail -20 $O/v$i.log; exit 1; }
+  env ${envs//,/ } timeout -k 10 300 python bench.py --full --gpus 1 --no-cpu-baseline --no-calibration $args > $O/v$i.log 2>&1 || { echo "FAILED $v"; tail -20 $O/v$i.log; exit 1; }
   python - "$O/v$i.log" "$v" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split('\n')[-1])

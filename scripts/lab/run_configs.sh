@@ -1,7 +1,7 @@
 #!/bin/bash
 # every bench config once (short), logs under gpurun_out/$1
 O=gpurun_out/$1; mkdir -p $O
-run() { name=$1; shift; timeout -k 10 400 python bench.py --gpus 1 --no-cpu-baseline "$@" > $O/$name.log 2>&1 || { echo "FAILED $name"; tail -5 $O/$name.log; }
+run() { name=$1; shift; timeout -k 10 400 python bench.py --full --gpus 1 --no-cpu-baseline "$@" > $O/$name.log 2>&1 || { echo "FAILED $name"; tail -5 $O/$name.log; }
   python - $O/$name.log $name <<'PY'
 import json,sys
 try:

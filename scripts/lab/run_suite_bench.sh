@@ -7,7 +7,7 @@ timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1;
 tail -5 $O/pytest_gpu.log
 [ $rc -ne 0 ] && exit $rc
 for i in 1 2 3; do
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 $2 > $O/bench$i.log 2>&1 || { tail -20 $O/bench$i.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 $2 > $O/bench$i.log 2>&1 || { tail -20 $O/bench$i.log; exit 1; }
   python - $O/bench$i.log <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split('\n')[-1])

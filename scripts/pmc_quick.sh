@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 cd /tmp
 OUT=$R/gpurun_out/pmcq_$TAG
 mkdir -p $OUT
-timeout -k 10 400 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $OUT -- python3 $R/bench.py --no-cpu-baseline --no-calibration --streams 1 "$@" > $OUT/log.txt 2>&1 || { tail -5 $OUT/log.txt; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $OUT -- python3 $R/bench.py --full --no-cpu-baseline --no-calibration --streams 1 "$@" > $OUT/log.txt 2>&1 || { tail -5 $OUT/log.txt; exit 1; }
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections
 f = sorted(glob.glob(sys.argv[1] + "/*/*_counter_collection.csv"))[-1]
