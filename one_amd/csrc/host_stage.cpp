@@ -407,16 +407,4 @@ void hostStageReleaseThread() {
   scratchReleaseThread();
 }
 
-ScopedPin::ScopedPin(const void *ptr, size_t bytes, bool enable) {
-  if (!enable || !ptr || !bytes) return;
-  if (hipHostRegister(const_cast<void *>(ptr), bytes, hipHostRegisterDefault) == hipSuccess)
-    p = const_cast<void *>(ptr);
-  else
-    (void)hipGetLastError();  // not an error of the call: the copies just stay synchronous
-}
-
-ScopedPin::~ScopedPin() {
-  if (p) (void)hipHostUnregister(p);
-}
-
 }  // namespace redgpu

@@ -100,14 +100,4 @@ hipError_t hostStage(int device, HostStage **out);
 // Frees every stage the calling thread holds.
 void hostStageReleaseThread();
 
-// Pins caller memory for the duration of one call so that copies on two streams overlap
-// (H2D of one chunk beside D2H of the previous one); silently does nothing if the runtime
-// refuses the range (read-only mappings, already registered memory).
-struct ScopedPin {
-  void *p = nullptr;
-  ScopedPin(const void *ptr, size_t bytes, bool enable);
-  ~ScopedPin();
-  bool pinned() const { return p != nullptr; }
-};
-
 }  // namespace redgpu

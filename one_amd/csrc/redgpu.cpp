@@ -24,6 +24,13 @@ using namespace redgpu;
 
 namespace {
 
+// a handle that can compute: refused before any HIP call when it has no device image
+int checkHandle(const redgpu_dfa *dfa) {
+  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
+  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  return REDGPU_OK;
+}
+
 int checkStyle(int style) {
   if (style < REDGPU_STY_INSTANT || style > REDGPU_STY_FULL)
     return fail(REDGPU_EEXEC, "unsupported style");  // lib/Matcher.cpp:45
@@ -49,18 +56,51 @@ LaunchCfg cfgOf(const redgpu_dfa *dfa, uint32_t extraFlags = 0) {
   return cfg;
 }
 
+// the rules checkBatch applies where the entry point asks for them
+enum BatchRule : unsigned {
+  kStrideLimit = 1,    // without offsets, lines of 2^40 bytes and more are refused
+  kTrailingLimit = 2,  // with offsets, at most 16 trailing bytes are dropped per line
+};
+
+// What a batch (data, offsets, stride, n > 0) must be; with offsets, stride is the number of
+// trailing bytes to drop per line.  The offsets of a device batch (total == nullptr) cannot be
+// read, so it has bytes when it has offsets or a stride.  A host batch reports *total, its
+// bytes, and *maxLen, its longest line; its offsets must be monotone (a decreasing pair would
+// underflow a line length on the device and send the walk far outside the buffer), and with
+// `cap` records per line (the list verbs) n * cap must stay countable.  A host form leaves the
+// trailing-bytes limit to the _dev form it stages into.  The checks fire in the order written.
+int checkBatch(const uint8_t *data, const uint64_t *offsets, uint64_t stride, uint64_t n,
+               unsigned rules, uint64_t *total = nullptr, uint64_t *maxLen = nullptr,
+               uint64_t cap = 0) {
+  if (!total && !data && (offsets || stride)) return fail(REDGPU_EAPI, "null data buffer");
+  if ((rules & kStrideLimit) && !offsets && stride >= (1ull << 40))
+    return fail(REDGPU_ELIMIT, "stride too large");
+  if (total) {
+    uint64_t m = 0;
+    for (uint64_t i = 0; offsets && i < n; ++i) {
+      if (offsets[i] > offsets[i + 1]) return fail(REDGPU_EAPI, "offsets not monotonic");
+      const uint64_t l = offsets[i + 1] - offsets[i];
+      m = l > m ? l : m;
+    }
+    if (maxLen) *maxLen = m;
+    if (cap && n > (~0ull / 16) / cap) return fail(REDGPU_ELIMIT, "n * cap too large");
+    *total = offsets ? offsets[n] : stride * n;
+    if (*total && !data) return fail(REDGPU_EAPI, "null data buffer");
+  }
+  if ((rules & kTrailingLimit) && offsets && stride > 16)
+    return fail(REDGPU_EAPI, "with offsets, stride is the number of trailing bytes to drop per "
+                             "line (0..16)");
+  return REDGPU_OK;
+}
+
 int runDev(const redgpu_dfa *dfa, int verb, int style, int doLeader, const uint8_t *data,
            const uint64_t *offsets, uint64_t stride, uint64_t n, int32_t *result,
            uint64_t *start, uint64_t *end, hipStream_t stream, uint32_t extraFlags = 0) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (int rc = checkStyle(style)) return rc;
   if (n == 0) return REDGPU_OK;
   if (!result) return fail(REDGPU_EAPI, "null result buffer");
-  if (!data && (offsets || stride)) return fail(REDGPU_EAPI, "null data buffer");
-  if (!offsets && stride >= (1ull << 40)) return fail(REDGPU_ELIMIT, "stride too large");
-  if (offsets && stride > 16) return fail(REDGPU_EAPI, "with offsets, stride is the number of "
-                                                       "trailing bytes to drop per line (0..16)");
+  if (int rc = checkBatch(data, offsets, stride, n, kStrideLimit | kTrailingLimit)) return rc;
   DeviceScope scope(dfa->im->device);
   if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
   Batch b{data, offsets, stride, n, result, start, end};
@@ -77,8 +117,7 @@ int runDev(const redgpu_dfa *dfa, int verb, int style, int doLeader, const uint8
 // into single launches.
 int runDevMany(const redgpu_dfa *dfa, int verb, int style, int doLeader, const redgpu_batch *bs,
                uint32_t nb, hipStream_t stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (int rc = checkStyle(style)) return rc;
   if (nb == 0) return REDGPU_OK;
   if (!bs) return fail(REDGPU_EAPI, "null batch descriptors");
@@ -88,11 +127,8 @@ int runDevMany(const redgpu_dfa *dfa, int verb, int style, int doLeader, const r
     const redgpu_batch &b = bs[k];
     if (b.n == 0) continue;
     if (!b.result) return fail(REDGPU_EAPI, "null result buffer");
-    if (!b.data && (b.offsets || b.stride)) return fail(REDGPU_EAPI, "null data buffer");
-    if (!b.offsets && b.stride >= (1ull << 40)) return fail(REDGPU_ELIMIT, "stride too large");
-    if (b.offsets && b.stride > 16)
-      return fail(REDGPU_EAPI, "with offsets, stride is the number of trailing bytes to drop "
-                               "per line (0..16)");
+    if (int rc = checkBatch(b.data, b.offsets, b.stride, b.n, kStrideLimit | kTrailingLimit))
+      return rc;
     const bool pos = verb == kMatch || verb == kSearch;
     v.push_back(Batch{b.data, b.offsets, b.stride, b.n, b.result, pos ? b.start : nullptr,
                       pos ? b.end : nullptr});
@@ -109,36 +145,6 @@ int runDevMany(const redgpu_dfa *dfa, int verb, int style, int doLeader, const r
   return REDGPU_OK;
 }
 
-// offsets[0..n] of a host-buffer call: monotone (a decreasing pair would underflow a line length
-// on the device and send the walk far outside the buffer)
-int checkOffsets(const uint64_t *offsets, uint64_t n, uint64_t *maxLen = nullptr) {
-  uint64_t m = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    if (offsets[i] > offsets[i + 1]) return fail(REDGPU_EAPI, "offsets not monotonic");
-    const uint64_t l = offsets[i + 1] - offsets[i];
-    m = l > m ? l : m;
-  }
-  if (maxLen) *maxLen = m;
-  return REDGPU_OK;
-}
-
-// The calling thread's staging for the handle's device (host_stage.h); the device scope must
-// be held by the caller.
-int stageOf(const redgpu_dfa *dfa, HostStage **st) {
-  hipError_t e = hostStage(dfa->im->device, st);
-  if (e != hipSuccess) return failHip(e, "host staging (streams)");
-  return REDGPU_OK;
-}
-
-#define STAGE_TRY(expr, what)                                  \
-  do {                                                         \
-    hipError_t e_ = (expr);                                    \
-    if (e_ != hipSuccess) {                                    \
-      (void)st->sync();                                        \
-      return failHip(e_, what);                                \
-    }                                                          \
-  } while (0)
-
 // device buffer slots of a HostStage
 enum StageSlot : int {
   kSlData = 0,   // +parity
@@ -152,16 +158,67 @@ enum StageSlot : int {
   kSlAux3 = 12,
 };
 
-// chunk size of the host-buffer pipeline (REDGPU_HOST_CHUNK_MB overrides: tuning)
-static uint64_t hostChunkBytes() {
-  static const uint64_t v = [] {
-    const char *e = getenv("REDGPU_HOST_CHUNK_MB");
-    const long mb = e ? atol(e) : 0;
-    return uint64_t(mb >= 1 && mb <= 1024 ? mb : 32) << 20;
-  }();
-  return v;
-}
-#define kHostChunkBytes hostChunkBytes()
+// One call of a host-buffer form: the device scope, the calling thread's HostStage and its
+// beginCall(inputBytes), device buffers from the stage's slots, and the copies between them and
+// the caller's memory.  The first step that fails drains both streams - no download may land in
+// caller memory after the call has returned - and sets rc(); every later step does nothing.
+// Every buffer of a call is taken before its first copy: growing a slot waits for the streams.
+class HostCall {
+ public:
+  HostCall(const redgpu_dfa *dfa, uint64_t inputBytes) : scope_(dfa->im->device) {
+    if (scope_.err != hipSuccess) {
+      rc_ = failHip(scope_.err, "hipSetDevice");
+      return;
+    }
+    const hipError_t e = hostStage(dfa->im->device, &st_);
+    if (e != hipSuccess) {
+      rc_ = failHip(e, "host staging (streams)");
+      return;
+    }
+    st_->beginCall(inputBytes);
+  }
+  bool ok() const { return rc_ == REDGPU_OK; }
+  int rc() const { return rc_; }
+  HostStage &stage() const { return *st_; }
+  hipStream_t stream() const { return st_->streams[0]; }
+
+  template <class T> T *buf(int slot, uint64_t count, const char *what) {
+    void *p = nullptr;
+    if (ok()) check(st_->get(slot, count * sizeof(T), &p), "hipMalloc ", what);
+    return static_cast<T *>(p);
+  }
+  // caller memory to and from the device on streams[idx]; `direct`: the caller pinned it
+  template <class T>
+  void upload(T *dev, const T *host, uint64_t count, const char *what, int idx = 0,
+              bool direct = false) {
+    if (ok()) check(st_->copyIn(dev, host, count * sizeof(T), idx, direct), "copy ", what);
+  }
+  template <class T>
+  void download(T *host, const T *dev, uint64_t count, const char *what, int idx = 0,
+                bool direct = false) {
+    if (ok()) check(st_->copyOut(host, dev, count * sizeof(T), idx, direct), "copy ", what);
+  }
+  // the form's _dev call, which returns an error code of its own
+  template <class F> void run(F &&devCall) {
+    if (ok() && (rc_ = devCall()) != REDGPU_OK) (void)st_->sync();
+  }
+  // streams[idx] (-1: both) drained, the downloads behind it in the caller's memory; rc()
+  int wait(int idx = 0) {
+    if (ok()) check(idx < 0 ? st_->sync() : st_->syncStream(idx), "hipStreamSynchronize");
+    return rc_;
+  }
+  // (only while ok())
+  void check(hipError_t e, const char *what, const char *noun = "") {
+    if (e == hipSuccess) return;
+    (void)st_->sync();
+    rc_ = failHip(e, (std::string(what) + noun).c_str());
+  }
+
+ private:
+  DeviceScope scope_;
+  HostStage *st_ = nullptr;
+  int rc_ = REDGPU_OK;
+};
 
 // offsets of a chunk that does not start at byte 0, rebased to the chunk's own buffer: the
 // kernels may read data[0, offsets[n]) anywhere (lanes without a line re-read block 0), so a
@@ -173,44 +230,9 @@ k_rebase(const uint64_t *in, uint64_t n1, uint64_t base, uint64_t *out) {
     out[i] = in[i] - base;
 }
 
-// host-buffer form: the batch is cut into chunks of ~32 MiB of input that alternate between the
-// thread's two private streams - copy in, kernel, copy out per chunk - so that with pinned
-// caller memory (registered for the duration of the call when the batch has several chunks)
-// the upload of one chunk runs beside the download of the previous one.  No allocation, no
-// stream creation and no device-wide synchronisation per call (host_stage.h).
-int runHost(const redgpu_dfa *dfa, int verb, int style, int doLeader, const uint8_t *data,
-            const uint64_t *offsets, uint64_t stride, uint64_t n, int32_t *result,
-            uint64_t *start, uint64_t *end) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
-  if (int rc = checkStyle(style)) return rc;
-  if (n == 0) return REDGPU_OK;
-  if (!result) return fail(REDGPU_EAPI, "null result buffer");
-  if (!offsets && stride >= (1ull << 40)) return fail(REDGPU_ELIMIT, "stride too large");
-  uint64_t maxLen = 0;
-  if (offsets)
-    if (int rc = checkOffsets(offsets, n, &maxLen)) return rc;
-  // the block-wise ragged kernels keep line positions in 32 bits: a line of 4 GiB or more takes
-  // the general kernel (64-bit positions) - here, where the offsets can be read
-  const uint32_t extra = maxLen >= (1ull << 32) - 256 ? REDGPU_F_FORCE_GENERIC : 0u;
-  const uint64_t total = offsets ? offsets[n] : stride * n;
-  if (total && !data) return fail(REDGPU_EAPI, "null data buffer");
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  HostStage *st = nullptr;
-  if (int rc = stageOf(dfa, &st)) return rc;
-  st->beginCall(total);
-
-  // Caller memory that is already pinned (redgpu_host_register, hipHostMalloc, torch's
-  // pin_memory): its copies are asynchronous as they stand, so even a batch of a few MiB is worth
-  // cutting - chunks of 8 MiB alternate between the two streams and the upload of one runs beside
-  // the walk and the download of the one before.  Pageable memory keeps the 32 MiB chunks and is
-  // only cut (and pinned for the call) above 64 MiB: below that the pinning costs more than the
-  // overlap returns.
-  const bool callerPinned = isPinnedHost(data) && isPinnedHost(result) &&
-                            (!start || isPinnedHost(start)) && (!end || isPinnedHost(end));
-  const uint64_t chunkBytes = callerPinned ? (8ull << 20) : kHostChunkBytes;
-  // chunk plan: cuts[c] .. cuts[c + 1] are the lines of chunk c
+// chunk plan of a host-buffer batch: cuts[c] .. cuts[c + 1] are the lines of chunk c
+std::vector<uint64_t> chunkCuts(const uint64_t *offsets, uint64_t stride, uint64_t n,
+                                uint64_t total, uint64_t chunkBytes) {
   std::vector<uint64_t> cuts{0};
   const uint64_t base0 = offsets ? offsets[0] : 0;
   if (total - base0 > 2 * chunkBytes && n >= 4096) {
@@ -234,6 +256,42 @@ int runHost(const redgpu_dfa *dfa, int verb, int style, int doLeader, const uint
     }
   }
   cuts.push_back(n);
+  return cuts;
+}
+
+// host-buffer form: the batch is cut into chunks of ~32 MiB of input that alternate between the
+// thread's two private streams - copy in, kernel, copy out per chunk - so that with pinned
+// caller memory (registered for the duration of the call when the batch has several chunks)
+// the upload of one chunk runs beside the download of the previous one.  No allocation, no
+// stream creation and no device-wide synchronisation per call (host_stage.h).
+int runHost(const redgpu_dfa *dfa, int verb, int style, int doLeader, const uint8_t *data,
+            const uint64_t *offsets, uint64_t stride, uint64_t n, int32_t *result,
+            uint64_t *start, uint64_t *end) {
+  if (int rc = checkHandle(dfa)) return rc;
+  if (int rc = checkStyle(style)) return rc;
+  if (n == 0) return REDGPU_OK;
+  if (!result) return fail(REDGPU_EAPI, "null result buffer");
+  uint64_t total = 0, maxLen = 0;
+  if (int rc = checkBatch(data, offsets, stride, n, kStrideLimit, &total, &maxLen)) return rc;
+  // the block-wise ragged kernels keep line positions in 32 bits: a line of 4 GiB or more takes
+  // the general kernel (64-bit positions) - here, where the offsets can be read
+  const uint32_t extra = maxLen >= (1ull << 32) - 256 ? REDGPU_F_FORCE_GENERIC : 0u;
+  HostCall call(dfa, total);
+  if (!call.ok()) return call.rc();
+  HostStage &st = call.stage();
+
+  // Caller memory that is already pinned (redgpu_host_register, hipHostMalloc, torch's
+  // pin_memory) is copied as it is: its copies are asynchronous as they stand, so even a batch
+  // of a few MiB is worth cutting - chunks of 8 MiB alternate between the two streams and the
+  // upload of one runs beside the walk and the download of the one before.  Pageable memory
+  // keeps the 32 MiB chunks and is only cut above 64 MiB: below that the pinning costs more
+  // than the overlap returns.  Its transfers go the way HostStage::copyIn / copyOut choose (a
+  // small call's through the thread's pinned arena, a large one's whole pages registered for
+  // the call - per chunk when there are several).
+  const bool callerPinned = isPinnedHost(data) && isPinnedHost(result) &&
+                            (!start || isPinnedHost(start)) && (!end || isPinnedHost(end));
+  const std::vector<uint64_t> cuts =
+      chunkCuts(offsets, stride, n, total, callerPinned ? (8ull << 20) : (32ull << 20));
   const size_t nChunks = cuts.size() - 1;
   const bool multi = nChunks > 1;
   uint64_t maxBytes = 0, maxLines = 0;
@@ -243,68 +301,50 @@ int runHost(const redgpu_dfa *dfa, int verb, int style, int doLeader, const uint
     if (bytes > maxBytes) maxBytes = bytes;
     if (hi - lo > maxLines) maxLines = hi - lo;
   }
-  // every buffer before the first copy: growing one waits for the streams
-  uint8_t *dData[2] = {nullptr, nullptr};
-  int32_t *dRes[2] = {nullptr, nullptr};
-  uint64_t *dStart[2] = {nullptr, nullptr}, *dEnd[2] = {nullptr, nullptr}, *dOff = nullptr;
+  uint8_t *dData[2] = {};
+  int32_t *dRes[2] = {};
+  uint64_t *dStart[2] = {}, *dEnd[2] = {}, *dReb[2] = {}, *dOff = nullptr;
   for (int k = 0; k < (multi ? 2 : 1); ++k) {
-    STAGE_TRY(st->get(kSlData + k, maxBytes, reinterpret_cast<void **>(&dData[k])), "hipMalloc data");
-    STAGE_TRY(st->get(kSlRes + k, maxLines * 4, reinterpret_cast<void **>(&dRes[k])), "hipMalloc result");
-    if (start)
-      STAGE_TRY(st->get(kSlStart + k, maxLines * 8, reinterpret_cast<void **>(&dStart[k])), "hipMalloc start");
-    if (end)
-      STAGE_TRY(st->get(kSlEnd + k, maxLines * 8, reinterpret_cast<void **>(&dEnd[k])), "hipMalloc end");
+    dData[k] = call.buf<uint8_t>(kSlData + k, maxBytes, "data");
+    dRes[k] = call.buf<int32_t>(kSlRes + k, maxLines, "result");
+    if (start) dStart[k] = call.buf<uint64_t>(kSlStart + k, maxLines, "start");
+    if (end) dEnd[k] = call.buf<uint64_t>(kSlEnd + k, maxLines, "end");
   }
-  uint64_t *dReb[2] = {nullptr, nullptr};
   if (offsets) {
-    STAGE_TRY(st->get(kSlOff, (n + 1) * 8, reinterpret_cast<void **>(&dOff)), "hipMalloc offsets");
-    if (multi || base0)
+    dOff = call.buf<uint64_t>(kSlOff, n + 1, "offsets");
+    if (multi || offsets[0])
       for (int k = 0; k < (multi ? 2 : 1); ++k)
-        STAGE_TRY(st->get(kSlAux0 + k, (maxLines + 1) * 8, reinterpret_cast<void **>(&dReb[k])),
-                  "hipMalloc chunk offsets");
-  }
-
-  // pinned caller memory makes the copies truly asynchronous (only worth its price when there
-  // is something to overlap)
-  // the caller's memory is pinned and copied as it is; otherwise HostStage::copyIn / copyOut
-  // choose per transfer (a small call's pageable memory through the thread's pinned arena, a
-  // large one's whole pages registered for the call - per chunk when there are several)
-  const bool direct = callerPinned;
-
-  if (offsets) {
-    STAGE_TRY(st->copyIn(dOff, offsets, (n + 1) * 8, 0, direct), "copy offsets");
-    if (multi) {
-      STAGE_TRY(hipEventRecord(st->ready, st->streams[0]), "hipEventRecord");
-      STAGE_TRY(hipStreamWaitEvent(st->streams[1], st->ready, 0), "hipStreamWaitEvent");
+        dReb[k] = call.buf<uint64_t>(kSlAux0 + k, maxLines + 1, "chunk offsets");
+    call.upload(dOff, offsets, n + 1, "offsets", 0, callerPinned);
+    if (multi && call.ok()) {  // stream 1's chunks read the offsets uploaded on stream 0
+      call.check(hipEventRecord(st.ready, st.streams[0]), "hipEventRecord");
+      if (call.ok())
+        call.check(hipStreamWaitEvent(st.streams[1], st.ready, 0), "hipStreamWaitEvent");
     }
   }
-  for (size_t c = 0; c < nChunks; ++c) {
+  for (size_t c = 0; c < nChunks && call.ok(); ++c) {
     const int k = int(c & 1);
-    hipStream_t s = st->streams[k];
+    hipStream_t s = st.streams[k];
     const uint64_t lo = cuts[c], hi = cuts[c + 1], nl = hi - lo;
     const uint64_t byteLo = offsets ? offsets[lo] : lo * stride;
     const uint64_t bytes = offsets ? offsets[hi] - byteLo : nl * stride;
-    if (bytes)
-      STAGE_TRY(st->copyIn(dData[k], data + byteLo, bytes, k, direct), "copy data");
+    call.upload(dData[k], data + byteLo, bytes, "data", k, callerPinned);
     const uint64_t *chunkOff = offsets ? dOff + lo : nullptr;
-    if (offsets && byteLo) {
+    if (offsets && byteLo && call.ok()) {
       const uint32_t blocks = uint32_t((nl + 256) / 256 < 1024 ? (nl + 256) / 256 : 1024);
       hipLaunchKernelGGL(k_rebase, dim3(blocks), dim3(256), 0, s, dOff + lo, nl + 1, byteLo,
                          dReb[k]);
       chunkOff = dReb[k];
     }
-    const int rc = runDev(dfa, verb, style, doLeader, dData[k], chunkOff, stride, nl, dRes[k],
-                          dStart[k], dEnd[k], s, extra);
-    if (rc != REDGPU_OK) {
-      (void)st->sync();
-      return rc;
-    }
-    STAGE_TRY(st->copyOut(result + lo, dRes[k], nl * 4, k, direct), "copy result");
-    if (start) STAGE_TRY(st->copyOut(start + lo, dStart[k], nl * 8, k, direct), "copy start");
-    if (end) STAGE_TRY(st->copyOut(end + lo, dEnd[k], nl * 8, k, direct), "copy end");
+    call.run([&] {
+      return runDev(dfa, verb, style, doLeader, dData[k], chunkOff, stride, nl, dRes[k],
+                    dStart[k], dEnd[k], s, extra);
+    });
+    call.download(result + lo, dRes[k], nl, "result", k, callerPinned);
+    if (start) call.download(start + lo, dStart[k], nl, "start", k, callerPinned);
+    if (end) call.download(end + lo, dEnd[k], nl, "end", k, callerPinned);
   }
-  STAGE_TRY(st->sync(), "hipStreamSynchronize");
-  return REDGPU_OK;
+  return call.wait(-1);
 }
 
 // the two verbs that emit a variable-length record list per line
@@ -313,12 +353,11 @@ enum ListVerb : int { kListCollect = 0, kListMatchAll = 1, kListMatchAllLeader =
 int collectDev(const redgpu_dfa *dfa, int listVerb, const uint8_t *data, const uint64_t *offsets,
                uint64_t stride, uint64_t n, uint64_t cap, uint64_t *counts, int32_t *result,
                uint64_t *start, uint64_t *end, hipStream_t stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (n == 0) return REDGPU_OK;
   if (!counts) return fail(REDGPU_EAPI, "null counts buffer");
   if (cap && !result) return fail(REDGPU_EAPI, "null result buffer");
-  if (!data && (offsets || stride)) return fail(REDGPU_EAPI, "null data buffer");
+  if (int rc = checkBatch(data, offsets, stride, n, 0)) return rc;
   DeviceScope scope(dfa->im->device);
   if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
   Batch b{data, offsets, stride, n, result, start, end};
@@ -641,52 +680,33 @@ int redgpu_match_all_batch(const redgpu_dfa *dfa, int do_leader, const uint8_t *
 static int listHost(const redgpu_dfa *dfa, int listVerb, const uint8_t *data,
                     const uint64_t *offsets, uint64_t stride, uint64_t n, uint64_t cap,
                     uint64_t *counts, int32_t *result, uint64_t *start, uint64_t *end) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (n == 0) return REDGPU_OK;
   if (!counts) return fail(REDGPU_EAPI, "null counts buffer");
   if (cap && !result) return fail(REDGPU_EAPI, "null result buffer");
-  if (offsets)
-    if (int rc = checkOffsets(offsets, n)) return rc;
-  if (!offsets && stride >= (1ull << 40)) return fail(REDGPU_ELIMIT, "stride too large");
-  if (cap && n > (~0ull / 16) / cap) return fail(REDGPU_ELIMIT, "n * cap too large");
-  const uint64_t total = offsets ? offsets[n] : stride * n;
-  if (total && !data) return fail(REDGPU_EAPI, "null data buffer");
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  HostStage *st = nullptr;
-  if (int rc = stageOf(dfa, &st)) return rc;
-  st->beginCall(total);
-  hipStream_t s = st->streams[0];
-  uint8_t *dData = nullptr;
-  uint64_t *dOff = nullptr, *dCnt = nullptr, *dStart = nullptr, *dEnd = nullptr;
-  int32_t *dRes = nullptr;
+  uint64_t total = 0;
+  if (int rc = checkBatch(data, offsets, stride, n, kStrideLimit, &total, nullptr, cap)) return rc;
+  HostCall call(dfa, total);
   const uint64_t slots = n * cap;
-  STAGE_TRY(st->get(kSlData, total, reinterpret_cast<void **>(&dData)), "hipMalloc data");
-  STAGE_TRY(st->get(kSlAux0, n * 8, reinterpret_cast<void **>(&dCnt)), "hipMalloc counts");
-  STAGE_TRY(st->get(kSlRes, (slots + 1) * 4, reinterpret_cast<void **>(&dRes)), "hipMalloc result");
-  if (start)
-    STAGE_TRY(st->get(kSlStart, (slots + 1) * 8, reinterpret_cast<void **>(&dStart)), "hipMalloc start");
-  if (end)
-    STAGE_TRY(st->get(kSlEnd, (slots + 1) * 8, reinterpret_cast<void **>(&dEnd)), "hipMalloc end");
-  if (offsets) {
-    STAGE_TRY(st->get(kSlOff, (n + 1) * 8, reinterpret_cast<void **>(&dOff)), "hipMalloc offsets");
-    STAGE_TRY(st->copyIn(dOff, offsets, (n + 1) * 8, 0), "copy offsets");
-  }
-  if (total) STAGE_TRY(st->copyIn(dData, data, total, 0), "copy data");
-  const int rc = collectDev(dfa, listVerb, dData, dOff, stride, n, cap, dCnt, dRes, dStart, dEnd, s);
-  if (rc != REDGPU_OK) {
-    (void)st->sync();
-    return rc;
-  }
-  STAGE_TRY(st->copyOut(counts, dCnt, n * 8, 0), "copy counts");
+  uint8_t *dData = call.buf<uint8_t>(kSlData, total, "data");
+  uint64_t *dCnt = call.buf<uint64_t>(kSlAux0, n, "counts");
+  int32_t *dRes = call.buf<int32_t>(kSlRes, slots + 1, "result");
+  uint64_t *dStart = start ? call.buf<uint64_t>(kSlStart, slots + 1, "start") : nullptr;
+  uint64_t *dEnd = end ? call.buf<uint64_t>(kSlEnd, slots + 1, "end") : nullptr;
+  uint64_t *dOff = offsets ? call.buf<uint64_t>(kSlOff, n + 1, "offsets") : nullptr;
+  if (offsets) call.upload(dOff, offsets, n + 1, "offsets");
+  call.upload(dData, data, total, "data");
+  call.run([&] {
+    return collectDev(dfa, listVerb, dData, dOff, stride, n, cap, dCnt, dRes, dStart, dEnd,
+                      call.stream());
+  });
+  call.download(counts, dCnt, n, "counts");
   if (slots) {
-    STAGE_TRY(st->copyOut(result, dRes, slots * 4, 0), "copy result");
-    if (start) STAGE_TRY(st->copyOut(start, dStart, slots * 8, 0), "copy start");
-    if (end) STAGE_TRY(st->copyOut(end, dEnd, slots * 8, 0), "copy end");
+    call.download(result, dRes, slots, "result");
+    if (start) call.download(start, dStart, slots, "start");
+    if (end) call.download(end, dEnd, slots, "end");
   }
-  STAGE_TRY(st->syncStream(0), "hipStreamSynchronize");
-  return REDGPU_OK;
+  return call.wait();
 }
 
 int redgpu_replace_batch_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
@@ -694,15 +714,12 @@ int redgpu_replace_batch_dev(const redgpu_dfa *dfa, int style, int do_leader, co
                              const uint8_t *repl, uint64_t repl_len, uint64_t max_count,
                              uint64_t *counts, uint64_t *out_offsets, uint8_t *out,
                              uint64_t out_cap, void *stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (int rc = checkStyle(style)) return rc;
   if (n == 0) return REDGPU_OK;
   if (!counts || !out_offsets) return fail(REDGPU_EAPI, "null output buffer");
-  if (!data && (offsets || stride)) return fail(REDGPU_EAPI, "null data buffer");
+  if (int rc = checkBatch(data, offsets, stride, n, kTrailingLimit)) return rc;
   if (repl_len && !repl) return fail(REDGPU_EAPI, "null replacement");
-  if (offsets && stride > 16) return fail(REDGPU_EAPI, "with offsets, stride is the number of "
-                                                       "trailing bytes to drop per line (0..16)");
   DeviceScope scope(dfa->im->device);
   if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
   Batch b{data, offsets, stride, n, nullptr, nullptr, nullptr};
@@ -719,67 +736,46 @@ int redgpu_replace_batch(const redgpu_dfa *dfa, int style, int do_leader, const 
                          const uint64_t *offsets, uint64_t stride, uint64_t n, const uint8_t *repl,
                          uint64_t repl_len, uint64_t max_count, uint64_t *counts,
                          uint64_t *out_offsets, uint8_t *out, uint64_t out_cap) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (int rc = checkStyle(style)) return rc;
   if (n == 0) return REDGPU_OK;
   if (!counts || !out_offsets) return fail(REDGPU_EAPI, "null output buffer");
-  if (offsets)
-    if (int rc = checkOffsets(offsets, n)) return rc;
-  if (!offsets && stride >= (1ull << 40)) return fail(REDGPU_ELIMIT, "stride too large");
-  const uint64_t total = offsets ? offsets[n] : stride * n;
-  if (total && !data) return fail(REDGPU_EAPI, "null data buffer");
+  uint64_t total = 0;
+  if (int rc = checkBatch(data, offsets, stride, n, kStrideLimit, &total)) return rc;
   if (repl_len && !repl) return fail(REDGPU_EAPI, "null replacement");
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  HostStage *st = nullptr;
-  if (int rc = stageOf(dfa, &st)) return rc;
-  st->beginCall(total);
-  hipStream_t s = st->streams[0];
-  uint8_t *dData = nullptr, *dRepl = nullptr, *dOut = nullptr;
-  uint64_t *dOff = nullptr, *dCnt = nullptr, *dOutOff = nullptr;
-  STAGE_TRY(st->get(kSlData, total, reinterpret_cast<void **>(&dData)), "hipMalloc data");
-  STAGE_TRY(st->get(kSlAux0, repl_len, reinterpret_cast<void **>(&dRepl)), "hipMalloc repl");
-  STAGE_TRY(st->get(kSlAux1, n * 8, reinterpret_cast<void **>(&dCnt)), "hipMalloc counts");
-  STAGE_TRY(st->get(kSlAux2, (n + 1) * 8, reinterpret_cast<void **>(&dOutOff)), "hipMalloc out offsets");
-  if (out && out_cap)
-    STAGE_TRY(st->get(kSlAux3, out_cap, reinterpret_cast<void **>(&dOut)), "hipMalloc out");
-  if (offsets) {
-    STAGE_TRY(st->get(kSlOff, (n + 1) * 8, reinterpret_cast<void **>(&dOff)), "hipMalloc offsets");
-    STAGE_TRY(st->copyIn(dOff, offsets, (n + 1) * 8, 0), "copy offsets");
+  HostCall call(dfa, total);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, total, "data");
+  uint8_t *dRepl = call.buf<uint8_t>(kSlAux0, repl_len, "repl");
+  uint64_t *dCnt = call.buf<uint64_t>(kSlAux1, n, "counts");
+  uint64_t *dOutOff = call.buf<uint64_t>(kSlAux2, n + 1, "out offsets");
+  uint8_t *dOut = out && out_cap ? call.buf<uint8_t>(kSlAux3, out_cap, "out") : nullptr;
+  uint64_t *dOff = offsets ? call.buf<uint64_t>(kSlOff, n + 1, "offsets") : nullptr;
+  if (offsets) call.upload(dOff, offsets, n + 1, "offsets");
+  call.upload(dData, data, total, "data");
+  call.upload(dRepl, repl, repl_len, "repl");
+  call.run([&] {
+    return redgpu_replace_batch_dev(dfa, style, do_leader, dData, dOff, stride, n, dRepl,
+                                    repl_len, max_count, dCnt, dOutOff, dOut,
+                                    dOut ? out_cap : 0, call.stream());
+  });
+  call.download(counts, dCnt, n, "counts");
+  call.download(out_offsets, dOutOff, n + 1, "out offsets");
+  if (int rc = call.wait()) return rc;
+  if (!dOut) return REDGPU_OK;
+  // the lines that fit are a prefix (offsets are monotone): copy up to the last one that does
+  uint64_t lo = 0, hi = n;  // largest k with out_offsets[k] <= out_cap
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi + 1) / 2;
+    if (out_offsets[mid] <= out_cap) lo = mid; else hi = mid - 1;
   }
-  if (total) STAGE_TRY(st->copyIn(dData, data, total, 0), "copy data");
-  if (repl_len) STAGE_TRY(st->copyIn(dRepl, repl, repl_len, 0), "copy repl");
-  const int rc = redgpu_replace_batch_dev(dfa, style, do_leader, dData, dOff, stride, n, dRepl,
-                                          repl_len, max_count, dCnt, dOutOff, dOut,
-                                          dOut ? out_cap : 0, s);
-  if (rc != REDGPU_OK) {
-    (void)st->sync();
-    return rc;
-  }
-  STAGE_TRY(st->copyOut(counts, dCnt, n * 8, 0), "copy counts");
-  STAGE_TRY(st->copyOut(out_offsets, dOutOff, (n + 1) * 8, 0),
-            "copy out offsets");
-  STAGE_TRY(st->syncStream(0), "hipStreamSynchronize");
-  if (dOut) {
-    // the lines that fit are a prefix (offsets are monotone): copy up to the last one that does
-    uint64_t lo = 0, hi = n;  // largest k with out_offsets[k] <= out_cap
-    while (lo < hi) {
-      const uint64_t mid = (lo + hi + 1) / 2;
-      if (out_offsets[mid] <= out_cap) lo = mid; else hi = mid - 1;
-    }
-    if (out_offsets[lo]) {
-      STAGE_TRY(st->copyOut(out, dOut, out_offsets[lo], 0), "copy out");
-      STAGE_TRY(st->syncStream(0), "hipStreamSynchronize");
-    }
-  }
-  return REDGPU_OK;
+  if (!out_offsets[lo]) return REDGPU_OK;
+  call.download(out, dOut, out_offsets[lo], "out");
+  return call.wait();
 }
 
 int redgpu_split_lines_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                            uint64_t *offsets, uint64_t cap, uint64_t *n_lines, void *stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (!offsets || !n_lines) return fail(REDGPU_EAPI, "null output buffer");
   if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
   if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
@@ -790,9 +786,7 @@ int redgpu_split_lines_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t 
   void *scratch = nullptr;
   // counts u32[nChunks], bases u64[nChunks], then the delimiter masks (2 bytes per 16 of input):
   // the calling thread's scratch for this stream (kernels.h) - what the next launch on the
-  // stream does with the same buffer comes behind these kernels.  (Up to round 3 this was
-  // hipMallocAsync / hipFreeAsync per call: ~12 us of host time each, and the only use of the
-  // stream-ordered allocator in the library.)
+  // stream does with the same buffer comes behind these kernels
   const size_t countBytes = (size_t(nChunks) * 4 + 15) & ~size_t(15);
   const size_t headBytes = countBytes + size_t(nChunks) * 8 + 16;
   HIP_TRY(scratchFor(s, headBytes + splitMaskBytes(len) + 16, &scratch), "hipMalloc scratch");
@@ -856,91 +850,65 @@ int redgpu_match_text_dev(const redgpu_dfa *dfa, int style, int do_leader, const
 int redgpu_match_text(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
                       uint64_t len, uint8_t delim, uint64_t *offsets, uint64_t cap,
                       uint64_t *n_lines, int32_t *result, uint64_t *start, uint64_t *end) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (!n_lines) return fail(REDGPU_EAPI, "null output buffer");
   if (cap && (!offsets || !result)) return fail(REDGPU_EAPI, "null output buffer");
   if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  HostStage *st = nullptr;
-  if (int rc = stageOf(dfa, &st)) return rc;
-  st->beginCall(len);
-  hipStream_t s = st->streams[0];
+  HostCall call(dfa, len);
   if (cap > len) cap = len;
-  uint8_t *dData = nullptr;
-  uint64_t *dOff = nullptr, *dN = nullptr, *dStart = nullptr, *dEnd = nullptr;
-  int32_t *dRes = nullptr;
-  STAGE_TRY(st->get(kSlData, len, reinterpret_cast<void **>(&dData)), "hipMalloc data");
-  STAGE_TRY(st->get(kSlAux0, 8, reinterpret_cast<void **>(&dN)), "hipMalloc count");
-  STAGE_TRY(st->get(kSlOff, (cap + 1) * 8, reinterpret_cast<void **>(&dOff)), "hipMalloc offsets");
-  STAGE_TRY(st->get(kSlRes, cap * 4, reinterpret_cast<void **>(&dRes)), "hipMalloc result");
-  if (start) STAGE_TRY(st->get(kSlStart, cap * 8, reinterpret_cast<void **>(&dStart)), "hipMalloc start");
-  if (end) STAGE_TRY(st->get(kSlEnd, cap * 8, reinterpret_cast<void **>(&dEnd)), "hipMalloc end");
-  if (len) STAGE_TRY(st->copyIn(dData, data, len, 0), "copy data");
-  const int rc = textDev(dfa, start || end ? kMatch : kCheck, style, do_leader, dData, len, delim,
-                         dOff, cap, dN, dRes, dStart, dEnd, s);
-  if (rc != REDGPU_OK) {
-    (void)st->sync();
-    return rc;
-  }
-  STAGE_TRY(st->copyOut(n_lines, dN, 8, 0), "copy count");
-  STAGE_TRY(st->syncStream(0), "hipStreamSynchronize");
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dN = call.buf<uint64_t>(kSlAux0, 1, "count");
+  uint64_t *dOff = call.buf<uint64_t>(kSlOff, cap + 1, "offsets");
+  int32_t *dRes = call.buf<int32_t>(kSlRes, cap, "result");
+  uint64_t *dStart = start ? call.buf<uint64_t>(kSlStart, cap, "start") : nullptr;
+  uint64_t *dEnd = end ? call.buf<uint64_t>(kSlEnd, cap, "end") : nullptr;
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return textDev(dfa, start || end ? kMatch : kCheck, style, do_leader, dData, len, delim, dOff,
+                   cap, dN, dRes, dStart, dEnd, call.stream());
+  });
+  call.download(n_lines, dN, 1, "count");
+  if (int rc = call.wait()) return rc;
   const uint64_t got = *n_lines < cap ? *n_lines : cap;
-  if (cap) STAGE_TRY(st->copyOut(offsets, dOff, (got + 1) * 8, 0), "copy offsets");
+  if (cap) call.download(offsets, dOff, got + 1, "offsets");
   if (got) {
-    STAGE_TRY(st->copyOut(result, dRes, got * 4, 0), "copy result");
-    if (start) STAGE_TRY(st->copyOut(start, dStart, got * 8, 0), "copy start");
-    if (end) STAGE_TRY(st->copyOut(end, dEnd, got * 8, 0), "copy end");
+    call.download(result, dRes, got, "result");
+    if (start) call.download(start, dStart, got, "start");
+    if (end) call.download(end, dEnd, got, "end");
   }
-  STAGE_TRY(st->syncStream(0), "hipStreamSynchronize");
-  return REDGPU_OK;
+  return call.wait();
 }
 
 int redgpu_split_lines(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                        uint64_t *offsets, uint64_t cap, uint64_t *n_lines) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (!offsets || !n_lines) return fail(REDGPU_EAPI, "null output buffer");
   if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  HostStage *st = nullptr;
-  if (int rc = stageOf(dfa, &st)) return rc;
-  st->beginCall(len);
-  hipStream_t s = st->streams[0];
-  uint8_t *dData = nullptr;
-  uint64_t *dOff = nullptr, *dN = nullptr;
-  STAGE_TRY(st->get(kSlData, len, reinterpret_cast<void **>(&dData)), "hipMalloc data");
-  STAGE_TRY(st->get(kSlAux0, 8, reinterpret_cast<void **>(&dN)), "hipMalloc count");
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dN = call.buf<uint64_t>(kSlAux0, 1, "count");
   // count first (room for no line at all), then size the device offsets to what will be kept
-  STAGE_TRY(st->get(kSlOff, 8, reinterpret_cast<void **>(&dOff)), "hipMalloc offsets");
-  if (len) STAGE_TRY(st->copyIn(dData, data, len, 0), "copy data");
-  int rc = redgpu_split_lines_dev(dfa, dData, len, delim, dOff, 0, dN, s);
-  if (rc != REDGPU_OK) {
-    (void)st->sync();
-    return rc;
-  }
-  STAGE_TRY(st->copyOut(n_lines, dN, 8, 0), "copy count");
-  STAGE_TRY(st->syncStream(0), "hipStreamSynchronize");
+  uint64_t *dOff = call.buf<uint64_t>(kSlOff, 1, "offsets");
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return redgpu_split_lines_dev(dfa, dData, len, delim, dOff, 0, dN, call.stream());
+  });
+  call.download(n_lines, dN, 1, "count");
+  if (int rc = call.wait()) return rc;
   const uint64_t got = *n_lines < cap ? *n_lines : cap;
   if (got) {
-    STAGE_TRY(st->get(kSlOff, (got + 1) * 8, reinterpret_cast<void **>(&dOff)), "hipMalloc offsets");
-    rc = redgpu_split_lines_dev(dfa, dData, len, delim, dOff, got, dN, s);
-    if (rc != REDGPU_OK) {
-      (void)st->sync();
-      return rc;
-    }
+    dOff = call.buf<uint64_t>(kSlOff, got + 1, "offsets");
+    call.run([&] {
+      return redgpu_split_lines_dev(dfa, dData, len, delim, dOff, got, dN, call.stream());
+    });
   }
-  STAGE_TRY(st->copyOut(offsets, dOff, (got + 1) * 8, 0), "copy offsets");
-  STAGE_TRY(st->syncStream(0), "hipStreamSynchronize");
-  return REDGPU_OK;
+  call.download(offsets, dOff, got + 1, "offsets");
+  return call.wait();
 }
 
 int redgpu_diag_read_dev(const redgpu_dfa *dfa, const void *data, uint64_t bytes, uint32_t *sink,
                          void *stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (!data || !sink) return fail(REDGPU_EAPI, "null buffer");
   if (reinterpret_cast<uintptr_t>(data) % 16) return fail(REDGPU_EAPI, "buffer not 16-byte aligned");
   DeviceScope scope(dfa->im->device);
@@ -954,8 +922,7 @@ int redgpu_diag_read_dev(const redgpu_dfa *dfa, const void *data, uint64_t bytes
 int redgpu_diag_lines_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t n_lines,
                           uint64_t line_bytes, int32_t *result, uint64_t *start, uint64_t *end,
                           uint32_t *sink, void *stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (line_bytes != 64 && (line_bytes % 128 || line_bytes == 0 || line_bytes >= (1ull << 31)))
     return fail(REDGPU_EAPI, "line_bytes must be 64 or a multiple of 128");
   if (!data || !sink || (line_bytes == 64 && (!result || !start || !end)))
@@ -972,8 +939,7 @@ int redgpu_diag_lines_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t n
 
 int redgpu_diag_lds_dev(const redgpu_dfa *dfa, uint32_t rounds, uint32_t *sink, uint64_t *lookups,
                         void *stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (!sink) return fail(REDGPU_EAPI, "null buffer");
   DeviceScope scope(dfa->im->device);
   if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
@@ -986,8 +952,7 @@ int redgpu_diag_lds_dev(const redgpu_dfa *dfa, uint32_t rounds, uint32_t *sink, 
 
 int redgpu_diag_l2_dev(const redgpu_dfa *dfa, const uint16_t *table, uint32_t rounds, uint32_t *sink,
                        uint64_t *lookups, void *stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (!table || !sink) return fail(REDGPU_EAPI, "null buffer");
   DeviceScope scope(dfa->im->device);
   if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
@@ -1001,13 +966,10 @@ int redgpu_diag_l2_dev(const redgpu_dfa *dfa, const uint16_t *table, uint32_t ro
 int redgpu_diag_walked_dev(const redgpu_dfa *dfa, int do_leader, const uint8_t *data,
                            const uint64_t *offsets, uint64_t stride, uint64_t n, uint64_t *walked,
                            void *stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (n == 0) return REDGPU_OK;
   if (!walked) return fail(REDGPU_EAPI, "null buffer");
-  if (!data && (offsets || stride)) return fail(REDGPU_EAPI, "null data buffer");
-  if (offsets && stride > 16) return fail(REDGPU_EAPI, "with offsets, stride is the number of "
-                                                       "trailing bytes to drop per line (0..16)");
+  if (int rc = checkBatch(data, offsets, stride, n, kTrailingLimit)) return rc;
   DeviceScope scope(dfa->im->device);
   if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
   Batch b{data, offsets, stride, n, nullptr, nullptr, nullptr};
@@ -1042,10 +1004,9 @@ uint64_t redgpu_scratch_entries(void) { return scratchEntries(); }
 
 int redgpu_dfa_tune_dev(redgpu_dfa *dfa, const uint8_t *data, const uint64_t *offsets,
                         uint64_t stride, uint64_t n, void *stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (n == 0) return REDGPU_OK;
-  if (!data && (offsets || stride)) return fail(REDGPU_EAPI, "null data buffer");
+  if (int rc = checkBatch(data, offsets, stride, n, 0)) return rc;
   DeviceScope scope(dfa->im->device);
   if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
   // a fused u8 table in LDS (<= 256 states) already takes the streaming kernels
@@ -1095,39 +1056,28 @@ int redgpu_dfa_tune_dev(redgpu_dfa *dfa, const uint8_t *data, const uint64_t *of
 
 int redgpu_dfa_tune(redgpu_dfa *dfa, const uint8_t *data, const uint64_t *offsets, uint64_t stride,
                     uint64_t n) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (n == 0) return REDGPU_OK;
-  if (offsets)
-    if (int rc = checkOffsets(offsets, n)) return rc;
-  const uint64_t total = offsets ? offsets[n] : stride * n;
-  if (total && !data) return fail(REDGPU_EAPI, "null data buffer");
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  HostStage *st = nullptr;
-  if (int rc = stageOf(dfa, &st)) return rc;
-  st->beginCall(total);
-  hipStream_t s = st->streams[0];
-  uint8_t *dData = nullptr;
-  uint64_t *dOff = nullptr;
-  STAGE_TRY(st->get(kSlData, total, reinterpret_cast<void **>(&dData)), "hipMalloc data");
-  if (offsets) {
-    STAGE_TRY(st->get(kSlOff, (n + 1) * 8, reinterpret_cast<void **>(&dOff)), "hipMalloc offsets");
-    STAGE_TRY(st->copyIn(dOff, offsets, (n + 1) * 8, 0), "copy offsets");
-  }
-  if (total) STAGE_TRY(st->copyIn(dData, data, total, 0), "copy data");
-  return redgpu_dfa_tune_dev(dfa, dData, dOff, stride, n, s);  // synchronises
+  uint64_t total = 0;
+  if (int rc = checkBatch(data, offsets, stride, n, kStrideLimit, &total)) return rc;
+  HostCall call(dfa, total);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, total, "data");
+  uint64_t *dOff = offsets ? call.buf<uint64_t>(kSlOff, n + 1, "offsets") : nullptr;
+  if (offsets) call.upload(dOff, offsets, n + 1, "offsets");
+  call.upload(dData, data, total, "data");
+  // (tune_dev synchronises)
+  call.run([&] { return redgpu_dfa_tune_dev(dfa, dData, dOff, stride, n, call.stream()); });
+  return call.rc();
 }
 
 int redgpu_advance_batch_dev(const redgpu_dfa *dfa, const uint8_t *data, const uint64_t *offsets,
                              uint64_t stride, uint64_t n, uint32_t *state, int32_t *result,
                              void *stream) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (n == 0) return REDGPU_OK;
   if (!state) return fail(REDGPU_EAPI, "null state buffer");
   if (!result) return fail(REDGPU_EAPI, "null result buffer");
-  if (!data && (offsets || stride)) return fail(REDGPU_EAPI, "null data buffer");
+  if (int rc = checkBatch(data, offsets, stride, n, 0)) return rc;
   DeviceScope scope(dfa->im->device);
   if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
   Batch b{data, offsets, stride, n, result, nullptr, nullptr};
@@ -1141,43 +1091,26 @@ int redgpu_advance_batch_dev(const redgpu_dfa *dfa, const uint8_t *data, const u
 
 int redgpu_advance_batch(const redgpu_dfa *dfa, const uint8_t *data, const uint64_t *offsets,
                          uint64_t stride, uint64_t n, uint32_t *state, int32_t *result) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (dfa->im->device < 0) return fail(REDGPU_EAPI, "dfa handle has no device image");
+  if (int rc = checkHandle(dfa)) return rc;
   if (n == 0) return REDGPU_OK;
   if (!state) return fail(REDGPU_EAPI, "null state buffer");
   if (!result) return fail(REDGPU_EAPI, "null result buffer");
-  if (offsets)
-    if (int rc = checkOffsets(offsets, n)) return rc;
-  const uint64_t total = offsets ? offsets[n] : stride * n;
-  if (total && !data) return fail(REDGPU_EAPI, "null data buffer");
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  HostStage *st = nullptr;
-  if (int rc = stageOf(dfa, &st)) return rc;
-  st->beginCall(total);
-  hipStream_t s = st->streams[0];
-  uint8_t *dData = nullptr;
-  uint64_t *dOff = nullptr;
-  uint32_t *dState = nullptr;
-  int32_t *dRes = nullptr;
-  STAGE_TRY(st->get(kSlData, total, reinterpret_cast<void **>(&dData)), "hipMalloc data");
-  STAGE_TRY(st->get(kSlAux0, n * 4, reinterpret_cast<void **>(&dState)), "hipMalloc state");
-  STAGE_TRY(st->get(kSlRes, n * 4, reinterpret_cast<void **>(&dRes)), "hipMalloc result");
-  if (offsets) {
-    STAGE_TRY(st->get(kSlOff, (n + 1) * 8, reinterpret_cast<void **>(&dOff)), "hipMalloc offsets");
-    STAGE_TRY(st->copyIn(dOff, offsets, (n + 1) * 8, 0), "copy offsets");
-  }
-  if (total) STAGE_TRY(st->copyIn(dData, data, total, 0), "copy data");
-  STAGE_TRY(st->copyIn(dState, state, n * 4, 0), "copy state");
-  const int rc = redgpu_advance_batch_dev(dfa, dData, dOff, stride, n, dState, dRes, s);
-  if (rc != REDGPU_OK) {
-    (void)st->sync();
-    return rc;
-  }
-  STAGE_TRY(st->copyOut(state, dState, n * 4, 0), "copy state back");
-  STAGE_TRY(st->copyOut(result, dRes, n * 4, 0), "copy result");
-  STAGE_TRY(st->syncStream(0), "hipStreamSynchronize");
-  return REDGPU_OK;
+  uint64_t total = 0;
+  if (int rc = checkBatch(data, offsets, stride, n, kStrideLimit, &total)) return rc;
+  HostCall call(dfa, total);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, total, "data");
+  uint32_t *dState = call.buf<uint32_t>(kSlAux0, n, "state");
+  int32_t *dRes = call.buf<int32_t>(kSlRes, n, "result");
+  uint64_t *dOff = offsets ? call.buf<uint64_t>(kSlOff, n + 1, "offsets") : nullptr;
+  if (offsets) call.upload(dOff, offsets, n + 1, "offsets");
+  call.upload(dData, data, total, "data");
+  call.upload(dState, state, n, "state");
+  call.run([&] {
+    return redgpu_advance_batch_dev(dfa, dData, dOff, stride, n, dState, dRes, call.stream());
+  });
+  call.download(state, dState, n, "state back");
+  call.download(result, dRes, n, "result");
+  return call.wait();
 }
 
 int redgpu_check_batch_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,

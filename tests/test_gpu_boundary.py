@@ -172,6 +172,13 @@ def test_list_verbs_validate_their_arguments():
                                          small.ctypes.data, small.ctypes.data, small.ctypes.data,
                                          small.ctypes.data)
     assert rc == _lib.ELIMIT
+    # a stride whose stride * n wraps to a small byte count is refused before anything is sized
+    # by it, as the check / match / list verbs refuse it
+    state, res = np.zeros(2, dtype=np.uint32), np.zeros(2, dtype=np.int32)
+    rc = _lib.lib().redgpu_advance_batch(exe._h, data.ctypes.data, None, 1 << 63, 2,
+                                         state.ctypes.data, res.ctypes.data)
+    assert rc == _lib.ELIMIT
+    assert _lib.lib().redgpu_dfa_tune(exe._h, data.ctypes.data, None, 1 << 63, 2) == _lib.ELIMIT
 
 
 @pytest.mark.parametrize("ndev", [1, 3])
