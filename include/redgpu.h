@@ -221,6 +221,26 @@ int redgpu_collect_batch(const redgpu_dfa *dfa, const uint8_t *data, const uint6
                          uint64_t stride, uint64_t n, uint64_t cap, uint64_t *counts,
                          int32_t *result, uint64_t *start, uint64_t *end);
 
+/*   redgpu_collect_long <-> Red::collect(string_view, vector<Outcome>&)  include/Red.h:115,
+ *                           lib/Red.cpp:103-116, over ONE long text, chunk-parallel across the
+ *                           device (redgpu_collect_batch walks a line per lane: a single text is
+ *                           one lane).  Positions are absolute in the text.  *count = matches
+ *                           FOUND, which may exceed cap (then only the first cap records are
+ *                           stored: redgpu_collect_batch's rule); start and end may be NULL.
+ *                           chunk_bytes = 0 sizes the chunks automatically; non-zero forces the
+ *                           chunk size (for tests: many chunk borders in a small text).  The
+ *                           records are exactly Red::collect's whatever the chunk size.  The
+ *                           host form uploads the whole text once (the chain of matches crosses
+ *                           all of it): texts larger than device memory are not streamed.
+ *                           redgpu_last_kernel() names the route: "k_collect_long" (chunks),
+ *                           "k_collect_long<closed>" (suffix-closed DFAs without a pure dead
+ *                           state: one attempt covers the text) or "k_collect" (one lane: short
+ *                           texts, DFAs whose attempts cannot end early, cap = 0 on a closed
+ *                           DFA).  Record slots at or past *count may be overwritten. */
+int redgpu_collect_long(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
+                        uint32_t chunk_bytes, uint64_t cap, uint64_t *count, int32_t *result,
+                        uint64_t *start, uint64_t *end);
+
 /*   redgpu_match_all_batch <-> matchAll(exec, string_view, vector<Outcome>&)  include/Matcher.h:127,
  *                              lib/Matcher.cpp:97-102, core include/Matcher.h:711-766 (also
  *                              Red::allMatches, lib/Red.cpp:713-715): ONE anchored walk per line
@@ -317,6 +337,11 @@ int redgpu_match_batches_dev(const redgpu_dfa *dfa, int style, int do_leader,
 int redgpu_collect_batch_dev(const redgpu_dfa *dfa, const uint8_t *data, const uint64_t *offsets,
                              uint64_t stride, uint64_t n, uint64_t cap, uint64_t *counts,
                              int32_t *result, uint64_t *start, uint64_t *end, void *stream);
+
+/* device pointers (count too), asynchronous on stream; nothing is read back to the host */
+int redgpu_collect_long_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
+                            uint32_t chunk_bytes, uint64_t cap, uint64_t *count, int32_t *result,
+                            uint64_t *start, uint64_t *end, void *stream);
 
 int redgpu_match_all_batch_dev(const redgpu_dfa *dfa, int do_leader, const uint8_t *data,
                                const uint64_t *offsets, uint64_t stride, uint64_t n,

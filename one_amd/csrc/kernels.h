@@ -121,6 +121,14 @@ hipError_t launchStreamBatches(const DevDfa &dfa, const Batch *bs, uint32_t nb, 
 hipError_t launchCollect(const DevDfa &dfa, const Batch &b, uint64_t cap, uint64_t *counts,
                          const LaunchCfg &cfg, hipStream_t stream);
 
+// Red::collect over ONE text of n bytes (k_collect_long.h): *count = matches found, the first
+// min(count, cap) records at result/start/end[0..); chunkBytes = 0 chooses the chunk size.
+// *kernelName = the route: "k_collect_long", "k_collect_long<closed>" or "k_collect".
+hipError_t launchCollectLong(const DevDfa &dfa, const uint8_t *data, uint64_t n, uint32_t chunkBytes,
+                             uint64_t cap, uint64_t *count, int32_t *result, uint64_t *start,
+                             uint64_t *end, const LaunchCfg &cfg, hipStream_t stream,
+                             const char **kernelName);
+
 // matchAll per line (include/Matcher.h:711-766): same record layout as launchCollect.
 hipError_t launchMatchAll(const DevDfa &dfa, const Batch &b, uint64_t cap, uint64_t *counts,
                           int doLeader, const LaunchCfg &cfg, hipStream_t stream);

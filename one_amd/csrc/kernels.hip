@@ -26,6 +26,8 @@
 //   k_ragged_long.h   k_ragged_outliers (the long lines of a batch: listed, walked first, huge ones as
 //                     pieces), k_ragged_pieces_fold (the pieces' records -> their lines' Outcomes)
 //   k_lists.h         k_collect, k_matchall, k_matchall_blocks (record lists per line)
+//   k_collect_long.h  k_cl_*: Red::collect over ONE long text, chunk-parallel (guessed entries,
+//                     re-walk rounds, serial finish, scan + scatter)
 //   k_style_blocks.h  k_style_blocks: early-exit styles and odd strides over the block walk
 //   k_misc.h          k_advance, k_replace (+ scan), k_visits, k_walked
 //   k_split.h         line splitting on the device
@@ -67,6 +69,7 @@ namespace {
 #include "k_stream_multi.h"
 #include "k_ragged.h"
 #include "k_lists.h"
+#include "k_collect_long.h"
 #include "k_style_blocks.h"
 #include "k_misc.h"
 #include "k_split.h"
@@ -486,6 +489,62 @@ hipError_t launchCollect(const DevDfa &d, const Batch &b, uint64_t cap, uint64_t
   case REDGPU_TAB_LDS_SPARSE: return CALL(REDGPU_TAB_LDS_SPARSE);                         \
   default: return CALL(REDGPU_TAB_GLOBAL_U32);                                            \
   }
+
+// Red::collect over one text (k_collect_long.h): the chunked chain, the suffix-closed route or
+// the one-lane k_collect - the same records either way.
+hipError_t launchCollectLong(const DevDfa &d, const uint8_t *data, uint64_t n, uint32_t chunkBytes,
+                             uint64_t cap, uint64_t *count, int32_t *result, uint64_t *start,
+                             uint64_t *end, const LaunchCfg &cfg, hipStream_t stream,
+                             const char **kernelName) {
+  // attempts that end early: at a pure dead end, or (suffix-closed) by ending the chain; with
+  // neither (SYN-256) every attempt runs to the end of the text and chunks would be quadratic
+  const bool closed = d.nPureDead == 0 && d.suffixClosed && d.startFreeCount > 4 && cap > 0;
+  const uint64_t c = collectLongChunk(n, chunkBytes, cfg);
+  if (n == 0 || (!chunkBytes && n < kClMinText) || (d.nPureDead == 0 && !closed)) {
+    *kernelName = "k_collect";
+    const Batch b{data, nullptr, n, 1, result, start, end};
+    return launchCollect(d, b, cap, count, cfg, stream);
+  }
+  if (closed) {
+    // no pure dead state and L = SIGMA* L: the attempt at 0 walks the whole text, and nothing can
+    // match behind its last accept - the chain is that one attempt, match<styLast,false>
+    *kernelName = "k_collect_long<closed>";
+    const Batch b{data, nullptr, n, 1, result, start, end};
+    const char *inner = "";
+    hipError_t e = launchBatch(d, b, kMatch, kStyLast, 0, cfg, stream, &inner);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cl_closed, dim3(1), dim3(64), 0, stream, result, count);
+    return hipGetLastError();
+  }
+  *kernelName = "k_collect_long";
+  ClBufs b{};
+  b.m = (n + c - 1) / c;
+  b.chunk = uint32_t(c);
+  b.slots = c < n ? c : n;
+  const uint64_t nb = (b.m + 1023) / 1024;
+  auto up16 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
+  const uint64_t recs = b.m * b.slots;
+  const size_t bytes = up16(b.m * 8) * 3 + up16(nb * 8) + up16(recs * 8) * 2 + up16(recs * 4) * 2 +
+                       up16(b.m * 4) * 2 + 64;
+  void *scratch = nullptr;
+  hipError_t e = raggedScratch(stream, bytes, &scratch);
+  if (e != hipSuccess) return e;
+  uint8_t *q = static_cast<uint8_t *>(scratch);
+  b.ent = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  b.exit = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  b.off = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  b.blockOff = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
+  b.ren = reinterpret_cast<uint64_t *>(q); q += up16(recs * 8);
+  b.rst = reinterpret_cast<uint64_t *>(q); q += up16(recs * 8);
+  b.res = reinterpret_cast<int32_t *>(q); q += up16(recs * 4);
+  b.rat = reinterpret_cast<uint32_t *>(q); q += up16(recs * 4);
+  b.cnt = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
+  b.work = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
+  b.ctl = reinterpret_cast<uint32_t *>(q);
+#define CL_CALL(K) launchCollectLongK<K>(d, data, n, b, cap, count, result, start, end, cfg, stream)
+  REDGPU_KIND_SWITCH(CL_CALL)
+#undef CL_CALL
+}
 
 hipError_t launchMatchAll(const DevDfa &d, const Batch &b, uint64_t cap, uint64_t *counts,
                           int doLeader, const LaunchCfg &cfg, hipStream_t stream) {

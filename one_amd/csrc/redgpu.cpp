@@ -709,6 +709,68 @@ static int listHost(const redgpu_dfa *dfa, int listVerb, const uint8_t *data,
   return call.wait();
 }
 
+// Red::collect over one text, chunk-parallel (k_collect_long.h)
+static int collectLongDev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
+                          uint32_t chunkBytes, uint64_t cap, uint64_t *count, int32_t *result,
+                          uint64_t *start, uint64_t *end, hipStream_t stream) {
+  if (int rc = checkHandle(dfa)) return rc;
+  if (!count) return fail(REDGPU_EAPI, "null count buffer");
+  if (cap && !result) return fail(REDGPU_EAPI, "null result buffer");
+  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
+  if (len >= (1ull << 40)) return fail(REDGPU_ELIMIT, "text too large");
+  if (chunkBytes && (len + chunkBytes - 1) / chunkBytes >= (1ull << 31))
+    return fail(REDGPU_ELIMIT, "too many chunks");
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  const LaunchCfg cfg{dfa->numCUs, (dfa->flags & REDGPU_F_FORCE_GENERIC) ? 1 : 0};
+  const char *name = "";
+  const hipError_t e = launchCollectLong(dfa->im->dev, data, len, chunkBytes, cap, count, result,
+                                         start, end, cfg, stream, &name);
+  tlsKernel = name;
+  if (e != hipSuccess) return failHip(e, "kernel launch");
+  return REDGPU_OK;
+}
+
+int redgpu_collect_long_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
+                            uint32_t chunk_bytes, uint64_t cap, uint64_t *count, int32_t *result,
+                            uint64_t *start, uint64_t *end, void *stream) {
+  return collectLongDev(dfa, data, len, chunk_bytes, cap, count, result, start, end,
+                        static_cast<hipStream_t>(stream));
+}
+
+// the whole text goes up once (the chain crosses all of it), the records come back
+int redgpu_collect_long(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
+                        uint32_t chunk_bytes, uint64_t cap, uint64_t *count, int32_t *result,
+                        uint64_t *start, uint64_t *end) {
+  if (int rc = checkHandle(dfa)) return rc;
+  if (!count) return fail(REDGPU_EAPI, "null count buffer");
+  if (cap && !result) return fail(REDGPU_EAPI, "null result buffer");
+  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
+  if (cap > (~0ull / 16)) return fail(REDGPU_ELIMIT, "cap too large");
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dCnt = call.buf<uint64_t>(kSlAux0, 1, "count");
+  int32_t *dRes = call.buf<int32_t>(kSlRes, cap + 1, "result");
+  uint64_t *dStart = start ? call.buf<uint64_t>(kSlStart, cap + 1, "start") : nullptr;
+  uint64_t *dEnd = end ? call.buf<uint64_t>(kSlEnd, cap + 1, "end") : nullptr;
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return collectLongDev(dfa, dData, len, chunk_bytes, cap, dCnt, cap ? dRes : nullptr, dStart,
+                          dEnd, call.stream());
+  });
+  uint64_t found = 0;
+  call.download(&found, dCnt, 1, "count");
+  if (int rc = call.wait()) return rc;
+  *count = found;
+  const uint64_t got = found < cap ? found : cap;
+  if (got) {
+    call.download(result, dRes, got, "result");
+    if (start) call.download(start, dStart, got, "start");
+    if (end) call.download(end, dEnd, got, "end");
+  }
+  return call.wait();
+}
+
 int redgpu_replace_batch_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
                              const uint64_t *offsets, uint64_t stride, uint64_t n,
                              const uint8_t *repl, uint64_t repl_len, uint64_t max_count,
