@@ -281,6 +281,35 @@ int redgpu_replace_batch(const redgpu_dfa *dfa, int style, int do_leader, const 
                          uint64_t repl_len, uint64_t max_count, uint64_t *counts,
                          uint64_t *out_offsets, uint8_t *out, uint64_t out_cap);
 
+/*   redgpu_replace_long <-> replace<style,doLeader>(exec, ptr, len, repl, out, max)
+ *                           include/Matcher.h:186-191, core :643-706, which Red's twenty
+ *                           replaceOne* / replaceAll* and Red::replace end in (include/Red.h:
+ *                           139-238), over ONE long text, chunk-parallel across the device
+ *                           (redgpu_replace_batch walks a line per lane: a single text is one
+ *                           lane).  *count = replaceCore's return value, *out_len = the size of
+ *                           its `out` string; both are always written.  out may be NULL (sizes
+ *                           only); with out != NULL the first min(*out_len, out_cap) bytes of the
+ *                           rewritten text are written (redgpu_collect_long's "first cap records"
+ *                           rule applied to bytes; bytes at or past *out_len may be overwritten,
+ *                           up to out_cap).  out must not overlap data.  max_count is
+ *                           replaceCore's `max`: only the first max_count matches in chain order
+ *                           are replaced, everything behind them is copied (0 copies the text;
+ *                           Red's replaceOne* is max_count = 1).  style is any of the five;
+ *                           do_leader as in redgpu_replace_batch.  chunk_bytes as in
+ *                           redgpu_collect_long (0 = automatic, non-zero forces it, for tests).
+ *                           The output is exactly the reference's whatever the chunk size.
+ *                           redgpu_last_kernel() names the route: "k_replace_long" (chunks) or
+ *                           "k_replace_long<one>" (one chunk, so one lane runs the chain in
+ *                           order: short texts, and DFAs without a pure dead state under
+ *                           styLast / styFull, whose failing attempts cannot end early); both
+ *                           assemble the output with the same tile-parallel copy.  The host form
+ *                           uploads the text once, sizes the device output from the first phase's
+ *                           *out_len and downloads min(*out_len, out_cap) bytes. */
+int redgpu_replace_long(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
+                        uint64_t len, uint32_t chunk_bytes, const uint8_t *repl, uint64_t repl_len,
+                        uint64_t max_count, uint64_t *count, uint64_t *out_len, uint8_t *out,
+                        uint64_t out_cap);
+
 /* ---- the same verbs over DEVICE-resident buffers, asynchronous on `stream` ---------------
  * data/offsets/result/start/end are device pointers on the handle's device; `stream` is a
  * hipStream_t (NULL = the default stream).  Nothing is copied or synchronised; the only
@@ -351,6 +380,13 @@ int redgpu_match_all_batch_dev(const redgpu_dfa *dfa, int do_leader, const uint8
 int redgpu_advance_batch_dev(const redgpu_dfa *dfa, const uint8_t *data, const uint64_t *offsets,
                              uint64_t stride, uint64_t n, uint32_t *state, int32_t *result,
                              void *stream);
+
+/* every pointer is device memory, count and out_len too; asynchronous on stream; nothing is
+ * read back to the host */
+int redgpu_replace_long_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
+                            uint64_t len, uint32_t chunk_bytes, const uint8_t *repl,
+                            uint64_t repl_len, uint64_t max_count, uint64_t *count,
+                            uint64_t *out_len, uint8_t *out, uint64_t out_cap, void *stream);
 
 /* repl is device memory too */
 int redgpu_replace_batch_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,

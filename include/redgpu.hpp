@@ -386,6 +386,25 @@ size_t replace(const Executable &exec, std::string_view sv, std::string_view rep
   return detail::replaceOne(exec, sv, repl, out, max, style, doLeader);
 }
 
+// replace(exec, sv, repl, out, max, style) over one long text, chunk-parallel on the device
+// (redgpu_replace_long): the run-time-style signature of lib/Matcher.cpp:72-92, doLeader = true.
+// Room for about the input's length first, one more call with the exact size otherwise.
+inline size_t replaceLong(const Executable &exec, std::string_view sv, std::string_view repl,
+                          std::string &out, size_t max, Style style) {
+  uint64_t cnt = 0, len = 0;
+  out.assign(sv.size() + 64, '\0');
+  for (int pass = 0; pass < 2; ++pass) {
+    throwOnError(redgpu_replace_long(exec.handle(), style, 1,
+                                     reinterpret_cast<const Byte *>(sv.data()), sv.size(), 0,
+                                     reinterpret_cast<const Byte *>(repl.data()), repl.size(), max,
+                                     &cnt, &len, reinterpret_cast<Byte *>(out.data()), out.size()));
+    if (len <= out.size()) break;
+    out.assign(size_t(len), '\0');
+  }
+  out.resize(size_t(len));
+  return size_t(cnt);
+}
+
 // StatefulMatcher: include/Matcher.h:770-792.  advance(Byte) as in the reference, plus
 // advance(ptr, len) for a whole chunk per launch.  exec must outlive this object.
 class StatefulMatcher {

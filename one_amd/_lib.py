@@ -142,6 +142,12 @@ def lib() -> C.CDLL:
         l.redgpu_replace_batch.restype = C.c_int
         l.redgpu_replace_batch.argtypes = [vp, i32, i32, vp, vp, u64, u64, vp, u64, u64, vp, vp,
                                            vp, u64]
+        l.redgpu_replace_long.restype = C.c_int
+        l.redgpu_replace_long.argtypes = [vp, i32, i32, vp, u64, C.c_uint32, vp, u64, u64, vp, vp,
+                                          vp, u64]
+        l.redgpu_replace_long_dev.restype = C.c_int
+        l.redgpu_replace_long_dev.argtypes = [vp, i32, i32, vp, u64, C.c_uint32, vp, u64, u64, vp,
+                                              vp, vp, u64, vp]
         l.redgpu_replace_batch_dev.restype = C.c_int
         l.redgpu_replace_batch_dev.argtypes = [vp, i32, i32, vp, vp, u64, u64, vp, u64, u64, vp,
                                                vp, vp, u64, vp]

@@ -26,6 +26,9 @@
 // (chunk-relative) + start u64 + end u64 = 24 bytes per slot, so ~24 bytes of scratch per text
 // byte.  (A record's start is the attempt's last "left the initial state", Matcher.h:582-587:
 // two attempts can report the same one, so chains are compared by attempt position.)
+// The same chain serves replaceCore over one text (k_replace_long.h): every kernel here takes a
+// MODE - kClCollect is the above, kClReplace swaps the attempt for replaceCore's (ClAttempt: style
+// and leader test) and keeps lean slots (attempt position + end, 12 bytes; res and rst unused).
 #pragma once
 
 constexpr int kClRounds = 4;
@@ -56,13 +59,25 @@ struct ClBufs {
   uint32_t chunk;
 };
 
+// MODE of the chain kernels: whose attempt runs at a position, and what a record slot keeps
+constexpr int kClCollect = 0;  // k_collect's attempt (searchCore <styLast, false>); result, at, start, end
+constexpr int kClReplace = 1;  // replaceCore's (k_replace_long.h): ClAttempt's style and leader; at, end
+
+struct ClAttempt {
+  int style = kStyLast;
+  int lead = 0;
+};
+
 // The chain over the attempt positions [q, hi) of p[0, n).  emit(result, at, start, end) per match,
 // false = stop here (the return value is then meaningless).  Returns the exit, or kClOpen when the
-// attempts walked more than `budget` bytes past their first one.  The attempt is k_collect's.
-template <class T, class E>
+// attempts walked more than `budget` bytes past their first one.  The attempt is k_collect's, or
+// (kClReplace) replaceCore's under a.style with the leader test: Instant stops at the first
+// accept, First and Tangent at the first non-accept behind one (First also where the result
+// changes), Full forgets its accept at every non-accept; result and start are then 0.
+template <int MODE = kClCollect, class T, class E>
 __device__ __forceinline__ uint64_t clChain(const T &tab, const LaneCtx &c, const StartFilter &flt,
                                             const uint8_t *p, uint64_t n, uint64_t q, uint64_t hi,
-                                            uint64_t budget, E &&emit) {
+                                            uint64_t budget, E &&emit, const ClAttempt a = ClAttempt{}) {
   uint64_t pos = q;
   while (pos < hi) {
     int how = 0;  // 1 = a match, 2 = suffix-closed stop, 3 = out of budget
@@ -76,26 +91,46 @@ __device__ __forceinline__ uint64_t clChain(const T &tab, const LaneCtx &c, cons
       if (st >= c.firstAccept) { aS = st; me = i + 1; any = true; }
       else if (st < c.nPureDead) return true;
       else if (nextByte != kNoPeek && tab.next(st, nextByte) < c.nPureDead) return true;
+      int32_t prev = 0;  // (kClReplace, styFirst) the result of the accepts so far
+      if constexpr (MODE == kClReplace) {
+        if (a.lead && !lookingAt(c, p, i, n)) return true;
+        if (any && a.style == kStyFirst) prev = c.res[st];
+      }
       const uint64_t lim = n - i - 1 > budget ? i + 1 + budget : n;
       uint64_t at = i + 1;
       auto stepOne = [&](uint32_t b2, uint64_t q2) -> bool {
         const uint32_t was = st;
         st = tab.next(st, b2);
         at = q2 + 1;
-        if (was == c.init && st != was) ms = q2;
         const bool acc = st >= c.firstAccept;
-        if (acc) { aS = st; me = q2 + 1; any = true; }
-        return acc || st >= c.nPureDead;
+        if constexpr (MODE == kClReplace) {
+          if (acc) {
+            if (a.style == kStyFirst) {
+              const int32_t r = c.res[st];
+              if (prev && r != prev) return false;
+              prev = r;
+            }
+            aS = st; me = q2 + 1; any = true;
+            return a.style != kStyInstant;
+          }
+          if (a.style == kStyFull) any = false;
+          else if (any && (a.style == kStyFirst || a.style == kStyTangent)) return false;
+          return st >= c.nPureDead;
+        } else {
+          if (was == c.init && st != was) ms = q2;
+          if (acc) { aS = st; me = q2 + 1; any = true; }
+          return acc || st >= c.nPureDead;
+        }
       };
       uint64_t q2 = i + 1;
-      bool alive = true;
+      bool alive = !(MODE == kClReplace && any && a.style == kStyInstant);
       for (uint32_t k = 0; k < 6 && q2 < lim && alive; ++k, ++q2) alive = stepOne(uint32_t(p[q2]), q2);
       if (alive)
         walkBytes(p, q2, lim, [&](uint32_t b2, uint64_t q3) -> bool { return alive = stepOne(b2, q3); });
       budget -= at - i - 1;
       if (alive && lim < n) { how = 3; return false; }
       if (!any) {
-        if (c.suffixClosed && alive) { how = 2; return false; }  // L = SIGMA* L
+        if (c.suffixClosed && alive && !(MODE == kClReplace && a.lead)) { how = 2; return false; }  // L = SIGMA* L
         return true;
       }
       how = 1; accS = aS; mA = i; mS = ms; mE = me;
@@ -104,7 +139,7 @@ __device__ __forceinline__ uint64_t clChain(const T &tab, const LaneCtx &c, cons
     if (how == 0) return hi;
     if (how == 2) return n;
     if (how == 3) return kClOpen;
-    if (!emit(c.res[accS], mA, mS, mE)) return 0;
+    if (!emit(MODE == kClReplace ? 0 : c.res[accS], mA, mS, mE)) return 0;
     pos = mE;
   }
   return pos;
@@ -113,9 +148,10 @@ __device__ __forceinline__ uint64_t clChain(const T &tab, const LaneCtx &c, cons
 // chunk j walked again from entry q: phase 1 finds where the new chain meets a record start of
 // the old one (only when the old walk finished: its exit is known), phase 2 moves the old tail
 // behind the new head and writes the head.  Without a meeting point the new chain is the record.
-template <class T>
+template <int MODE = kClCollect, class T>
 __device__ void clRewalk(const T &tab, const LaneCtx &c, const StartFilter &flt, const uint8_t *p,
-                         uint64_t n, const ClBufs &b, uint64_t j, uint64_t q, uint64_t budget) {
+                         uint64_t n, const ClBufs &b, uint64_t j, uint64_t q, uint64_t budget,
+                         const ClAttempt a = ClAttempt{}) {
   const uint64_t lo = j * b.chunk;
   const uint64_t hi = lo + b.chunk < n ? lo + b.chunk : n;
   const uint64_t base = j * b.slots;
@@ -124,15 +160,15 @@ __device__ void clRewalk(const T &tab, const LaneCtx &c, const StartFilter &flt,
   const bool conv = oldExit != kClOpen;
   uint32_t r = 0, k = 0;
   bool hit = false;
-  const uint64_t ex = clChain(tab, c, flt, p, n, q, hi, budget, [&](int32_t, uint64_t a, uint64_t, uint64_t) {
+  const uint64_t ex = clChain<MODE>(tab, c, flt, p, n, q, hi, budget, [&](int32_t, uint64_t at, uint64_t, uint64_t) {
     if (conv) {
-      const uint32_t rel = uint32_t(a - lo);
+      const uint32_t rel = uint32_t(at - lo);
       while (k < cnt0 && b.rat[base + k] < rel) ++k;
       if (k < cnt0 && b.rat[base + k] == rel) { hit = true; return false; }
     }
     ++r;
     return true;
-  });
+  }, a);
   if (!hit && ex == kClOpen) {
     b.exit[j] = kClOpen;
     b.cnt[j] = 0;
@@ -142,16 +178,20 @@ __device__ void clRewalk(const T &tab, const LaneCtx &c, const StartFilter &flt,
     const uint32_t tail = cnt0 - k;
     if (r < k) {
       for (uint32_t t = 0; t < tail; ++t) {
-        b.res[base + r + t] = b.res[base + k + t];
+        if constexpr (MODE == kClCollect) {
+          b.res[base + r + t] = b.res[base + k + t];
+          b.rst[base + r + t] = b.rst[base + k + t];
+        }
         b.rat[base + r + t] = b.rat[base + k + t];
-        b.rst[base + r + t] = b.rst[base + k + t];
         b.ren[base + r + t] = b.ren[base + k + t];
       }
     } else if (r > k) {
       for (uint32_t t = tail; t-- > 0;) {
-        b.res[base + r + t] = b.res[base + k + t];
+        if constexpr (MODE == kClCollect) {
+          b.res[base + r + t] = b.res[base + k + t];
+          b.rst[base + r + t] = b.rst[base + k + t];
+        }
         b.rat[base + r + t] = b.rat[base + k + t];
-        b.rst[base + r + t] = b.rst[base + k + t];
         b.ren[base + r + t] = b.ren[base + k + t];
       }
     }
@@ -162,13 +202,15 @@ __device__ void clRewalk(const T &tab, const LaneCtx &c, const StartFilter &flt,
   }
   if (r == 0) return;
   uint32_t w = 0;
-  (void)clChain(tab, c, flt, p, n, q, hi, budget, [&](int32_t rv, uint64_t a, uint64_t s, uint64_t e) {
-    b.res[base + w] = rv;
-    b.rat[base + w] = uint32_t(a - lo);
-    b.rst[base + w] = s;
+  (void)clChain<MODE>(tab, c, flt, p, n, q, hi, budget, [&](int32_t rv, uint64_t at, uint64_t s, uint64_t e) {
+    if constexpr (MODE == kClCollect) {
+      b.res[base + w] = rv;
+      b.rst[base + w] = s;
+    }
+    b.rat[base + w] = uint32_t(at - lo);
     b.ren[base + w] = e;
     return ++w < r;
-  });
+  }, a);
 }
 
 template <int KIND>
@@ -190,9 +232,9 @@ __global__ void __launch_bounds__(64) k_cl_init(ClBufs b) {
 }
 
 // every chunk from its guessed entry (chunk 0 from 0, exactly)
-template <int KIND, int kThreads>
+template <int KIND, int kThreads, int MODE = kClCollect>
 __global__ void __launch_bounds__(kThreads)
-k_cl_walk(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, uint64_t budget) {
+k_cl_walk(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, uint64_t budget, ClAttempt a) {
   extern __shared__ __align__(16) uint8_t lds[];
   const Tab<KIND> tab = stageTab<KIND, kThreads>(d, lds);
   const LaneCtx c = clCtx<KIND>(d, lds);
@@ -203,20 +245,22 @@ k_cl_walk(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, uint64_t budget) {
     const uint64_t hi = lo + b.chunk < n ? lo + b.chunk : n;
     uint64_t q = 0;
     if (j) {
-      q = clChain(tab, c, flt, p, n, lo > kClWarm ? lo - kClWarm : 0, lo, budget,
-                  [](int32_t, uint64_t, uint64_t, uint64_t) { return true; });
+      q = clChain<MODE>(tab, c, flt, p, n, lo > kClWarm ? lo - kClWarm : 0, lo, budget,
+                        [](int32_t, uint64_t, uint64_t, uint64_t) { return true; }, a);
       if (q == kClOpen) q = lo;
     }
     const uint64_t base = j * b.slots;
     uint32_t k = 0;
-    const uint64_t ex = clChain(tab, c, flt, p, n, q, hi, budget, [&](int32_t rv, uint64_t a, uint64_t s, uint64_t e) {
-      b.res[base + k] = rv;
-      b.rat[base + k] = uint32_t(a - lo);
-      b.rst[base + k] = s;
+    const uint64_t ex = clChain<MODE>(tab, c, flt, p, n, q, hi, budget, [&](int32_t rv, uint64_t at, uint64_t s, uint64_t e) {
+      if constexpr (MODE == kClCollect) {
+        b.res[base + k] = rv;
+        b.rst[base + k] = s;
+      }
+      b.rat[base + k] = uint32_t(at - lo);
       b.ren[base + k] = e;
       ++k;
       return true;
-    });
+    }, a);
     b.ent[j] = q;
     b.exit[j] = ex;
     b.cnt[j] = ex == kClOpen ? 0u : k;
@@ -235,9 +279,10 @@ __global__ void __launch_bounds__(256) k_cl_resolve(ClBufs b, int round) {
   }
 }
 
-template <int KIND, int kThreads>
+template <int KIND, int kThreads, int MODE = kClCollect>
 __global__ void __launch_bounds__(kThreads)
-k_cl_rewalk(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, int round, uint64_t budget) {
+k_cl_rewalk(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, int round, uint64_t budget,
+            ClAttempt a) {
   extern __shared__ __align__(16) uint8_t lds[];
   if (b.ctl[round] == 0) return;  // uniform: nothing queued this round
   const Tab<KIND> tab = stageTab<KIND, kThreads>(d, lds);
@@ -247,7 +292,7 @@ k_cl_rewalk(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, int round, uint64_
   const uint64_t step = uint64_t(gridDim.x) * kThreads;
   for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < cnt; i += step) {
     const uint32_t j = b.work[i];
-    clRewalk(tab, c, flt, p, n, b, j, b.ent[j], budget);
+    clRewalk<MODE>(tab, c, flt, p, n, b, j, b.ent[j], budget, a);
   }
 }
 
@@ -263,8 +308,9 @@ __global__ void __launch_bounds__(256) k_cl_check(ClBufs b) {
 }
 
 // one lane, in order, from the first open chunk: every exit it reads is final
-template <int KIND>
-__global__ void __launch_bounds__(64) k_cl_serial(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b) {
+template <int KIND, int MODE = kClCollect>
+__global__ void __launch_bounds__(64)
+k_cl_serial(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, ClAttempt a) {
   extern __shared__ __align__(16) uint8_t lds[];
   if (b.ctl[kClRounds] >= b.m) return;  // uniform: everything is final
   const Tab<KIND> tab = stageTab<KIND, 64>(d, lds);
@@ -275,7 +321,7 @@ __global__ void __launch_bounds__(64) k_cl_serial(DevDfa d, const uint8_t *p, ui
     const uint64_t want = j ? b.exit[j - 1] : 0;
     if (b.ent[j] == want && b.exit[j] != kClOpen) continue;
     b.ent[j] = want;
-    clRewalk(tab, c, flt, p, n, b, j, want, kClOpen);
+    clRewalk<MODE>(tab, c, flt, p, n, b, j, want, kClOpen, a);
   }
 }
 
@@ -342,16 +388,17 @@ __global__ void __launch_bounds__(64) k_cl_closed(const int32_t *result, uint64_
   if (threadIdx.x == 0) *count = result[0] > 0 ? 1u : 0u;
 }
 
-template <int KIND>
-hipError_t launchCollectLongK(const DevDfa &d, const uint8_t *p, uint64_t n, const ClBufs &b,
-                              uint64_t cap, uint64_t *count, int32_t *result, uint64_t *start,
-                              uint64_t *end, const LaunchCfg &cfg, hipStream_t stream) {
+// the chain of every chunk, final: walk, rounds, check + serial finish, and the scan of the counts
+template <int KIND, int MODE>
+hipError_t launchClChain(const DevDfa &d, const uint8_t *p, uint64_t n, const ClBufs &b,
+                         const ClAttempt a, uint64_t *count, const LaunchCfg &cfg,
+                         hipStream_t stream) {
   constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
   constexpr int kThreads = kLds ? 1024 : 256;
   const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
-  hipError_t e = setLds(k_cl_walk<KIND, kThreads>, ldsBytes);
-  if (e == hipSuccess) e = setLds(k_cl_rewalk<KIND, kThreads>, ldsBytes);
-  if (e == hipSuccess) e = setLds(k_cl_serial<KIND>, ldsBytes);
+  hipError_t e = setLds(k_cl_walk<KIND, kThreads, MODE>, ldsBytes);
+  if (e == hipSuccess) e = setLds(k_cl_rewalk<KIND, kThreads, MODE>, ldsBytes);
+  if (e == hipSuccess) e = setLds(k_cl_serial<KIND, MODE>, ldsBytes);
   if (e != hipSuccess) return e;
   const uint64_t perCu = kLds ? (ldsBytes <= 80 * 1024 ? 2 : 1) : 8;
   uint64_t blocks = (b.m + kThreads - 1) / kThreads;
@@ -362,18 +409,27 @@ hipError_t launchCollectLongK(const DevDfa &d, const uint8_t *p, uint64_t n, con
   // (speculative attempts: 16 bytes per chunk byte past their first, and 1 KiB)
   const uint64_t budget = uint64_t(b.chunk) * 16 + 1024;
   hipLaunchKernelGGL(k_cl_init, dim3(1), dim3(64), 0, stream, b);
-  hipLaunchKernelGGL((k_cl_walk<KIND, kThreads>), dim3(uint32_t(blocks)), dim3(kThreads), ldsBytes,
-                     stream, d, p, n, b, budget);
+  hipLaunchKernelGGL((k_cl_walk<KIND, kThreads, MODE>), dim3(uint32_t(blocks)), dim3(kThreads),
+                     ldsBytes, stream, d, p, n, b, budget, a);
   for (int round = 0; round < kClRounds; ++round) {
     hipLaunchKernelGGL(k_cl_resolve, dim3(uint32_t(small)), dim3(256), 0, stream, b, round);
-    hipLaunchKernelGGL((k_cl_rewalk<KIND, kThreads>), dim3(uint32_t(blocks)), dim3(kThreads),
-                       ldsBytes, stream, d, p, n, b, round, budget);
+    hipLaunchKernelGGL((k_cl_rewalk<KIND, kThreads, MODE>), dim3(uint32_t(blocks)), dim3(kThreads),
+                       ldsBytes, stream, d, p, n, b, round, budget, a);
   }
   hipLaunchKernelGGL(k_cl_check, dim3(uint32_t(small)), dim3(256), 0, stream, b);
-  hipLaunchKernelGGL((k_cl_serial<KIND>), dim3(1), dim3(64), ldsBytes, stream, d, p, n, b);
+  hipLaunchKernelGGL((k_cl_serial<KIND, MODE>), dim3(1), dim3(64), ldsBytes, stream, d, p, n, b, a);
   const uint64_t nb = (b.m + 1023) / 1024;
   hipLaunchKernelGGL(k_cl_scan1, dim3(uint32_t(nb)), dim3(1024), 0, stream, b);
   hipLaunchKernelGGL(k_cl_scan2, dim3(1), dim3(1024), 0, stream, b, nb, count);
+  return hipGetLastError();
+}
+
+template <int KIND>
+hipError_t launchCollectLongK(const DevDfa &d, const uint8_t *p, uint64_t n, const ClBufs &b,
+                              uint64_t cap, uint64_t *count, int32_t *result, uint64_t *start,
+                              uint64_t *end, const LaunchCfg &cfg, hipStream_t stream) {
+  const hipError_t e = launchClChain<KIND, kClCollect>(d, p, n, b, ClAttempt{}, count, cfg, stream);
+  if (e != hipSuccess) return e;
   if (cap) {
     uint64_t sb = (b.m + 3) / 4;
     if (sb > uint64_t(cfg.numCUs) * 16) sb = uint64_t(cfg.numCUs) * 16;

@@ -143,6 +143,16 @@ hipError_t launchAdvance(const DevDfa &dfa, const Batch &b, uint32_t *state, con
 hipError_t launchVisits(const DevDfa &dfa, const Batch &b, uint32_t *hist, const LaunchCfg &cfg,
                         hipStream_t stream);
 
+// replaceCore over ONE text of n bytes (k_replace_long.h): *count = replacements made (at most
+// max), *outLen = the rewritten text's length, its first min(*outLen, outCap) bytes in out (may
+// be null).  phases: 1 = count and size, 2 = write out from what phase 1 left in this stream's
+// scratch, 3 = both.  *kernelName = the route: "k_replace_long" or "k_replace_long<one>".
+hipError_t launchReplaceLong(const DevDfa &dfa, int style, int doLeader, const uint8_t *data,
+                             uint64_t n, uint32_t chunkBytes, const uint8_t *repl, uint64_t replLen,
+                             uint64_t max, uint64_t *count, uint64_t *outLen, uint8_t *out,
+                             uint64_t outCap, int phases, const LaunchCfg &cfg, hipStream_t stream,
+                             const char **kernelName);
+
 // replaceCore per line (include/Matcher.h:643-706): counts[n], outOffsets[n + 1] (exclusive scan
 // of the rewritten lengths, [n] = total) always; with out != nullptr also the rewritten bytes of
 // every line that fits below outCap.  repl is device memory.

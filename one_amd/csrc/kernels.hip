@@ -26,6 +26,8 @@
 //   k_ragged_long.h   k_ragged_outliers (the long lines of a batch: listed, walked first, huge ones as
 //                     pieces), k_ragged_pieces_fold (the pieces' records -> their lines' Outcomes)
 //   k_lists.h         k_collect, k_matchall, k_matchall_blocks (record lists per line)
+//   k_replace_long.h  k_rl_*: replaceCore over ONE long text: k_collect_long.h's chain under any
+//                     style, then the assembly (sums, scans, a tile-driven copy/insert)
 //   k_collect_long.h  k_cl_*: Red::collect over ONE long text, chunk-parallel (guessed entries,
 //                     re-walk rounds, serial finish, scan + scatter)
 //   k_style_blocks.h  k_style_blocks: early-exit styles and odd strides over the block walk
@@ -70,6 +72,7 @@ namespace {
 #include "k_ragged.h"
 #include "k_lists.h"
 #include "k_collect_long.h"
+#include "k_replace_long.h"
 #include "k_style_blocks.h"
 #include "k_misc.h"
 #include "k_split.h"
@@ -544,6 +547,67 @@ hipError_t launchCollectLong(const DevDfa &d, const uint8_t *data, uint64_t n, u
 #define CL_CALL(K) launchCollectLongK<K>(d, data, n, b, cap, count, result, start, end, cfg, stream)
   REDGPU_KIND_SWITCH(CL_CALL)
 #undef CL_CALL
+}
+
+// replaceCore over one text (k_replace_long.h): the chain of k_collect_long.h under the call's
+// style and leader setting, then the assembly.  phases: 1 = the chain, *count and *outLen; 2 = the
+// copy into out, from the scratch phase 1 left on this stream; 3 = both.
+hipError_t launchReplaceLong(const DevDfa &d, int style, int doLeader, const uint8_t *data,
+                             uint64_t n, uint32_t chunkBytes, const uint8_t *repl, uint64_t replLen,
+                             uint64_t max, uint64_t *count, uint64_t *outLen, uint8_t *out,
+                             uint64_t outCap, int phases, const LaunchCfg &cfg, hipStream_t stream,
+                             const char **kernelName) {
+  *kernelName = "k_replace_long";
+  if (n == 0) {
+    if (phases & 1) hipLaunchKernelGGL(k_rl_empty, dim3(1), dim3(64), 0, stream, count, outLen);
+    return hipGetLastError();
+  }
+  const ClAttempt a{style, doLeader && d.leaderLen > 0 ? 1 : 0};
+  // one chunk (the chain in order, on one lane) for a short text, and where failing attempts
+  // cannot end early: no pure dead state, under a style that walks on behind an accept
+  const bool early = d.nPureDead > 0 || style == kStyInstant || style == kStyFirst ||
+                     style == kStyTangent;
+  uint64_t c = collectLongChunk(n, chunkBytes, cfg);
+  if (!chunkBytes && (n < kClMinText || !early)) c = n;
+  if (c > (1ull << 30)) c = 1ull << 30;  // (positions inside a chunk are 32-bit)
+  if (c >= n) *kernelName = "k_replace_long<one>";
+  ClBufs b{};
+  RlBufs r{};
+  b.m = (n + c - 1) / c;
+  b.chunk = uint32_t(c < n ? c : n);
+  b.slots = b.chunk;
+  const uint64_t nb = (b.m + 1023) / 1024;
+  auto up16 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
+  const uint64_t recs = b.m * b.slots;
+  const size_t bytes = up16(b.m * 8) * 5 + up16(nb * 8) * 3 + up16(recs * 8) + up16(recs * 4) +
+                       up16(b.m * 4) * 2 + 64;
+  void *scratch = nullptr;
+  hipError_t e = raggedScratch(stream, bytes, &scratch);
+  if (e != hipSuccess) return e;
+  uint8_t *q = static_cast<uint8_t *>(scratch);
+  b.ent = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  b.exit = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  b.off = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  r.rem = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  r.cov = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  b.blockOff = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
+  r.blockRem = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
+  r.blockCov = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
+  b.ren = reinterpret_cast<uint64_t *>(q); q += up16(recs * 8);
+  b.rat = reinterpret_cast<uint32_t *>(q); q += up16(recs * 4);
+  b.cnt = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
+  b.work = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
+  b.ctl = reinterpret_cast<uint32_t *>(q);
+  if (phases & 1) {
+    e = [&]() -> hipError_t {
+#define RL_CALL(K) launchClChain<K, kClReplace>(d, data, n, b, a, count, cfg, stream)
+      REDGPU_KIND_SWITCH(RL_CALL)
+#undef RL_CALL
+    }();
+    if (e != hipSuccess) return e;
+  }
+  return launchRlAssemble(data, n, b, r, repl, replLen, max, count, outLen, (phases & 1) != 0,
+                          (phases & 2) ? out : nullptr, outCap, cfg, stream);
 }
 
 hipError_t launchMatchAll(const DevDfa &d, const Batch &b, uint64_t cap, uint64_t *counts,

@@ -835,6 +835,85 @@ int redgpu_replace_batch(const redgpu_dfa *dfa, int style, int do_leader, const 
   return call.wait();
 }
 
+// the arguments of both forms, in this order: the handle, the style, the buffers, the limits, and
+// last whether the handle has a device image (so a device-less handle still names a bad argument)
+static int checkReplaceLong(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
+                            uint32_t chunkBytes, const uint8_t *repl, uint64_t replLen,
+                            const uint64_t *count, const uint64_t *outLen) {
+  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
+  if (int rc = checkStyle(style)) return rc;
+  if (!count) return fail(REDGPU_EAPI, "null count buffer");
+  if (!outLen) return fail(REDGPU_EAPI, "null out_len buffer");
+  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
+  if (replLen && !repl) return fail(REDGPU_EAPI, "null replacement");
+  if (len >= (1ull << 40)) return fail(REDGPU_ELIMIT, "text too large");
+  if (chunkBytes && (len + chunkBytes - 1) / chunkBytes >= (1ull << 31))
+    return fail(REDGPU_ELIMIT, "too many chunks");
+  return checkHandle(dfa);
+}
+
+// replaceCore over one text, chunk-parallel (k_replace_long.h); phases as launchReplaceLong's
+static int replaceLongDev(const redgpu_dfa *dfa, int style, int doLeader, const uint8_t *data,
+                          uint64_t len, uint32_t chunkBytes, const uint8_t *repl, uint64_t replLen,
+                          uint64_t maxCount, uint64_t *count, uint64_t *outLen, uint8_t *out,
+                          uint64_t outCap, int phases, hipStream_t stream) {
+  if (int rc = checkReplaceLong(dfa, style, data, len, chunkBytes, repl, replLen, count, outLen))
+    return rc;
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  const LaunchCfg cfg{dfa->numCUs, 0};
+  const char *name = "";
+  const hipError_t e = launchReplaceLong(dfa->im->dev, style, doLeader ? 1 : 0, data, len,
+                                         chunkBytes, repl, replLen, maxCount, count, outLen, out,
+                                         outCap, phases, cfg, stream, &name);
+  tlsKernel = name;
+  if (e != hipSuccess) return failHip(e, "kernel launch");
+  return REDGPU_OK;
+}
+
+int redgpu_replace_long_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
+                            uint64_t len, uint32_t chunk_bytes, const uint8_t *repl,
+                            uint64_t repl_len, uint64_t max_count, uint64_t *count,
+                            uint64_t *out_len, uint8_t *out, uint64_t out_cap, void *stream) {
+  return replaceLongDev(dfa, style, do_leader, data, len, chunk_bytes, repl, repl_len, max_count,
+                        count, out_len, out, out_cap, 3, static_cast<hipStream_t>(stream));
+}
+
+// the text goes up once; phase 1 leaves the records in the stream's scratch and the sizes, the
+// device output is sized from them, phase 2 assembles it: the text is walked once
+int redgpu_replace_long(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
+                        uint64_t len, uint32_t chunk_bytes, const uint8_t *repl, uint64_t repl_len,
+                        uint64_t max_count, uint64_t *count, uint64_t *out_len, uint8_t *out,
+                        uint64_t out_cap) {
+  if (int rc = checkReplaceLong(dfa, style, data, len, chunk_bytes, repl, repl_len, count, out_len))
+    return rc;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint8_t *dRepl = call.buf<uint8_t>(kSlAux0, repl_len, "repl");
+  uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 2, "sizes");
+  call.upload(dData, data, len, "data");
+  call.upload(dRepl, repl, repl_len, "repl");
+  call.run([&] {
+    return replaceLongDev(dfa, style, do_leader, dData, len, chunk_bytes, dRepl, repl_len,
+                          max_count, dSizes, dSizes + 1, nullptr, 0, 1, call.stream());
+  });
+  uint64_t sizes[2] = {0, 0};
+  call.download(sizes, dSizes, 2, "sizes");
+  if (int rc = call.wait()) return rc;
+  *count = sizes[0];
+  *out_len = sizes[1];
+  const uint64_t put = sizes[1] < out_cap ? sizes[1] : out_cap;
+  if (!out || !put) return REDGPU_OK;
+  // (the streams are drained: growing the slot waits for nothing)
+  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
+  call.run([&] {
+    return replaceLongDev(dfa, style, do_leader, dData, len, chunk_bytes, dRepl, repl_len,
+                          max_count, dSizes, dSizes + 1, dOut, put, 2, call.stream());
+  });
+  call.download(out, dOut, put, "out");
+  return call.wait();
+}
+
 int redgpu_split_lines_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                            uint64_t *offsets, uint64_t cap, uint64_t *n_lines, void *stream) {
   if (int rc = checkHandle(dfa)) return rc;

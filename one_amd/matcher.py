@@ -626,6 +626,67 @@ def replace(exe, text: bytes, repl: bytes, max_count, style, do_leader=True):
     return int(counts[0]), out.tobytes()
 
 
+def replace_long(exe, text, repl: bytes, style=styLast, do_leader=True, max_count=(1 << 62), *,
+                 chunk_bytes=0, out=None):
+    """replace<style,doLeader> (include/Matcher.h:643-706; what Red's replaceOne* / replaceAll*,
+    include/Red.h:139-238, end in) over ONE long text, chunk-parallel on the GPU
+    (redgpu_replace_long[_dev]) -> (count, rewritten).  text: bytes / numpy uint8 (staged by the
+    library; rewritten comes back as bytes) or a contiguous uint8 CUDA tensor (the _dev form on
+    torch's current stream: a sizes-only call, then an output tensor of exactly out_len bytes;
+    rewritten is a CUDA uint8 tensor and count an int after a synchronisation of that stream).
+    out=: a contiguous uint8 CUDA tensor to write into, in ONE call - rewritten is then
+    out[:min(out_len, out.numel())] and the third value returned is out_len.  max_count=1 is
+    replaceOne*.  chunk_bytes=0: automatic."""
+    r = np.frombuffer(bytes(repl), dtype=np.uint8)
+    l = _lib.lib()
+    if _is_torch(text):
+        import torch
+        if not text.is_cuda or text.dtype != torch.uint8 or not text.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = text.device
+        stream = torch.cuda.current_stream(dev)
+        drepl = torch.from_numpy(r.copy()).to(dev) if r.size else None
+        sizes = torch.zeros(2, dtype=torch.int64, device=dev)
+
+        def call(o):
+            _check(l.redgpu_replace_long_dev(
+                exe._h, int(style), 1 if do_leader else 0,
+                text.data_ptr() if text.numel() else None, text.numel(), int(chunk_bytes),
+                drepl.data_ptr() if drepl is not None else None, r.size, int(max_count),
+                sizes.data_ptr(), sizes.data_ptr() + 8, o.data_ptr() if o is not None and o.numel() else None,
+                o.numel() if o is not None else 0, stream.cuda_stream))
+            return [int(v) for v in sizes.tolist()]
+
+        if out is not None:
+            if (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
+                    not out.is_contiguous() or out.device != dev):
+                raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
+            count, out_len = call(out)
+            return count, out[:min(out_len, out.numel())], out_len
+        count, out_len = call(None)
+        res = torch.empty(out_len, dtype=torch.uint8, device=dev)
+        if out_len:
+            call(res)
+        return count, res
+    if out is not None:
+        raise RedExceptApi("out= goes with a CUDA tensor text")
+    a = _host_u8(text)
+    cnt = C.c_uint64(0)
+    olen = C.c_uint64(0)
+    # first guess: output about as long as the input; once more with the exact size otherwise
+    cap = int(a.size + 64)
+    for _ in range(2):
+        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+        _check(l.redgpu_replace_long(
+            exe._h, int(style), 1 if do_leader else 0, a.ctypes.data if a.size else None, a.size,
+            int(chunk_bytes), r.ctypes.data if r.size else None, r.size, int(max_count),
+            C.byref(cnt), C.byref(olen), buf.ctypes.data, cap))
+        if int(olen.value) <= cap:
+            break
+        cap = int(olen.value)
+    return int(cnt.value), buf[:int(olen.value)].tobytes()
+
+
 def split_lines(exe, data, delim=b"\n", cap=None):
     """redgpu_split_lines: offsets of the delimiter-terminated lines of a raw text buffer, found
     on the device (the rule of lib/Util.cpp:109-130: bytes after the last delimiter are not a
