@@ -310,6 +310,29 @@ int redgpu_replace_long(const redgpu_dfa *dfa, int style, int do_leader, const u
                         uint64_t max_count, uint64_t *count, uint64_t *out_len, uint8_t *out,
                         uint64_t out_cap);
 
+/*   redgpu_search_long <-> search<style,doLeader>(exec, ptr, len)  include/Matcher.h:172-173, core
+ *                          :557-640, which Red::searchInstant ... Red::searchFull, Red::partialMatch
+ *                          and findAndConsume end in, over ONE long text, chunk-parallel across the
+ *                          device (redgpu_search_batch walks a line per lane: a single text is one
+ *                          lane).  *result, *start, *end = the fields of that Outcome: the match of
+ *                          the lowest start position whose attempt succeeds, 0 / 0 / 0 when there
+ *                          is none, searchCore's own answer on an empty text.  result is required;
+ *                          start and end may be NULL (result only: scan's use).  style is any of
+ *                          the five; do_leader as in redgpu_search_batch.  chunk_bytes as in
+ *                          redgpu_collect_long (0 = automatic, non-zero forces it, for tests).
+ *                          The Outcome is exactly the reference's whatever the chunk size.  A
+ *                          match near the front ends the call early: chunks are handed out in
+ *                          text order and dropped once a lower position has matched.
+ *                          redgpu_last_kernel() names the route: "k_search_long" (chunks) or
+ *                          "k_search_long<one>" (the batch kernels over a batch of one: the empty
+ *                          text, texts under 16 KiB, DFAs without a pure dead state under styLast
+ *                          / styFull, whose failing attempts cannot end early, and suffix-closed
+ *                          DFAs without the leader, whose search is one anchored walk).  The host
+ *                          form uploads the text once and downloads the three values. */
+int redgpu_search_long(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
+                       uint64_t len, uint32_t chunk_bytes, int32_t *result, uint64_t *start,
+                       uint64_t *end);
+
 /* ---- the same verbs over DEVICE-resident buffers, asynchronous on `stream` ---------------
  * data/offsets/result/start/end are device pointers on the handle's device; `stream` is a
  * hipStream_t (NULL = the default stream).  Nothing is copied or synchronised; the only
@@ -387,6 +410,12 @@ int redgpu_replace_long_dev(const redgpu_dfa *dfa, int style, int do_leader, con
                             uint64_t len, uint32_t chunk_bytes, const uint8_t *repl,
                             uint64_t repl_len, uint64_t max_count, uint64_t *count,
                             uint64_t *out_len, uint8_t *out, uint64_t out_cap, void *stream);
+
+/* every pointer is device memory, result, start and end too; asynchronous on stream; nothing is
+ * read back to the host */
+int redgpu_search_long_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
+                           uint64_t len, uint32_t chunk_bytes, int32_t *result, uint64_t *start,
+                           uint64_t *end, void *stream);
 
 /* repl is device memory too */
 int redgpu_replace_batch_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,

@@ -405,6 +405,26 @@ inline size_t replaceLong(const Executable &exec, std::string_view sv, std::stri
   return size_t(cnt);
 }
 
+// search(exec, sv, style) over one long text, chunk-parallel on the device (redgpu_search_long):
+// the run-time-style signature, doLeader = true; the template as Matcher.h:172-173
+inline Outcome searchLong(const Executable &exec, std::string_view sv, Style style) {
+  Result r = 0;
+  uint64_t s = 0, e = 0;
+  throwOnError(redgpu_search_long(exec.handle(), style, 1,
+                                  reinterpret_cast<const Byte *>(sv.data()), sv.size(), 0, &r, &s,
+                                  &e));
+  return Outcome{r, size_t(s), size_t(e)};
+}
+template <Style style, bool doLeader>
+Outcome searchLong(const Executable &exec, std::string_view sv) {
+  Result r = 0;
+  uint64_t s = 0, e = 0;
+  throwOnError(redgpu_search_long(exec.handle(), style, doLeader,
+                                  reinterpret_cast<const Byte *>(sv.data()), sv.size(), 0, &r, &s,
+                                  &e));
+  return Outcome{r, size_t(s), size_t(e)};
+}
+
 // StatefulMatcher: include/Matcher.h:770-792.  advance(Byte) as in the reference, plus
 // advance(ptr, len) for a whole chunk per launch.  exec must outlive this object.
 class StatefulMatcher {

@@ -148,6 +148,10 @@ def lib() -> C.CDLL:
         l.redgpu_replace_long_dev.restype = C.c_int
         l.redgpu_replace_long_dev.argtypes = [vp, i32, i32, vp, u64, C.c_uint32, vp, u64, u64, vp,
                                               vp, vp, u64, vp]
+        l.redgpu_search_long.restype = C.c_int
+        l.redgpu_search_long.argtypes = [vp, i32, i32, vp, u64, C.c_uint32, vp, vp, vp]
+        l.redgpu_search_long_dev.restype = C.c_int
+        l.redgpu_search_long_dev.argtypes = [vp, i32, i32, vp, u64, C.c_uint32, vp, vp, vp, vp]
         l.redgpu_replace_batch_dev.restype = C.c_int
         l.redgpu_replace_batch_dev.argtypes = [vp, i32, i32, vp, vp, u64, u64, vp, u64, u64, vp,
                                                vp, vp, u64, vp]

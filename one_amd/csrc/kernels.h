@@ -153,6 +153,14 @@ hipError_t launchReplaceLong(const DevDfa &dfa, int style, int doLeader, const u
                              uint64_t outCap, int phases, const LaunchCfg &cfg, hipStream_t stream,
                              const char **kernelName);
 
+// searchCore over ONE text of n bytes (k_search_long.h): *result, *start, *end (the last two may
+// be null) = the Outcome of search<style, doLeader>; chunkBytes = 0 chooses the chunk size.
+// *kernelName = the route: "k_search_long" or "k_search_long<one>".
+hipError_t launchSearchLong(const DevDfa &dfa, int style, int doLeader, const uint8_t *data,
+                            uint64_t n, uint32_t chunkBytes, int32_t *result, uint64_t *start,
+                            uint64_t *end, const LaunchCfg &cfg, hipStream_t stream,
+                            const char **kernelName);
+
 // replaceCore per line (include/Matcher.h:643-706): counts[n], outOffsets[n + 1] (exclusive scan
 // of the rewritten lengths, [n] = total) always; with out != nullptr also the rewritten bytes of
 // every line that fits below outCap.  repl is device memory.

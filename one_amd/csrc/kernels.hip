@@ -30,6 +30,9 @@
 //                     style, then the assembly (sums, scans, a tile-driven copy/insert)
 //   k_collect_long.h  k_cl_*: Red::collect over ONE long text, chunk-parallel (guessed entries,
 //                     re-walk rounds, serial finish, scan + scatter)
+//   k_search_long.h   k_sl_*: searchCore over ONE long text: every chunk tries its own positions in
+//                     order, the lowest success wins (atomic min), windows in text order and an
+//                     early exit, bounded attempts and a serial finish
 //   k_style_blocks.h  k_style_blocks: early-exit styles and odd strides over the block walk
 //   k_misc.h          k_advance, k_replace (+ scan), k_visits, k_walked
 //   k_split.h         line splitting on the device
@@ -73,6 +76,7 @@ namespace {
 #include "k_lists.h"
 #include "k_collect_long.h"
 #include "k_replace_long.h"
+#include "k_search_long.h"
 #include "k_style_blocks.h"
 #include "k_misc.h"
 #include "k_split.h"
@@ -608,6 +612,47 @@ hipError_t launchReplaceLong(const DevDfa &d, int style, int doLeader, const uin
   }
   return launchRlAssemble(data, n, b, r, repl, replLen, max, count, outLen, (phases & 1) != 0,
                           (phases & 2) ? out : nullptr, outCap, cfg, stream);
+}
+
+// searchCore over one text (k_search_long.h): chunks that try their own attempt positions, or the
+// batch kernels over a batch of one - the same Outcome either way.
+hipError_t launchSearchLong(const DevDfa &d, int style, int doLeader, const uint8_t *data, uint64_t n,
+                            uint32_t chunkBytes, int32_t *result, uint64_t *start, uint64_t *end,
+                            const LaunchCfg &cfg, hipStream_t stream, const char **kernelName) {
+  const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
+  // failing attempts end early at a pure dead end, or under a style that stops behind an accept
+  const bool early = d.nPureDead > 0 || style == kStyInstant || style == kStyFirst ||
+                     style == kStyTangent;
+  // one lane: the empty text; and at the automatic size short texts, attempts that cannot end
+  // early, and suffix-closed DFAs without the leader - their search is ONE anchored walk
+  // (normalizeVerbStyle), which chunks of attempt positions would only repeat
+  if (n == 0 || (!chunkBytes && (n < kClMinText || !early || (d.suffixClosed && !lead)))) {
+    *kernelName = "k_search_long<one>";
+    const Batch b{data, nullptr, n, 1, result, start, end};
+    const char *inner = "";
+    return launchBatch(d, b, kSearch, style, doLeader, cfg, stream, &inner);
+  }
+  *kernelName = "k_search_long";
+  uint64_t c = searchLongChunk(n, chunkBytes, cfg);
+  if (c > (1ull << 30)) c = 1ull << 30;  // (positions inside a chunk are 31-bit)
+  SlBufs b{};
+  b.m = (n + c - 1) / c;
+  b.chunk = uint32_t(c);
+  auto up16 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
+  const size_t bytes = 64 + up16(b.m * 8) * 2 + up16(b.m * 4) * 2;
+  void *scratch = nullptr;
+  hipError_t e = raggedScratch(stream, bytes, &scratch);
+  if (e != hipSuccess) return e;
+  uint8_t *q = static_cast<uint8_t *>(scratch);
+  b.ctl = reinterpret_cast<uint64_t *>(q); q += 64;
+  b.rst = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  b.ren = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  b.res = reinterpret_cast<int32_t *>(q); q += up16(b.m * 4);
+  b.state = reinterpret_cast<uint32_t *>(q);
+  const SlAttempt a{style, lead, lead && d.init >= d.firstAccept ? 1 : 0};
+#define SL_CALL(K) launchSearchLongK<K>(d, data, n, b, a, result, start, end, cfg, stream)
+  REDGPU_KIND_SWITCH(SL_CALL)
+#undef SL_CALL
 }
 
 hipError_t launchMatchAll(const DevDfa &d, const Batch &b, uint64_t cap, uint64_t *counts,

@@ -914,6 +914,62 @@ int redgpu_replace_long(const redgpu_dfa *dfa, int style, int do_leader, const u
   return call.wait();
 }
 
+// the arguments of both forms, in checkReplaceLong's order: the handle, the style, the buffers,
+// the limits, and last whether the handle has a device image
+static int checkSearchLong(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
+                           uint32_t chunkBytes, const int32_t *result) {
+  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
+  if (int rc = checkStyle(style)) return rc;
+  if (!result) return fail(REDGPU_EAPI, "null result buffer");
+  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
+  if (len >= (1ull << 40)) return fail(REDGPU_ELIMIT, "text too large");
+  if (chunkBytes && (len + chunkBytes - 1) / chunkBytes >= (1ull << 31))
+    return fail(REDGPU_ELIMIT, "too many chunks");
+  return checkHandle(dfa);
+}
+
+// searchCore over one text, chunk-parallel (k_search_long.h)
+int redgpu_search_long_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
+                           uint64_t len, uint32_t chunk_bytes, int32_t *result, uint64_t *start,
+                           uint64_t *end, void *stream) {
+  if (int rc = checkSearchLong(dfa, style, data, len, chunk_bytes, result)) return rc;
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  const LaunchCfg cfg = cfgOf(dfa);
+  const char *name = "";
+  const hipError_t e = launchSearchLong(dfa->im->dev, style, do_leader ? 1 : 0, data, len,
+                                        chunk_bytes, result, start, end, cfg,
+                                        static_cast<hipStream_t>(stream), &name);
+  tlsKernel = name;
+  if (e != hipSuccess) return failHip(e, "kernel launch");
+  return REDGPU_OK;
+}
+
+// the text goes up once, the three values of the Outcome come back
+int redgpu_search_long(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
+                       uint64_t len, uint32_t chunk_bytes, int32_t *result, uint64_t *start,
+                       uint64_t *end) {
+  if (int rc = checkSearchLong(dfa, style, data, len, chunk_bytes, result)) return rc;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  int32_t *dRes = call.buf<int32_t>(kSlRes, 1, "result");
+  uint64_t *dPos = call.buf<uint64_t>(kSlAux0, 2, "start and end");
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return redgpu_search_long_dev(dfa, style, do_leader, dData, len, chunk_bytes, dRes, dPos,
+                                  dPos + 1, call.stream());
+  });
+  int32_t res = 0;
+  uint64_t pos[2] = {0, 0};
+  call.download(&res, dRes, 1, "result");
+  call.download(pos, dPos, 2, "start and end");
+  if (int rc = call.wait()) return rc;
+  *result = res;
+  if (start) *start = pos[0];
+  if (end) *end = pos[1];
+  return REDGPU_OK;
+}
+
 int redgpu_split_lines_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                            uint64_t *offsets, uint64_t cap, uint64_t *n_lines, void *stream) {
   if (int rc = checkHandle(dfa)) return rc;

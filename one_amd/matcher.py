@@ -687,6 +687,35 @@ def replace_long(exe, text, repl: bytes, style=styLast, do_leader=True, max_coun
     return int(cnt.value), buf[:int(olen.value)].tobytes()
 
 
+def search_long(exe, text, style=styLast, do_leader=True, *, chunk_bytes=0):
+    """search<style,doLeader> (include/Matcher.h:172-173, core :557-640; what Red's search* and
+    partialMatch end in) over ONE long text, chunk-parallel on the GPU (redgpu_search_long[_dev])
+    -> (result, start, end): the match of the lowest start position, (0, 0, 0) without one.
+    text: bytes / numpy uint8 (staged by the library; three ints come back) or a contiguous uint8
+    CUDA tensor (the _dev form on torch's current stream: three one-element CUDA tensors - int32,
+    int64, int64 - and no synchronisation).  A match near the front ends the call early.
+    chunk_bytes=0: automatic."""
+    l = _lib.lib()
+    if _is_torch(text):
+        import torch
+        if not text.is_cuda or text.dtype != torch.uint8 or not text.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = text.device
+        res = torch.empty(1, dtype=torch.int32, device=dev)
+        pos = torch.empty(2, dtype=torch.int64, device=dev)
+        _check(l.redgpu_search_long_dev(
+            exe._h, int(style), 1 if do_leader else 0, text.data_ptr() if text.numel() else None,
+            text.numel(), int(chunk_bytes), res.data_ptr(), pos.data_ptr(), pos.data_ptr() + 8,
+            torch.cuda.current_stream(dev).cuda_stream))
+        return res, pos[0:1], pos[1:2]
+    a = _host_u8(text)
+    res, st, en = C.c_int32(0), C.c_uint64(0), C.c_uint64(0)
+    _check(l.redgpu_search_long(exe._h, int(style), 1 if do_leader else 0,
+                                a.ctypes.data if a.size else None, a.size, int(chunk_bytes),
+                                C.byref(res), C.byref(st), C.byref(en)))
+    return int(res.value), int(st.value), int(en.value)
+
+
 def split_lines(exe, data, delim=b"\n", cap=None):
     """redgpu_split_lines: offsets of the delimiter-terminated lines of a raw text buffer, found
     on the device (the rule of lib/Util.cpp:109-130: bytes after the last delimiter are not a
