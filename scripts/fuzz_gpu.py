@@ -1,7 +1,13 @@
 """Differential fuzz on the GPU: random DFAs x random line shapes x every verb / style / leader x
 random placement and kernel-selection flags, against the CPU oracle.  Not part of the pytest
 suite (it is open-ended); a failure prints the case and exits non-zero.
-usage: fuzz_gpu.py [cases] [seed]"""
+usage: fuzz_gpu.py [cases] [seed] [hot | cls | lists | blocks | long]
+long: the DFAs and placement flags of the general mode, one buffer of 2 KiB to 128 KiB as ONE
+text through collect_long, replace_long and search_long (random style, leader setting, chunk
+size, cap / max count and replacement).  Without a pure dead state an attempt that does not
+accept walks to the end of the text - quadratic on the CPU and on the device's one lane - so
+those DFAs get the first KiB of the buffer, and so do DFAs whose pure dead state the text's
+walks do not reach (walks_die)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -18,6 +24,7 @@ CLS_BIAS = len(sys.argv) > 3 and sys.argv[3] == "cls"           # ... of the cla
 LISTS = len(sys.argv) > 3 and sys.argv[3] == "lists"            # only the record-list verbs
 BLOCKS = len(sys.argv) > 3 and sys.argv[3] == "blocks"          # >= 4096 lines, check / match /
                                                                 # match_all: the block kernels
+LONG = len(sys.argv) > 3 and sys.argv[3] == "long"              # one text, the *_long verbs
 rng = np.random.default_rng(seed)
 ALPHA = np.frombuffer(b"abcdefghijklmnopqrstuvwxyz0123456789 ./:-_=&?%@[]", dtype=np.uint8)
 
@@ -106,11 +113,66 @@ def make_data(nbytes, blob_name):
     return np.ascontiguousarray(d)
 
 
+def walks_die(cpu, data):
+    """64 walks of 256 bytes from the initial state, spread over data: at most one in eight may
+    still be alive (a state is a dead end when every byte leads back to it with result 0)"""
+    k, L = 64, 256
+    pos = np.linspace(0, len(data) - L, k).astype(np.int64)
+    buf = np.concatenate([data[p:p + L] for p in pos])
+    st = np.full(k, O.STATE_INITIAL, dtype=np.uint32)
+    cpu.advance_batch(buf, st, stride=L, n=k)
+    alive = 0
+    for t in set(st.tolist()):
+        nxt = np.full(256, t, dtype=np.uint32)
+        res = cpu.advance_batch(np.arange(256, dtype=np.uint8), nxt, stride=1, n=256)
+        if not ((nxt == t).all() and (res == 0).all()):
+            alive += int((st == t).sum())
+    return alive * 8 <= k
+
+
+def long_case(desc, blob, exe, cpu, data):
+    """collect_long, replace_long and search_long over data as one text; the failing call or None"""
+    if exe.info["n_pure_dead"] == 0 or not walks_die(cpu, data):
+        data = data[:1024]
+    text = data.tobytes()
+    for verb in ("collect_long", "replace_long", "search_long"):
+        sty = int(rng.integers(1, 6))
+        lead = int(rng.integers(0, 2))
+        chunk = int(rng.choice([0, 1, 3, 16, 64, 1000, 4096]))
+        if verb == "collect_long":
+            cap = [None, 0, 5, 4096][int(rng.integers(0, 4))]
+            recs, k = cpu.collect(text, 4096)
+            if k > len(recs):
+                recs, k = cpu.collect(text, k)
+            cnt, r, s, e = one_amd.collect_long(exe, data, cap, chunk_bytes=chunk)
+            ok = cnt == k and list(zip(r.tolist(), s.tolist(), e.tolist())) == \
+                (recs if cap is None else recs[:cap])
+            what = (verb, chunk, cap)
+        elif verb == "replace_long":
+            repl = [b"", b"#", b"<<>>", b"0123456789" * 4][int(rng.integers(0, 4))]
+            mx = int(rng.choice([0, 1, 3, 1 << 40]))
+            ok = one_amd.replace_long(exe, data, repl, sty, bool(lead), mx, chunk_bytes=chunk) == \
+                cpu.replace(text, repl, sty, bool(lead), mx)
+            what = (verb, chunk, sty, lead, repl, mx)
+        else:
+            ok = one_amd.search_long(exe, data, sty, bool(lead), chunk_bytes=chunk) == \
+                tuple(int(v) for v in cpu.search(text, sty, bool(lead)))
+            what = (verb, chunk, sty, lead)
+        kern = one_amd.last_kernel()
+        stats[kern] = stats.get(kern, 0) + 1
+        if not ok:
+            return what + (len(text), kern)
+    return None
+
+
 t0 = time.time()
 stats = {}
 for case in range(cases):
     name, blob = make_dfa()
-    shape, nbytes = make_lines()
+    if LONG:
+        shape, nbytes = {}, int(rng.integers(2048, 128 * 1024 + 1))
+    else:
+        shape, nbytes = make_lines()
     data = make_data(nbytes, name)
     flags = {}
     for f, p in ((("force_generic", 0.05), ("no_bucketing", 0.3), ("force_stream", 0.5)) if CLS_BIAS else
@@ -133,6 +195,18 @@ for case in range(cases):
         continue
     cpu = O.CpuOracle(blob)
     desc = (case, name, {k: (v if not hasattr(v, "shape") else "offsets[%d]" % (len(v) - 1)) for k, v in shape.items()}, flags, exe.info["table_kind"])
+    if LONG:
+        try:
+            bad = long_case(desc, blob, exe, cpu, data)
+        except one_amd.RedExcept as e:
+            print("ERROR", desc, e)
+            sys.exit(1)
+        if bad:
+            print("MISMATCH", desc, bad)       # (cases and seed reproduce it)
+            sys.exit(1)
+        if case % 25 == 0:
+            print("case", case, "%.0fs" % (time.time() - t0), flush=True)
+        continue
     verbs = (["match", "check", "advance", "match", "check"] if HOT_BIAS else
              ["match", "check", "scan", "search", "advance", "match_all", "collect", "replace"])
     if BLOCKS:

@@ -121,6 +121,15 @@ def test_table_placement():
     from oracle.reda_writer import random_dfa as _rd
     assert one_amd.Executable(_rd(700, 64, 4), device="none").info["table_kind"] == 3
     assert one_amd.Executable(_rd(270, 256, 4), device="none").info["table_kind"] == 2
+    # more than 65,536 reachable states: u32 entries in L2, whatever is forced
+    big = _rd(80000, 4, 5, dead_frac=0.05, accept_frac=0.1)
+    for opts in ({}, {"force_hot": True}, {"force_global": True}):
+        i = one_amd.Executable(big, device="none", **opts).info
+        assert i["table_kind"] == 5 and i["n_hot"] == 0 and i["states_used"] > 65536, (opts, i)
+    # LDS room for 16 rows only sends the 212-state URI table to the hot-row form, and hot rows
+    # are ranked for more than 256 states only: the hot-row kernels over an empty hot set
+    i = one_amd.Executable(load_dfa("uri"), device="none", lds_table_max=16 * 256).info
+    assert i["table_kind"] == 6 and i["n_hot"] == 0
 
 
 def test_host_only_handle_refuses_compute():
