@@ -45,16 +45,23 @@ __device__ __forceinline__ uint4 ntLoad16(const uint8_t *p) {
 // not read by this launch; with two workgroups per CU the 20-batch configs[1] launch took 319 us
 // against 345-349 us for either measure alone and for neither, r3 lab); bit 0: non-temporal
 // input loads too (lab only: slower, 465 against 421 us).  REDGPU_MULTI_NT picks another value.
+// R1: 64-byte LINES - every block ends a line (the launcher's promise), so R is the constant 1
+// and the non-temporal stores stand alone in the code.  With R read from the descriptor the
+// choice "non-temporal if R == 1, plain otherwise" is an if / else around two copies of the same
+// stores: the compiler merges the copies and the merged stores lose the hint (in the ISA of that
+// form not one store carries nt) - which is how configs[1] ran with plain stores.
 // LEAN: the deferred-bookkeeping step of k_stream_lean.h (long lines; the two remembered pieces of
 // a line are re-walked exactly when the line ends).
 // GR: groups of two chains per lane (2 = four lines per lane; LEAN only, k_stream_lean.h).
-template <int MODE, int HALVES, int THREADS, int NT = 2, bool LEAN = false, int GR = 1>
+template <int MODE, int HALVES, int THREADS, int NT = 2, bool LEAN = false, int GR = 1,
+          bool R1 = false>
 __global__ void __launch_bounds__(THREADS)
 k_stream_multi(DevDfa d, MultiIo m) {
   static_assert(MODE == kSmLastStartEnd || MODE == kSmLastEnd || MODE == kSmFullStart ||
                 MODE == kSmFull, "the plain output modes only");
   static_assert(!LEAN || MODE != kSmFull, "styFull without start has no bookkeeping to defer");
   static_assert(GR == 1 || LEAN, "more than two chains per lane: the lean step only");
+  static_assert(!R1 || (HALVES == 1 && !LEAN && GR == 1), "R1: the plain 64-byte walk only");
   constexpr uint32_t BLK = 64 * HALVES;
   constexpr int CH = kStreamChains * GR;
   constexpr bool kAcc = MODE == kSmLastStartEnd || MODE == kSmLastEnd;
@@ -66,7 +73,7 @@ k_stream_multi(DevDfa d, MultiIo m) {
 
   const uint32_t init = d.init, firstAccept = d.firstAccept;
   const uint32_t lineLen = m.lineLen;
-  const uint32_t R = lineLen / BLK;  // blocks per line
+  const uint32_t R = R1 ? 1u : lineLen / BLK;  // blocks per line
   const uint32_t nTiles = m.tileStart[m.nb];
   const uint32_t G = gridDim.x;
   if (blockIdx.x >= nTiles) return;
@@ -397,6 +404,13 @@ hipError_t launchStreamMultiN(const DevDfa &d, const MultiIo &m, const LaunchCfg
   const bool wide = m.lineLen % 128 == 0;
   const uint32_t want = uint32_t(cfg.numCUs) * uint32_t(wide ? 1 : wgs);
   const uint32_t blocks = tiles < want ? tiles : want;
+  if constexpr (!LEAN) {
+    if (m.lineLen == 64) {
+      hipLaunchKernelGGL((k_stream_multi<MODE, 1, kStreamThreads, NT, false, 1, true>), dim3(blocks),
+                         dim3(kStreamThreads), 0, stream, d, m);
+      return hipGetLastError();
+    }
+  }
   if (wide)
     hipLaunchKernelGGL((k_stream_multi<MODE, 2, kStreamThreads, NT, LEAN>), dim3(blocks),
                        dim3(kStreamThreads), 0, stream, d, m);

@@ -769,8 +769,10 @@ hipError_t launchDiagLines(const uint8_t *data, uint64_t nLines, uint32_t lineBy
                        lineBytes, sink);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_diag_lines, dim3(uint32_t(numCUs)), dim3(512), 0, stream, data, nLines, res,
-                     st, en, sink);
+  // two workgroups per CU when the tiles allow, as launchStreamMultiN
+  const uint64_t tiles = nLines / 1024, want = uint64_t(numCUs) * 2;
+  hipLaunchKernelGGL(k_diag_lines, dim3(uint32_t(tiles < want ? tiles : want)), dim3(512), 0,
+                     stream, data, nLines, res, st, en, sink);
   return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // hbm_probe.hip - lab: what does HBM give this chip for the access patterns the streaming walk
 // uses?  Streaming reads (coalesced 16 B/lane; 64-byte line per lane as k_stream requests it),
 // with and without the 20 B per 64 B line of Outcome stores, plain and non-temporal, at several
-// occupancies.  Prints GB/s of bytes read (+ written).  Not part of the product.
+// occupancies; and the store side swept in the walk's own pipelined loop (mapping x store width x
+// planes x non-temporal).  Prints GB/s of bytes read (+ written).  Not part of the product.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -62,6 +63,92 @@ __global__ void k_lines(const uint8_t *data, uint64_t nLines, int32_t *res, uint
         }
       }
     }
+  }
+  if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) atomicAdd(sink, 1);
+}
+
+// The walk's memory side as k_stream_multi runs it (k_diag_lines is this loop): 512 threads, two
+// register sets, the NEXT tile's 8 loads issued before this tile's stores, the loop rotated so
+// that no wait for input sits out a store.  MAP 0: lines c * 512 + tid; 1: a wave on one strip of
+// 128 lines, wave * 128 + c * 64 + lane.  STORE 0: none; 1: per line dword + dwordx2 + dwordx2;
+// 2: paired through one DPP exchange with the neighbouring lane, per two lines dwordx2 + dwordx4 +
+// dwordx4.  PLANES 1..3: result / + end / + start = 4, 12, 20 bytes written per line.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+template <int MAP> __device__ __forceinline__ uint32_t lineOf(uint32_t tid, int c) {
+  return MAP ? (tid >> 6) * 128 + uint32_t(c) * 64 + (tid & 63) : uint32_t(c) * 512 + tid;
+}
+__device__ __forceinline__ void pairExchange(uint32_t v0, uint32_t v1, bool odd, uint32_t &lo,
+                                             uint32_t &hi) {
+  const uint32_t give = odd ? v0 : v1;
+  const uint32_t got = uint32_t(__builtin_amdgcn_update_dpp(0, int(give), 0xB1, 0xF, 0xF, false));
+  lo = odd ? got : v0;
+  hi = odd ? v1 : got;
+}
+template <int NT, class T> __device__ __forceinline__ void st_(T v, T *p) {
+  if (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+template <int MAP, int STORE, int PLANES, int NT_ST>
+__global__ void __launch_bounds__(512)
+k_lines_pipe(const uint8_t *data, uint64_t nLines, int32_t *res, uint64_t *st, uint64_t *en,
+             uint32_t *sink) {
+  const uint64_t tiles = nLines / 1024, G = gridDim.x;
+  if (blockIdx.x >= tiles) return;
+  const uint64_t Q = (tiles - blockIdx.x + G - 1) / G;
+  uint64_t ldT = blockIdx.x, ldQ = 0, t = blockIdx.x;
+  u32x4 acc = {0, 0, 0, 0};
+  u32x4 A[2][4], B[2][4];
+  auto issue = [&](u32x4 (&blk)[2][4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+        blk[c][k] = reinterpret_cast<const u32x4 *>(
+            data + (ldT * 1024 + lineOf<MAP>(threadIdx.x, c)) * 64)[k];
+    if (ldQ + 1 < Q) { ++ldQ; ldT += G; }
+  };
+  auto walk = [&](const u32x4 (&blk)[2][4]) {
+    u32x4 x[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      x[c] = blk[c][0] ^ blk[c][1] ^ blk[c][2] ^ blk[c][3];
+      acc ^= x[c];
+    }
+    if (STORE == 1) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const uint64_t ln = t * 1024 + lineOf<MAP>(threadIdx.x, c);
+        st_<NT_ST>(int32_t(x[c].x), res + ln);
+        if (PLANES > 1) st_<NT_ST>(uint64_t(x[c].z), en + ln);
+        if (PLANES > 2) st_<NT_ST>(uint64_t(x[c].y), st + ln);
+      }
+    } else if (STORE == 2) {
+      const bool odd = threadIdx.x & 1;
+      const uint64_t at = t * 1024 + (odd ? lineOf<MAP>(threadIdx.x - 1, 1) : lineOf<MAP>(threadIdx.x, 0));
+      uint32_t lo, hi;
+      pairExchange(x[0].x, x[1].x, odd, lo, hi);
+      st_<NT_ST>(u32x2{lo, hi}, reinterpret_cast<u32x2 *>(res + at));
+      if (PLANES > 1) {
+        pairExchange(x[0].z, x[1].z, odd, lo, hi);
+        st_<NT_ST>(u32x4{lo, 0u, hi, 0u}, reinterpret_cast<u32x4 *>(en + at));
+      }
+      if (PLANES > 2) {
+        pairExchange(x[0].y, x[1].y, odd, lo, hi);
+        st_<NT_ST>(u32x4{lo, 0u, hi, 0u}, reinterpret_cast<u32x4 *>(st + at));
+      }
+    }
+    t += G;
+  };
+  issue(A);
+  issue(B);
+  walk(A);
+  issue(A);
+  for (uint64_t q = 1; q < Q; q += 2) {
+    walk(B);
+    if (q + 1 >= Q) break;
+    issue(B);
+    walk(A);
+    issue(A);
   }
   if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) atomicAdd(sink, 1);
 }
@@ -145,6 +232,15 @@ int main() {
   LINES(2, 0, 0, 0, 512, 1) LINES(2, 0, 0, 0, 512, 2) LINES(4, 0, 0, 0, 512, 1) LINES(4, 0, 0, 0, 512, 2) LINES(2, 1, 0, 0, 512, 2)
   LINES(2, 0, 1, 0, 512, 1) LINES(2, 0, 1, 1, 512, 1) LINES(2, 0, 1, 0, 512, 2) LINES(2, 0, 1, 1, 512, 2)
   LINES(4, 0, 1, 1, 512, 2) LINES(2, 0, 1, 1, 256, 4) LINES(2, 0, 1, 1, 1024, 1) LINES(2, 1, 1, 1, 512, 2)
+  // the store side of the 64-byte walk, pipelined as the walk is, 512 threads x 2 workgroups per CU
+#define PIPE(MAP, STO, PL, NTS) { const int wr = (STO) ? ((PL) == 1 ? 4 : (PL) == 2 ? 12 : 20) : 0; \
+    float ms = timeit([&] { hipLaunchKernelGGL((k_lines_pipe<MAP, STO, PL, NTS>), dim3(cus * 2), dim3(512), 0, 0, d, nLines, res, st, en, sink); }, 5); \
+    printf("pipelined line/lane  map %s  stores %-6s  %2d B/line  nt_st %d : read %7.1f GB/s  traffic %7.1f GB/s\n", (MAP) ? "strip" : "c*512", \
+           (STO) == 0 ? "none" : (STO) == 1 ? "narrow" : "paired", wr, NTS, bytes / ms / 1e6, (bytes + nLines * wr) / ms / 1e6); }
+#define PIPE_MAP(MAP) PIPE(MAP, 0, 1, 0) \
+    PIPE(MAP, 1, 1, 0) PIPE(MAP, 1, 2, 0) PIPE(MAP, 1, 3, 0) PIPE(MAP, 1, 1, 1) PIPE(MAP, 1, 2, 1) PIPE(MAP, 1, 3, 1) \
+    PIPE(MAP, 2, 1, 0) PIPE(MAP, 2, 2, 0) PIPE(MAP, 2, 3, 0) PIPE(MAP, 2, 1, 1) PIPE(MAP, 2, 2, 1) PIPE(MAP, 2, 3, 1)
+  PIPE_MAP(0) PIPE_MAP(1)
 #define LONG(LPL, LB, THR, WG) { float ms = timeit([&] { hipLaunchKernelGGL((k_long<LPL>), dim3(cus * WG), dim3(THR), 0, 0, d, bytes / LB, LB, sink); }, 5); \
     printf("long lines %5d B, 128 B per lane request, %d lines/lane  %4d thr x %d WG/CU : %7.1f GB/s\n", LB, LPL, THR, WG, bytes / ms / 1e6); }
   LONG(2, 4096, 512, 1) LONG(2, 4096, 512, 2) LONG(4, 4096, 512, 1) LONG(1, 4096, 512, 2) LONG(2, 512, 512, 1) LONG(2, 1024, 512, 1) LONG(2, 16384, 512, 1) LONG(2, 65536, 256, 1)
