@@ -252,6 +252,25 @@ int redgpu_match_all_batch(const redgpu_dfa *dfa, int do_leader, const uint8_t *
                            const uint64_t *offsets, uint64_t stride, uint64_t n, uint64_t cap,
                            uint64_t *counts, int32_t *result, uint64_t *start, uint64_t *end);
 
+/*   redgpu_match_all_long <-> matchAll(exec, string_view, vector<Outcome>&)  include/Matcher.h:127,
+ *                             lib/Matcher.cpp:97-102, core include/Matcher.h:711-766, over ONE long
+ *                             text, chunk-parallel across the device (redgpu_match_all_batch walks
+ *                             a line per lane: a single text is one lane).  Positions are absolute
+ *                             in the text.  *count = records FOUND, which may exceed cap; the first
+ *                             min(*count, cap) records are stored complete (record cap-1 with its
+ *                             final end); start and end may be NULL, result only when cap = 0.
+ *                             do_leader as in redgpu_match_all_batch (1 = the reference's entry).
+ *                             chunk_bytes = 0 sizes the chunks automatically; non-zero forces the
+ *                             chunk size (for tests).  The records are exactly matchAll's whatever
+ *                             the chunk size.  The host form uploads the whole text once.
+ *                             redgpu_last_kernel() names the route: "k_match_all_long" (chunks) or
+ *                             "k_matchall" (one lane: the empty text, texts under 16 KiB at the
+ *                             automatic size, DFAs with a pure dead end that has a way out).
+ *                             Record slots at or past *count may be overwritten. */
+int redgpu_match_all_long(const redgpu_dfa *dfa, int do_leader, const uint8_t *data, uint64_t len,
+                          uint32_t chunk_bytes, uint64_t cap, uint64_t *count, int32_t *result,
+                          uint64_t *start, uint64_t *end);
+
 /*   redgpu_advance_batch <-> StatefulMatcher (include/Matcher.h:770-792, lib/Matcher.cpp:106-158),
  *                            n independent matchers advanced by one CHUNK each: state[i] is
  *                            matcher i's state_ on entry and on return (an opaque token, valid
@@ -400,6 +419,11 @@ int redgpu_match_all_batch_dev(const redgpu_dfa *dfa, int do_leader, const uint8
                                uint64_t cap, uint64_t *counts, int32_t *result, uint64_t *start,
                                uint64_t *end, void *stream);
 
+/* device pointers (count too), asynchronous on stream; nothing is read back to the host */
+int redgpu_match_all_long_dev(const redgpu_dfa *dfa, int do_leader, const uint8_t *data,
+                              uint64_t len, uint32_t chunk_bytes, uint64_t cap, uint64_t *count,
+                              int32_t *result, uint64_t *start, uint64_t *end, void *stream);
+
 int redgpu_advance_batch_dev(const redgpu_dfa *dfa, const uint8_t *data, const uint64_t *offsets,
                              uint64_t stride, uint64_t n, uint32_t *state, int32_t *result,
                              void *stream);
@@ -500,6 +524,12 @@ int redgpu_diag_lines_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t n
  *    bandwidth.  *lookups (host) = gathers performed. */
 int redgpu_diag_l2_dev(const redgpu_dfa *dfa, const uint16_t *table, uint32_t rounds, uint32_t *sink,
                        uint64_t *lookups, void *stream);
+/*  - redgpu_diag_match_all_long_dev: how the calling thread's last redgpu_match_all_long_dev call
+ *    on `stream` resolved its chunks (route "k_match_all_long"; EAPI after any other).  Queues a
+ *    copy of 8 words into stats (device memory): [0..3] chunks walked again in each of the four
+ *    rounds, [4] the first chunk still inconsistent behind them (= [7] when there is none),
+ *    [5] 1 = the leader test passed, [6] chunks the serial lane walked again, [7] chunks. */
+int redgpu_diag_match_all_long_dev(const redgpu_dfa *dfa, uint32_t *stats, void *stream);
 int redgpu_diag_walked_dev(const redgpu_dfa *dfa, int do_leader, const uint8_t *data,
                            const uint64_t *offsets, uint64_t stride, uint64_t n, uint64_t *walked,
                            void *stream);

@@ -354,6 +354,27 @@ inline size_t collectLong(const Executable &exec, std::string_view sv, std::vect
   return out.size();
 }
 
+// matchAll(exec, sv, out) (include/Matcher.h:127, lib/Matcher.cpp:97-102: doLeader = true) over one
+// long text, chunk-parallel on the device (redgpu_match_all_long): room for 16 records first, one
+// retry with the exact count, as collectLong
+inline size_t matchAllLong(const Executable &exec, std::string_view sv, std::vector<Outcome> &out) {
+  uint64_t cap = 16, found = 0;
+  std::vector<Result> r;
+  std::vector<uint64_t> s, e;
+  for (int pass = 0; pass < 2; ++pass) {
+    r.assign(cap, 0);
+    s.assign(cap, 0);
+    e.assign(cap, 0);
+    throwOnError(redgpu_match_all_long(exec.handle(), 1, reinterpret_cast<const Byte *>(sv.data()),
+                                       sv.size(), 0, cap, &found, r.data(), s.data(), e.data()));
+    if (found <= cap) break;
+    cap = found;
+  }
+  out.clear();
+  for (uint64_t i = 0; i < found; ++i) out.push_back(Outcome{r[i], size_t(s[i]), size_t(e[i])});
+  return out.size();
+}
+
 // replace(exec, sv, repl, out, max, style): include/Matcher.h:119-124, lib/Matcher.cpp:72-92
 // (run-time style, doLeader = true); the templates of Matcher.h:186-211 below it
 namespace detail {

@@ -126,6 +126,13 @@ def lib() -> C.CDLL:
         l.redgpu_collect_long.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, vp, vp, vp]
         l.redgpu_collect_long_dev.restype = C.c_int
         l.redgpu_collect_long_dev.argtypes = [vp, vp, u64, C.c_uint32, u64, vp, vp, vp, vp, vp]
+        l.redgpu_match_all_long.restype = C.c_int
+        l.redgpu_match_all_long.argtypes = [vp, C.c_int, vp, u64, C.c_uint32, u64, vp, vp, vp, vp]
+        l.redgpu_diag_match_all_long_dev.restype = C.c_int
+        l.redgpu_diag_match_all_long_dev.argtypes = [vp, vp, vp]
+        l.redgpu_match_all_long_dev.restype = C.c_int
+        l.redgpu_match_all_long_dev.argtypes = [vp, C.c_int, vp, u64, C.c_uint32, u64, vp, vp, vp, vp,
+                                                vp]
         l.redgpu_match_all_batch.restype = C.c_int
         l.redgpu_match_all_batch.argtypes = [vp, i32, vp, vp, u64, u64, u64, vp, vp, vp, vp]
         l.redgpu_match_all_batch_dev.restype = C.c_int

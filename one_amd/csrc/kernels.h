@@ -133,6 +133,16 @@ hipError_t launchCollectLong(const DevDfa &dfa, const uint8_t *data, uint64_t n,
 hipError_t launchMatchAll(const DevDfa &dfa, const Batch &b, uint64_t cap, uint64_t *counts,
                           int doLeader, const LaunchCfg &cfg, hipStream_t stream);
 
+// matchAll over ONE text of n bytes (k_match_all_long.h): *count = records found, the first
+// min(count, cap) complete at result/start/end[0..); chunkBytes = 0 chooses the chunk size.
+// *kernelName = the route: "k_match_all_long" or "k_matchall".  *ctl = the chunked route's 8 control
+// words in the stream's scratch (k_match_all_long.h: queued per round, first open chunk, leader
+// passed, chunks the serial lane walked, chunks), or nullptr on the one-lane route.
+hipError_t launchMatchAllLong(const DevDfa &dfa, int doLeader, const uint8_t *data, uint64_t n,
+                              uint32_t chunkBytes, uint64_t cap, uint64_t *count, int32_t *result,
+                              uint64_t *start, uint64_t *end, const LaunchCfg &cfg,
+                              hipStream_t stream, const char **kernelName, const uint32_t **ctl);
+
 // StatefulMatcher::advance over one chunk per line (include/Matcher.h:770-792):
 // state[line] in/out (device state index, >= nStates means "fresh matcher"), b.result out.
 hipError_t launchAdvance(const DevDfa &dfa, const Batch &b, uint32_t *state, const LaunchCfg &cfg,

@@ -30,6 +30,8 @@
 //                     style, then the assembly (sums, scans, a tile-driven copy/insert)
 //   k_collect_long.h  k_cl_*: Red::collect over ONE long text, chunk-parallel (guessed entries,
 //                     re-walk rounds, serial finish, scan + scatter)
+//   k_match_all_long.h  k_ml_*: matchAllCore over ONE long text: chunks from guessed entry STATES,
+//                     re-walk rounds, serial finish, (sum, max) scan, records emitted in place
 //   k_search_long.h   k_sl_*: searchCore over ONE long text: every chunk tries its own positions in
 //                     order, the lowest success wins (atomic min), windows in text order and an
 //                     early exit, bounded attempts and a serial finish
@@ -77,6 +79,7 @@ namespace {
 #include "k_collect_long.h"
 #include "k_replace_long.h"
 #include "k_search_long.h"
+#include "k_match_all_long.h"
 #include "k_style_blocks.h"
 #include "k_misc.h"
 #include "k_split.h"
@@ -662,6 +665,49 @@ hipError_t launchMatchAll(const DevDfa &d, const Batch &b, uint64_t cap, uint64_
 #define MA_CALL(K) launchMatchAllK<K>(d, b, cap, counts, lead, cfg, stream)
   REDGPU_KIND_SWITCH(MA_CALL)
 #undef MA_CALL
+}
+
+// matchAllCore over one text (k_match_all_long.h): the chunked walk, or the batch kernels over a
+// batch of one - the same records either way.
+hipError_t launchMatchAllLong(const DevDfa &d, int doLeader, const uint8_t *data, uint64_t n,
+                              uint32_t chunkBytes, uint64_t cap, uint64_t *count, int32_t *result,
+                              uint64_t *start, uint64_t *end, const LaunchCfg &cfg,
+                              hipStream_t stream, const char **kernelName, const uint32_t **ctl) {
+  *ctl = nullptr;
+  // one lane: the empty text, short texts at the automatic size, and pure dead ends with a way
+  // out - the walk's stop at one (Matcher.h:755-756) is then observable, and k_matchall has it
+  if (n == 0 || (!chunkBytes && n < kClMinText) || !d.deadAbsorbing) {
+    *kernelName = "k_matchall";
+    const Batch b{data, nullptr, n, 1, result, start, end};
+    return launchMatchAll(d, b, cap, count, doLeader, cfg, stream);
+  }
+  *kernelName = "k_match_all_long";
+  const uint64_t c = collectLongChunk(n, chunkBytes, cfg);
+  MlBufs b{};
+  b.m = (n + c - 1) / c;
+  b.chunk = uint32_t(c);
+  const uint64_t nb = (b.m + 1023) / 1024;
+  auto up16 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
+  const size_t bytes = up16(b.m * 8) * 2 + up16(nb * 8) * 2 + up16(b.m * 4) * 5 + 64;
+  void *scratch = nullptr;
+  hipError_t e = raggedScratch(stream, bytes, &scratch);
+  if (e != hipSuccess) return e;
+  uint8_t *q = static_cast<uint8_t *>(scratch);
+  b.esc = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  b.off = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
+  b.blockOff = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
+  b.blockEsc = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
+  b.ent = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
+  b.exit = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
+  b.cnt = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
+  b.head = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
+  b.work = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
+  b.ctl = reinterpret_cast<uint32_t *>(q);
+  *ctl = b.ctl;
+  const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
+#define ML_CALL(K) launchMatchAllLongK<K>(d, data, n, b, lead, cap, count, result, start, end, cfg, stream)
+  REDGPU_KIND_SWITCH(ML_CALL)
+#undef ML_CALL
 }
 
 template <int KIND>

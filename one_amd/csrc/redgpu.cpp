@@ -771,6 +771,90 @@ int redgpu_collect_long(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len
   return call.wait();
 }
 
+// the control words of this thread's last chunked match_all_long call, and the stream it ran on
+static thread_local const uint32_t *tlsMlCtl = nullptr;
+static thread_local hipStream_t tlsMlStream = nullptr;
+
+static int matchAllLongArgs(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint64_t cap,
+                            const uint64_t *count, const int32_t *result) {
+  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
+  if (!count) return fail(REDGPU_EAPI, "null count buffer");
+  if (cap && !result) return fail(REDGPU_EAPI, "null result buffer");
+  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
+  return checkHandle(dfa);
+}
+
+// matchAll over one text, chunk-parallel (k_match_all_long.h)
+static int matchAllLongDev(const redgpu_dfa *dfa, int doLeader, const uint8_t *data, uint64_t len,
+                           uint32_t chunkBytes, uint64_t cap, uint64_t *count, int32_t *result,
+                           uint64_t *start, uint64_t *end, hipStream_t stream) {
+  if (int rc = matchAllLongArgs(dfa, data, len, cap, count, result)) return rc;
+  if (len >= (1ull << 40)) return fail(REDGPU_ELIMIT, "text too large");
+  if (chunkBytes && (len + chunkBytes - 1) / chunkBytes >= (1ull << 31))
+    return fail(REDGPU_ELIMIT, "too many chunks");
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  const LaunchCfg cfg{dfa->numCUs, (dfa->flags & REDGPU_F_FORCE_GENERIC) ? 1 : 0};
+  const char *name = "";
+  const hipError_t e = launchMatchAllLong(dfa->im->dev, doLeader ? 1 : 0, data, len, chunkBytes, cap,
+                                          count, result, start, end, cfg, stream, &name, &tlsMlCtl);
+  tlsMlStream = stream;
+  tlsKernel = name;
+  if (e != hipSuccess) return failHip(e, "kernel launch");
+  return REDGPU_OK;
+}
+
+int redgpu_match_all_long_dev(const redgpu_dfa *dfa, int do_leader, const uint8_t *data,
+                              uint64_t len, uint32_t chunk_bytes, uint64_t cap, uint64_t *count,
+                              int32_t *result, uint64_t *start, uint64_t *end, void *stream) {
+  return matchAllLongDev(dfa, do_leader, data, len, chunk_bytes, cap, count, result, start, end,
+                         static_cast<hipStream_t>(stream));
+}
+
+// the whole text goes up once, the count and the records that were kept come back
+int redgpu_match_all_long(const redgpu_dfa *dfa, int do_leader, const uint8_t *data, uint64_t len,
+                          uint32_t chunk_bytes, uint64_t cap, uint64_t *count, int32_t *result,
+                          uint64_t *start, uint64_t *end) {
+  if (int rc = matchAllLongArgs(dfa, data, len, cap, count, result)) return rc;
+  if (cap > (~0ull / 16)) return fail(REDGPU_ELIMIT, "cap too large");
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dCnt = call.buf<uint64_t>(kSlAux0, 1, "count");
+  int32_t *dRes = call.buf<int32_t>(kSlRes, cap + 1, "result");
+  uint64_t *dStart = start ? call.buf<uint64_t>(kSlStart, cap + 1, "start") : nullptr;
+  uint64_t *dEnd = end ? call.buf<uint64_t>(kSlEnd, cap + 1, "end") : nullptr;
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return matchAllLongDev(dfa, do_leader, dData, len, chunk_bytes, cap, dCnt,
+                           cap ? dRes : nullptr, dStart, dEnd, call.stream());
+  });
+  uint64_t found = 0;
+  call.download(&found, dCnt, 1, "count");
+  if (int rc = call.wait()) return rc;
+  *count = found;
+  const uint64_t got = found < cap ? found : cap;
+  if (got) {
+    call.download(result, dRes, got, "result");
+    if (start) call.download(start, dStart, got, "start");
+    if (end) call.download(end, dEnd, got, "end");
+  }
+  return call.wait();
+}
+
+// how the calling thread's last redgpu_match_all_long_dev call resolved its chunks
+int redgpu_diag_match_all_long_dev(const redgpu_dfa *dfa, uint32_t *stats, void *stream) {
+  if (int rc = checkHandle(dfa)) return rc;
+  if (!stats) return fail(REDGPU_EAPI, "null stats buffer");
+  if (!tlsMlCtl || tlsMlStream != static_cast<hipStream_t>(stream))
+    return fail(REDGPU_EAPI, "no chunked match_all_long call of this thread on this stream");
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  const hipError_t e = hipMemcpyAsync(stats, tlsMlCtl, 8 * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                                      static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return failHip(e, "hipMemcpyAsync");
+  return REDGPU_OK;
+}
+
 int redgpu_replace_batch_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
                              const uint64_t *offsets, uint64_t stride, uint64_t n,
                              const uint8_t *repl, uint64_t repl_len, uint64_t max_count,

@@ -511,6 +511,55 @@ def collect_long(exe, text, cap=None, *, chunk_bytes=0):
     return count, res[:k], st[:k], en[:k]
 
 
+def match_all_long(exe, text, cap=None, do_leader=True, *, chunk_bytes=0):
+    """matchAll (include/Matcher.h:711-766; lib/Matcher.cpp:97-102 runs it with doLeader = true)
+    over ONE long text, chunk-parallel on the GPU (redgpu_match_all_long[_dev]) -> (count, result
+    int32[k], start uint64[k], end uint64[k]) with k = min(count, cap).  text, cap and chunk_bytes
+    as in collect_long: bytes / numpy uint8, or a contiguous uint8 CUDA tensor on torch's current
+    stream (the arrays then come back as CUDA tensors)."""
+    if cap is not None and cap < 0:
+        raise RedExceptApi("cap must be >= 0")
+    lead = 1 if do_leader else 0
+    if _is_torch(text):
+        import torch
+        if not text.is_cuda or text.dtype != torch.uint8 or not text.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = text.device
+        stream = torch.cuda.current_stream(dev)
+        room = 4096 if cap is None else cap
+        for _ in range(2):
+            cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+            res = torch.empty(max(room, 1), dtype=torch.int32, device=dev)
+            st = torch.empty(max(room, 1), dtype=torch.int64, device=dev)
+            en = torch.empty(max(room, 1), dtype=torch.int64, device=dev)
+            _check(_lib.lib().redgpu_match_all_long_dev(
+                exe._h, lead, text.data_ptr() if text.numel() else None, text.numel(),
+                int(chunk_bytes), room, cnt.data_ptr(), res.data_ptr(), st.data_ptr(),
+                en.data_ptr(), stream.cuda_stream))
+            count = int(cnt.item())
+            if cap is not None or count <= room:
+                break
+            room = count
+        k = min(count, room)
+        return count, res[:k], st[:k], en[:k]
+    a = _host_u8(text)
+    room = 4096 if cap is None else cap
+    for _ in range(2):
+        cnt = C.c_uint64(0)
+        res = np.zeros(max(room, 1), dtype=np.int32)
+        st = np.zeros(max(room, 1), dtype=np.uint64)
+        en = np.zeros(max(room, 1), dtype=np.uint64)
+        _check(_lib.lib().redgpu_match_all_long(
+            exe._h, lead, a.ctypes.data if a.size else None, a.size, int(chunk_bytes), room,
+            C.byref(cnt), res.ctypes.data, st.ctypes.data, en.ctypes.data))
+        count = int(cnt.value)
+        if cap is not None or count <= room:
+            break
+        room = count
+    k = min(count, room)
+    return count, res[:k], st[:k], en[:k]
+
+
 def match_all_batch(exe, data, cap, do_leader=True, *, offsets=None, stride=0, n=None):
     """matchAll (include/Matcher.h:711-766; the reference's public entry, lib/Matcher.cpp:97-102,
     runs with doLeader = true) over every line: one anchored walk reporting each maximal run of

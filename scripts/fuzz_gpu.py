@@ -3,11 +3,11 @@ random placement and kernel-selection flags, against the CPU oracle.  Not part o
 suite (it is open-ended); a failure prints the case and exits non-zero.
 usage: fuzz_gpu.py [cases] [seed] [hot | cls | lists | blocks | long]
 long: the DFAs and placement flags of the general mode, one buffer of 2 KiB to 128 KiB as ONE
-text through collect_long, replace_long and search_long (random style, leader setting, chunk
-size, cap / max count and replacement).  Without a pure dead state an attempt that does not
-accept walks to the end of the text - quadratic on the CPU and on the device's one lane - so
-those DFAs get the first KiB of the buffer, and so do DFAs whose pure dead state the text's
-walks do not reach (walks_die)."""
+text through collect_long, replace_long, search_long and match_all_long (random style, leader
+setting, chunk size, cap / max count and replacement).  Without a pure dead state an attempt that
+does not accept walks to the end of the text - quadratic on the CPU and on the device's one lane -
+so those DFAs get the first KiB of the buffer, and so do DFAs whose pure dead state the text's
+walks do not reach (walks_die); match_all_long is one anchored walk and always gets all of it."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -131,11 +131,13 @@ def walks_die(cpu, data):
 
 
 def long_case(desc, blob, exe, cpu, data):
-    """collect_long, replace_long and search_long over data as one text; the failing call or None"""
+    """collect_long, replace_long, search_long and match_all_long over data as one text; the
+    failing call or None"""
+    whole = data
     if exe.info["n_pure_dead"] == 0 or not walks_die(cpu, data):
         data = data[:1024]
     text = data.tobytes()
-    for verb in ("collect_long", "replace_long", "search_long"):
+    for verb in ("collect_long", "replace_long", "search_long", "match_all_long"):
         sty = int(rng.integers(1, 6))
         lead = int(rng.integers(0, 2))
         chunk = int(rng.choice([0, 1, 3, 16, 64, 1000, 4096]))
@@ -154,6 +156,15 @@ def long_case(desc, blob, exe, cpu, data):
             ok = one_amd.replace_long(exe, data, repl, sty, bool(lead), mx, chunk_bytes=chunk) == \
                 cpu.replace(text, repl, sty, bool(lead), mx)
             what = (verb, chunk, sty, lead, repl, mx)
+        elif verb == "match_all_long":
+            cap = [None, 0, 5, 4096][int(rng.integers(0, 4))]
+            recs, k = cpu.match_all(whole.tobytes(), bool(lead), 4096 if cap is None else max(cap, 1))
+            if cap is None and k > len(recs):
+                recs, k = cpu.match_all(whole.tobytes(), bool(lead), k)
+            cnt, r, s, e = one_amd.match_all_long(exe, whole, cap, bool(lead), chunk_bytes=chunk)
+            ok = cnt == k and list(zip(r.tolist(), s.tolist(), e.tolist())) == \
+                (recs if cap is None else recs[:cap])
+            what = (verb, chunk, lead, cap, len(whole))
         else:
             ok = one_amd.search_long(exe, data, sty, bool(lead), chunk_bytes=chunk) == \
                 tuple(int(v) for v in cpu.search(text, sty, bool(lead)))
