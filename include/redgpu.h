@@ -487,6 +487,46 @@ int redgpu_match_text(const redgpu_dfa *dfa, int style, int do_leader, const uin
                       uint64_t len, uint8_t delim, uint64_t *offsets, uint64_t cap,
                       uint64_t *n_lines, int32_t *result, uint64_t *start, uint64_t *end);
 
+/* grep: raw text in, only the lines that match out - include/Red.h:65 names the use
+ * ("searchInstant() - appropriate for grep"), tools/skim_red.cpp:36-46 is its loop: the lines
+ * lib/Util.cpp:109-130 cuts, each handed to search<style,doLeader> (include/Matcher.h:172-173,
+ * core 557-640).
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter are not a line.
+ *  - Line k is selected iff (search<style,do_leader>(line k).result_ > 0) != (invert != 0)
+ *    (invert = grep -v).  The verb goes through the identities every batch launch applies first;
+ *    for every DFA the Outcome is exactly what redgpu_search_batch gives for that line.
+ *  - The selected lines are reported in text order, as record j of line / begin / finish /
+ *    result / start / end: line[j] = the 0-based index of the line, begin[j] = the offset of its
+ *    first byte in data, finish[j] = the offset of its delimiter, result/start/end[j] = the
+ *    Outcome of search on that line alone, positions relative to begin[j] (redgpu_match_text's
+ *    convention); under invert the Outcome of a selected line is (0, 0, 0).
+ *  - *n_selected = min(selected lines, max_count) (max_count = grep -m); it may exceed cap, and
+ *    then only the first cap records are stored.  *n_lines = delimiters found.
+ *  - Every array pointer and n_lines may be NULL, each on its own; all arrays NULL, or cap == 0,
+ *    gives the count only (grep -c), and no line is walked twice.
+ *  - REDGPU_EAPI for a NULL n_selected or a NULL data with len > 0 (checked before the handle's
+ *    device is looked at), REDGPU_EEXEC for a style that does not exist, REDGPU_ELIMIT for a
+ *    text redgpu_split_lines refuses.
+ *  - An empty text, or one without a delimiter: *n_lines = 0 and *n_selected = 0 (the _dev form
+ *    writes them on the stream).
+ * redgpu_last_kernel() says "k_grep_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - no count is read
+ * back, and no per-line array is needed from the caller or in scratch (the lines are driven from
+ * the split's delimiter bitmap; scratch is len / 4 + 32 bytes per 16 KiB of text).
+ * redgpu_grep_text: host buffers - one upload of the text, then n_lines, n_selected and the
+ * filled prefixes back. */
+int redgpu_grep_text(const redgpu_dfa *dfa, int style, int do_leader, int invert,
+                     const uint8_t *data, uint64_t len, uint8_t delim, uint64_t max_count,
+                     uint64_t cap, uint64_t *n_lines, uint64_t *n_selected, uint64_t *line,
+                     uint64_t *begin, uint64_t *finish, int32_t *result, uint64_t *start,
+                     uint64_t *end);
+int redgpu_grep_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int invert,
+                         const uint8_t *data, uint64_t len, uint8_t delim, uint64_t max_count,
+                         uint64_t cap, uint64_t *n_lines, uint64_t *n_selected, uint64_t *line,
+                         uint64_t *begin, uint64_t *finish, int32_t *result, uint64_t *start,
+                         uint64_t *end, void *stream);
+
 /* Measurement aid, no counterpart in the reference: one streaming read of `bytes` of device
  * memory (16-byte aligned) on the handle's device, asynchronous on `stream` - the read-bandwidth
  * calibration bench.py reports beside the roofline.  `sink` is a device uint32 the kernel may

@@ -185,6 +185,52 @@ inline std::vector<Outcome> matchText(const Executable &exec, std::string_view t
   return out;
 }
 
+// grep (include/Red.h:65: "searchInstant() - appropriate for grep"; tools/skim_red.cpp:36-46): the
+// lines of a text blob that search<style,doLeader> selects - result > 0, or the others under
+// invert - in text order, at most max of them.  line_ = the line's 0-based index, [begin_, end_) =
+// the line in `text` (end_ = its delimiter), outcome_ = search on that line alone (positions
+// relative to begin_; {0, 0, 0} under invert).
+struct GrepHit {
+  size_t line_, begin_, end_;
+  Outcome outcome_;
+};
+
+// room for text.size() / 128 + 16 records first, one retry with the exact count
+inline std::vector<GrepHit> grepText(const Executable &exec, std::string_view text,
+                                     Style style = styInstant, bool doLeader = true,
+                                     bool invert = false, char delim = '\n',
+                                     size_t max = SIZE_MAX) {
+  const Byte *p = reinterpret_cast<const Byte *>(text.data());
+  uint64_t cap = text.size() / 128 + 16, found = 0;
+  std::vector<uint64_t> ln, bg, fn, s, e;
+  std::vector<Result> r;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    ln.resize(cap); bg.resize(cap); fn.resize(cap); s.resize(cap); e.resize(cap); r.resize(cap);
+    throwOnError(redgpu_grep_text(exec.handle(), style, doLeader, invert, p, text.size(),
+                                  Byte(delim), max, cap, nullptr, &found, ln.data(), bg.data(),
+                                  fn.data(), r.data(), s.data(), e.data()));
+    if (found <= cap) break;
+    cap = found;
+  }
+  std::vector<GrepHit> out(found < cap ? found : cap);
+  for (size_t i = 0; i < out.size(); ++i)
+    out[i] = GrepHit{size_t(ln[i]), size_t(bg[i]), size_t(fn[i]),
+                     Outcome{r[i], size_t(s[i]), size_t(e[i])}};
+  return out;
+}
+
+// grep -c: the count alone, no records
+inline size_t grepCount(const Executable &exec, std::string_view text, Style style = styInstant,
+                        bool doLeader = true, bool invert = false, char delim = '\n',
+                        size_t max = SIZE_MAX) {
+  uint64_t found = 0;
+  throwOnError(redgpu_grep_text(exec.handle(), style, doLeader, invert,
+                                reinterpret_cast<const Byte *>(text.data()), text.size(),
+                                Byte(delim), max, 0, nullptr, &found, nullptr, nullptr, nullptr,
+                                nullptr, nullptr, nullptr));
+  return size_t(found);
+}
+
 // ---- several GPUs of one node: one image per device, contiguous shards, results in the caller's
 // arrays - the device form of tools/thr_red.cpp:84-91 (N workers over one shared Red).  devices
 // may name a device more than once (the shards then share it). ----------------------------------

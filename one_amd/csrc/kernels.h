@@ -189,6 +189,19 @@ hipError_t launchSplitLines(const uint8_t *data, uint64_t len, uint8_t delim, ui
                             uint64_t cap, uint64_t *nLines, uint32_t *counts, uint64_t *bases,
                             uint16_t *masks, hipStream_t stream);
 
+// grep over a raw text (k_grep.h): the lines of launchSplitLines' rule that search<style, doLeader>
+// selects (result > 0, or the others under invert), as records in text order: *nSelected =
+// min(selected, maxCount), the first min(*nSelected, cap) records in line / begin / finish /
+// result / start / end (each may be null, nLines too).  scratch: grepScratchBytes(len) bytes of
+// device memory, 16-byte aligned.  *kernelName = "k_grep_text".
+uint64_t grepScratchBytes(uint64_t len);
+hipError_t launchGrepText(const DevDfa &dfa, int style, int doLeader, int invert, const uint8_t *data,
+                          uint64_t len, uint8_t delim, uint64_t maxCount, uint64_t cap,
+                          uint64_t *nLines, uint64_t *nSelected, uint64_t *line, uint64_t *begin,
+                          uint64_t *finish, int32_t *result, uint64_t *start, uint64_t *end,
+                          void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                          const char **kernelName);
+
 // bench.py's read-bandwidth calibration: one streaming pass over `bytes` (16-byte aligned).
 hipError_t launchDiagRead(const void *data, uint64_t bytes, uint32_t *sink, int numCUs,
                           hipStream_t stream);

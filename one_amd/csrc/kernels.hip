@@ -38,6 +38,8 @@
 //   k_style_blocks.h  k_style_blocks: early-exit styles and odd strides over the block walk
 //   k_misc.h          k_advance, k_replace (+ scan), k_visits, k_walked
 //   k_split.h         line splitting on the device
+//   k_grep.h          k_gp_*: grep over a raw text - the split's delimiter bitmap drives the lines,
+//                     a wave per 16 KiB chunk selects, a scan orders, a second pass writes records
 //   k_diag.h          bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
@@ -50,16 +52,18 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled three times in parallel (Makefile: -DREDGPU_TU=1/2/3): the templates are
+// This file is compiled four times in parallel (Makefile: -DREDGPU_TU=1/2/3/4): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
-// 3 = everything else and the dispatch.  REDGPU_TU undefined or 0 = all of it in one unit.
+// 3 = everything else and the dispatch, 4 = k_grep.  REDGPU_TU undefined or 0 = all of it in one
+// unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
 #endif
 #define REDGPU_TU_STREAM (REDGPU_TU == 0 || REDGPU_TU == 1)
 #define REDGPU_TU_RAGGED (REDGPU_TU == 0 || REDGPU_TU == 2)
 #define REDGPU_TU_GENERIC (REDGPU_TU == 0 || REDGPU_TU == 3)
+#define REDGPU_TU_GREP (REDGPU_TU == 0 || REDGPU_TU == 4)
 
 namespace redgpu {
 
@@ -85,6 +89,7 @@ namespace {
 #include "k_split.h"
 #include "k_diag.h"
 #include "launchers.h"
+#include "k_grep.h"
 
 } // namespace
 
@@ -869,8 +874,10 @@ hipError_t launchAdvance(const DevDfa &d, const Batch &b, uint32_t *state, const
 #undef AD_CALL
 }
 
+#endif  // REDGPU_TU_GENERIC
+
 // The identities launchBatch applies before it picks a kernel.
-static void normalizeVerbStyle(const DevDfa &d, const LaunchCfg &cfg, bool lead, int &verb,
+[[maybe_unused]] static void normalizeVerbStyle(const DevDfa &d, const LaunchCfg &cfg, bool lead, int &verb,
                                int &style) {
   // L = SIGMA* L (DfaImage::suffixClosed - patterns added with a loose start) and no leader: the
   // sliding loops of scan and search (Matcher.h:511-553, :575-621) ARE their first attempt.  It
@@ -892,6 +899,75 @@ static void normalizeVerbStyle(const DevDfa &d, const LaunchCfg &cfg, bool lead,
     style = kStyLast;
 }
 
+#if REDGPU_TU_GREP
+// grep over a raw text (k_grep.h): the split's count and scan as they stand, then the k_gp_* passes.
+// scratch: grepScratchBytes(len) bytes, 16-byte aligned.
+uint64_t grepScratchBytes(uint64_t len) {
+  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
+  return nChunks * 32 + 32 + 2 * nChunks * (kSplitChunk / 8);
+}
+
+hipError_t launchGrepText(const DevDfa &d, int style, int doLeader, int invert, const uint8_t *data,
+                          uint64_t len, uint8_t delim, uint64_t maxCount, uint64_t cap,
+                          uint64_t *nLines, uint64_t *nSelected, uint64_t *line, uint64_t *begin,
+                          uint64_t *finish, int32_t *result, uint64_t *start, uint64_t *end,
+                          void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                          const char **kernelName) {
+  *kernelName = "k_grep_text";
+  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
+  // [bases, open, selBases: u64[nChunks] each][counts, selCounts: u32[nChunks] each]
+  // [lines, total, dummy: u64, 8 spare][delimiter bitmap][selected bitmap]
+  uint8_t *q = static_cast<uint8_t *>(scratch);
+  uint64_t *bases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint64_t *open = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint64_t *selBases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint32_t *counts = reinterpret_cast<uint32_t *>(q); q += nChunks * 4;
+  uint32_t *selCounts = reinterpret_cast<uint32_t *>(q); q += nChunks * 4;
+  uint64_t *misc = reinterpret_cast<uint64_t *>(q); q += 32;
+  uint16_t *masks = reinterpret_cast<uint16_t *>(q); q += nChunks * (kSplitChunk / 8);
+  uint16_t *selMasks = reinterpret_cast<uint16_t *>(q);
+  uint64_t *total = misc + 1, *dummy = misc + 2;
+  if (nChunks) {
+    hipLaunchKernelGGL(k_split_count, dim3(uint32_t(nChunks)), dim3(kSplitThreads), 0, stream, data,
+                       len, uint32_t(delim), nChunks, counts, masks);
+  }
+  // (k_split_scan's offsets[0] store goes to a spare word)
+  hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, counts, nChunks, bases,
+                     nLines ? nLines : misc, dummy, uint64_t(0));
+  if (nChunks) {
+    uint64_t small = (nChunks + 3) / 4;
+    if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
+    hipLaunchKernelGGL(k_gp_last, dim3(uint32_t(small)), dim3(256), 0, stream, masks, counts,
+                       nChunks, open, selMasks);
+    hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, open, nChunks);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
+  int verb = kSearch;
+  normalizeVerbStyle(d, cfg, lead != 0, verb, style);
+  const GpBufs b{masks, selMasks, bases, open, selCounts, selBases, nChunks};
+  const GpOut out{cap < maxCount ? cap : maxCount, line, begin, finish, result, start, end};
+  const bool write = out.limit > 0 && (line || begin || finish || result || start || end);
+#define GP_ARGS d, data, b, style, lead, invert, out, write, total, maxCount, nSelected, selBases, \
+                dummy, cfg, stream
+#define GP_CALL(K) \
+  (verb == kSearch ? launchGrepK<K, kSearch>(GP_ARGS) : launchGrepK<K, kMatch>(GP_ARGS))
+  switch (d.tableKind) {
+  case REDGPU_TAB_LDS_FUSED_U8: return GP_CALL(REDGPU_TAB_LDS_FUSED_U8);
+  case REDGPU_TAB_LDS_FUSED_U16: return GP_CALL(REDGPU_TAB_LDS_FUSED_U16);
+  case REDGPU_TAB_LDS_CLASS_U16: return GP_CALL(REDGPU_TAB_LDS_CLASS_U16);
+  case REDGPU_TAB_GLOBAL_U16: return GP_CALL(REDGPU_TAB_GLOBAL_U16);
+  case REDGPU_TAB_HOT_ROWS: return GP_CALL(REDGPU_TAB_HOT_ROWS);
+  case REDGPU_TAB_LDS_SPARSE: return GP_CALL(REDGPU_TAB_LDS_SPARSE);
+  default: return GP_CALL(REDGPU_TAB_GLOBAL_U32);
+  }
+#undef GP_CALL
+#undef GP_ARGS
+}
+#endif  // REDGPU_TU_GREP
+
+#if REDGPU_TU_GENERIC
 hipError_t launchBatches(const DevDfa &d, const Batch *bs, uint32_t nb, int verb, int style,
                          int doLeader, const LaunchCfg &cfg, hipStream_t stream,
                          const char **kernelName) {

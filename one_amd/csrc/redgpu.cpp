@@ -1160,6 +1160,82 @@ int redgpu_match_text(const redgpu_dfa *dfa, int style, int do_leader, const uin
   return call.wait();
 }
 
+// the arguments of both grep forms: what can be refused without a device first
+static int checkGrepText(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
+                         const uint64_t *nSelected) {
+  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
+  if (!nSelected) return fail(REDGPU_EAPI, "null n_selected buffer");
+  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
+  if (int rc = checkStyle(style)) return rc;
+  if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
+  return checkHandle(dfa);
+}
+
+// raw text -> the lines search selects, as records in text order (k_grep.h): everything on
+// `stream`, no count read back
+int redgpu_grep_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int invert,
+                         const uint8_t *data, uint64_t len, uint8_t delim, uint64_t max_count,
+                         uint64_t cap, uint64_t *n_lines, uint64_t *n_selected, uint64_t *line,
+                         uint64_t *begin, uint64_t *finish, int32_t *result, uint64_t *start,
+                         uint64_t *end, void *stream) {
+  if (int rc = checkGrepText(dfa, style, data, len, n_selected)) return rc;
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // ONE allocation for the call, carved up by launchGrepText: the split's pieces and the grep's own
+  void *scratch = nullptr;
+  HIP_TRY(scratchFor(s, size_t(grepScratchBytes(len)), &scratch), "hipMalloc scratch");
+  const LaunchCfg cfg = cfgOf(dfa);
+  const char *name = "";
+  const hipError_t e = launchGrepText(dfa->im->dev, style, do_leader ? 1 : 0, invert ? 1 : 0, data,
+                                      len, delim, max_count, cap, n_lines, n_selected, line, begin,
+                                      finish, result, start, end, scratch, cfg, s, &name);
+  tlsKernel = name;
+  if (e != hipSuccess) return failHip(e, "kernel launch");
+  return REDGPU_OK;
+}
+
+// host-buffer form: one upload of the text, then the two counts and the filled prefixes back
+int redgpu_grep_text(const redgpu_dfa *dfa, int style, int do_leader, int invert,
+                     const uint8_t *data, uint64_t len, uint8_t delim, uint64_t max_count,
+                     uint64_t cap, uint64_t *n_lines, uint64_t *n_selected, uint64_t *line,
+                     uint64_t *begin, uint64_t *finish, int32_t *result, uint64_t *start,
+                     uint64_t *end) {
+  if (int rc = checkGrepText(dfa, style, data, len, n_selected)) return rc;
+  if (cap > len) cap = len;  // a buffer holds no more lines than bytes
+  if (cap > max_count) cap = max_count;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dN = call.buf<uint64_t>(kSlAux0, 2, "counts");
+  uint64_t *dLine = line && cap ? call.buf<uint64_t>(kSlOff, cap, "line") : nullptr;
+  uint64_t *dBegin = begin && cap ? call.buf<uint64_t>(kSlAux1, cap, "begin") : nullptr;
+  uint64_t *dFinish = finish && cap ? call.buf<uint64_t>(kSlAux2, cap, "finish") : nullptr;
+  int32_t *dRes = result && cap ? call.buf<int32_t>(kSlRes, cap, "result") : nullptr;
+  uint64_t *dStart = start && cap ? call.buf<uint64_t>(kSlStart, cap, "start") : nullptr;
+  uint64_t *dEnd = end && cap ? call.buf<uint64_t>(kSlEnd, cap, "end") : nullptr;
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return redgpu_grep_text_dev(dfa, style, do_leader, invert, dData, len, delim, max_count, cap,
+                                dN, dN + 1, dLine, dBegin, dFinish, dRes, dStart, dEnd,
+                                call.stream());
+  });
+  uint64_t counts[2] = {0, 0};
+  call.download(counts, dN, 2, "counts");
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = counts[0];
+  *n_selected = counts[1];
+  const uint64_t got = counts[1] < cap ? counts[1] : cap;
+  if (got) {
+    if (dLine) call.download(line, dLine, got, "line");
+    if (dBegin) call.download(begin, dBegin, got, "begin");
+    if (dFinish) call.download(finish, dFinish, got, "finish");
+    if (dRes) call.download(result, dRes, got, "result");
+    if (dStart) call.download(start, dStart, got, "start");
+    if (dEnd) call.download(end, dEnd, got, "end");
+  }
+  return call.wait();
+}
+
 int redgpu_split_lines(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                        uint64_t *offsets, uint64_t cap, uint64_t *n_lines) {
   if (int rc = checkHandle(dfa)) return rc;

@@ -854,6 +854,73 @@ def match_text(exe, data, style, do_leader=True, *, delim=b"\n", cap=None, want_
             en[:k] if en is not None else None)
 
 
+def grep_text(exe, data, style=styInstant, do_leader=True, *, invert=False, delim=b"\n", cap=None,
+              max_count=1 << 62, want_outcome=True):
+    """redgpu_grep_text[_dev]: the delimiter-terminated lines of a raw text buffer that
+    search<style,doLeader> selects (result > 0; invert=True: the others, grep -v), as compact
+    records in text order - include/Red.h:65's "appropriate for grep", tools/skim_red.cpp:36-46's
+    loop.  Record j: line[j] = the line's 0-based index, begin[j] / finish[j] = the offsets of its
+    first byte and of its delimiter, result / start / end[j] = the Outcome of search on that line
+    alone (positions relative to begin[j]; (0, 0, 0) under invert).  n_selected = min(selected
+    lines, max_count) (grep -m) and may exceed cap.
+    Host input -> (n_lines, n_selected, line, begin, finish, result, start, end): numpy arrays
+    trimmed to min(n_selected, cap); cap=None sizes them with a counting call first (the text is
+    then uploaded twice - pass a cap to avoid that - unless nothing is selected); cap=0 only
+    counts (grep -c).  want_outcome=False leaves result / start / end None (no line is walked a
+    second time).
+    A CUDA uint8 tensor needs cap -> the same tuple as device tensors, n_lines and n_selected as
+    1-element int64 tensors, asynchronously on the current stream and without any read-back;
+    entries from min(n_selected, cap) on are untouched."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    style, lead, inv = int(style), 1 if do_leader else 0, 1 if invert else 0
+    max_count = int(max_count)
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        if cap is None:
+            raise RedExceptApi("device grep_text needs cap (room in the output tensors)")
+        dev = data.device
+        cnt = torch.empty(2, dtype=torch.int64, device=dev)
+        ln, bg, fn = (torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(3))
+        res = torch.empty(cap, dtype=torch.int32, device=dev) if want_outcome else None
+        st = torch.empty(cap, dtype=torch.int64, device=dev) if want_outcome else None
+        en = torch.empty(cap, dtype=torch.int64, device=dev) if want_outcome else None
+        _check(l.redgpu_grep_text_dev(
+            exe._h, style, lead, inv, data.data_ptr() if data.numel() else None, data.numel(), d,
+            max_count, cap, cnt.data_ptr(), cnt.data_ptr() + 8, ln.data_ptr(), bg.data_ptr(),
+            fn.data_ptr(), res.data_ptr() if want_outcome else None,
+            st.data_ptr() if want_outcome else None, en.data_ptr() if want_outcome else None,
+            torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], ln, bg, fn, res, st, en
+    a = _host_u8(data)
+    dp = a.ctypes.data if a.size else None
+    nl, ns = C.c_uint64(0), C.c_uint64(0)
+    if cap is None:
+        _check(l.redgpu_grep_text(exe._h, style, lead, inv, dp, a.size, d, max_count, 0,
+                                  C.byref(nl), C.byref(ns), None, None, None, None, None, None))
+        cap = int(ns.value)
+        if cap == 0:  # nothing selected: the counting call said it all
+            none = lambda dt: np.zeros(0, dtype=dt) if want_outcome else None  # noqa: E731
+            u = np.zeros(0, dtype=np.uint64)
+            return (int(nl.value), 0, u, u.copy(), u.copy(), none(np.int32), none(np.uint64),
+                    none(np.uint64))
+    cap = int(cap)
+    ln, bg, fn = (np.zeros(cap, dtype=np.uint64) for _ in range(3))
+    res = np.zeros(cap, dtype=np.int32) if want_outcome else None
+    st = np.zeros(cap, dtype=np.uint64) if want_outcome else None
+    en = np.zeros(cap, dtype=np.uint64) if want_outcome else None
+    _check(l.redgpu_grep_text(
+        exe._h, style, lead, inv, dp, a.size, d, max_count, cap, C.byref(nl), C.byref(ns),
+        ln.ctypes.data, bg.ctypes.data, fn.ctypes.data,
+        res.ctypes.data if want_outcome else None, st.ctypes.data if want_outcome else None,
+        en.ctypes.data if want_outcome else None))
+    k = min(int(ns.value), cap)
+    cut = lambda x: x[:k] if x is not None else None  # noqa: E731
+    return (int(nl.value), int(ns.value), ln[:k], bg[:k], fn[:k], cut(res), cut(st), cut(en))
+
+
 class StatefulMatcher:
     """Mirror of zezax::red::StatefulMatcher (include/Matcher.h:770-792): `advance(byte)` and
     `result()`; `advance_bytes` feeds a whole chunk in one kernel launch.  The executable must

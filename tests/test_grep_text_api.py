@@ -1,0 +1,69 @@
+"""redgpu_grep_text[_dev] (the lines of a raw text that match, as compact records): the C-ABI
+face that needs no GPU - the symbols, refused NULL arguments, refused device-less handles."""
+import ctypes as C
+
+import pytest
+
+import one_amd
+from one_amd import _lib
+from golden_util import load_dfa
+
+TEXT = b"123\nabc\n45\n"
+
+
+def _args(data=TEXT, n_selected=None, arrays=None, cap=4, style=1):
+    """(style, do_leader, invert, data, len, delim, max_count, cap, n_lines, n_selected, six arrays)"""
+    a = arrays or [None] * 6
+    return [style, 1, 0, data, len(TEXT), 0x0A, 1 << 62, cap, None, n_selected, *a]
+
+
+def test_grep_text_symbols_exported():
+    lib = _lib.lib()
+    for name in ("redgpu_grep_text", "redgpu_grep_text_dev"):
+        assert hasattr(lib, name), name
+        assert name in _lib.declared_symbols(), name
+    assert "grep_text" in one_amd.__all__
+    assert callable(one_amd.grep_text)
+
+
+def test_grep_text_null_handle_refused():
+    lib = _lib.lib()
+    cnt = C.c_uint64(7)
+    assert lib.redgpu_grep_text(None, *_args(n_selected=C.byref(cnt))) == _lib.EAPI
+    assert "handle" in lib.redgpu_last_error().decode()
+    assert lib.redgpu_grep_text_dev(None, *_args(n_selected=C.byref(cnt)), None) == _lib.EAPI
+    assert "handle" in lib.redgpu_last_error().decode()
+    assert cnt.value == 7
+
+
+@pytest.mark.parametrize("form", ["host", "dev"])
+def test_grep_text_null_arguments_refused(form):
+    exe = one_amd.Executable(load_dfa("num3"), device="none")
+    lib = _lib.lib()
+    f = lib.redgpu_grep_text if form == "host" else lib.redgpu_grep_text_dev
+    extra = [] if form == "host" else [None]
+    cnt = C.c_uint64(7)
+    line = (C.c_uint64 * 4)()
+    arrays = [line, None, None, None, None, None]
+    # NULL n_selected, NULL data with len > 0: each refused for its own reason (the argument
+    # checks run before the handle's device is looked at)
+    assert f(exe._h, *_args(n_selected=None, arrays=arrays), *extra) == _lib.EAPI
+    assert "n_selected" in lib.redgpu_last_error().decode(), lib.redgpu_last_error()
+    assert f(exe._h, *_args(data=None, n_selected=C.byref(cnt), arrays=arrays), *extra) == _lib.EAPI
+    assert "null data" in lib.redgpu_last_error().decode(), lib.redgpu_last_error()
+    # a style that does not exist
+    assert f(exe._h, *_args(n_selected=C.byref(cnt), style=9), *extra) == _lib.EEXEC
+    # ... and with nothing wrong, for the missing device; every array NULL is no fault
+    assert f(exe._h, *_args(n_selected=C.byref(cnt), arrays=arrays), *extra) == _lib.EAPI
+    assert "device" in lib.redgpu_last_error().decode()
+    assert f(exe._h, *_args(n_selected=C.byref(cnt), cap=0), *extra) == _lib.EAPI
+    assert "device" in lib.redgpu_last_error().decode()
+    assert cnt.value == 7
+
+
+def test_grep_text_device_none_handle_refused():
+    exe = one_amd.Executable(load_dfa("num3"), device="none")
+    with pytest.raises(one_amd.RedExceptApi):
+        one_amd.grep_text(exe, TEXT)
+    with pytest.raises(one_amd.RedExceptApi):
+        one_amd.grep_text(exe, b"", one_amd.styLast, False, invert=True, cap=0)
