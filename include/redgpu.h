@@ -247,7 +247,14 @@ int redgpu_collect_long(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len
  *                              reporting every maximal run of bytes with the same accepted result
  *                              (RE2::Set::Match style).  The reference's public entry always
  *                              runs with doLeader = true: pass do_leader = 1 for parity with it.
- *                              Record layout and counts[] exactly as redgpu_collect_batch. */
+ *                              Record layout and counts[] exactly as redgpu_collect_batch.
+ *                              redgpu_last_kernel() names the kernel launched: "k_matchall" (a
+ *                              test per byte: tables outside LDS, REDGPU_F_FORCE_GENERIC, a pure
+ *                              dead end with a way out) or the block-wise form,
+ *                              "k_matchall_blocks<1024,1>", "k_matchall_blocks<512,1>" (at most
+ *                              256 states, one staged byte per position),
+ *                              "k_matchall_blocks<1024,2>" or "k_matchall_blocks<512,2>" (two);
+ *                              1024 or 512 threads, whichever keeps more lanes on a CU. */
 int redgpu_match_all_batch(const redgpu_dfa *dfa, int do_leader, const uint8_t *data,
                            const uint64_t *offsets, uint64_t stride, uint64_t n, uint64_t cap,
                            uint64_t *counts, int32_t *result, uint64_t *start, uint64_t *end);

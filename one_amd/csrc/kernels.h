@@ -130,8 +130,11 @@ hipError_t launchCollectLong(const DevDfa &dfa, const uint8_t *data, uint64_t n,
                              const char **kernelName);
 
 // matchAll per line (include/Matcher.h:711-766): same record layout as launchCollect.
+// *kernelName = the kernel launched: "k_matchall" (one walk per lane, a test per byte) or the
+// block-wise "k_matchall_blocks<THREADS,W>" with THREADS = 1024 | 512 and W = 1 | 2.
 hipError_t launchMatchAll(const DevDfa &dfa, const Batch &b, uint64_t cap, uint64_t *counts,
-                          int doLeader, const LaunchCfg &cfg, hipStream_t stream);
+                          int doLeader, const LaunchCfg &cfg, hipStream_t stream,
+                          const char **kernelName);
 
 // matchAll over ONE text of n bytes (k_match_all_long.h): *count = records found, the first
 // min(count, cap) complete at result/start/end[0..); chunkBytes = 0 chooses the chunk size.

@@ -664,10 +664,12 @@ hipError_t launchSearchLong(const DevDfa &d, int style, int doLeader, const uint
 }
 
 hipError_t launchMatchAll(const DevDfa &d, const Batch &b, uint64_t cap, uint64_t *counts,
-                          int doLeader, const LaunchCfg &cfg, hipStream_t stream) {
+                          int doLeader, const LaunchCfg &cfg, hipStream_t stream,
+                          const char **kernelName) {
+  *kernelName = "k_matchall";
   if (b.n == 0) return hipSuccess;
   const int lead = doLeader && d.leaderLen > 0;
-#define MA_CALL(K) launchMatchAllK<K>(d, b, cap, counts, lead, cfg, stream)
+#define MA_CALL(K) launchMatchAllK<K>(d, b, cap, counts, lead, cfg, stream, kernelName)
   REDGPU_KIND_SWITCH(MA_CALL)
 #undef MA_CALL
 }
@@ -682,9 +684,11 @@ hipError_t launchMatchAllLong(const DevDfa &d, int doLeader, const uint8_t *data
   // one lane: the empty text, short texts at the automatic size, and pure dead ends with a way
   // out - the walk's stop at one (Matcher.h:755-756) is then observable, and k_matchall has it
   if (n == 0 || (!chunkBytes && n < kClMinText) || !d.deadAbsorbing) {
-    *kernelName = "k_matchall";
     const Batch b{data, nullptr, n, 1, result, start, end};
-    return launchMatchAll(d, b, cap, count, doLeader, cfg, stream);
+    const char *inner = "";  // (the route's name stays "k_matchall", whichever instantiation runs)
+    const hipError_t e = launchMatchAll(d, b, cap, count, doLeader, cfg, stream, &inner);
+    *kernelName = "k_matchall";
+    return e;
   }
   *kernelName = "k_match_all_long";
   const uint64_t c = collectLongChunk(n, chunkBytes, cfg);

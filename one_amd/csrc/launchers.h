@@ -133,7 +133,8 @@ hipError_t launchCollectK(const DevDfa &d, const Batch &b, uint64_t cap, uint64_
 
 template <int KIND>
 hipError_t launchMatchAllK(const DevDfa &d, const Batch &b, uint64_t cap, uint64_t *counts,
-                           int lead, const LaunchCfg &cfg, hipStream_t stream) {
+                           int lead, const LaunchCfg &cfg, hipStream_t stream,
+                           const char **kernelName) {
   constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
   constexpr int kThreads = kLds ? 1024 : 256;
   if constexpr (Tab<KIND>::kInLds) {
@@ -159,6 +160,7 @@ hipError_t launchMatchAllK(const DevDfa &d, const Batch &b, uint64_t cap, uint64
     if (e2 != hipSuccess) return e2;                                                           \
     hipLaunchKernelGGL((k_matchall_blocks<KIND, T, W>), dim3(uint32_t(blocks)), dim3(T),      \
                        ldsBytes, stream, d, b, cap, counts, lead);                             \
+    *kernelName = "k_matchall_blocks<" #T "," #W ">";                                          \
   } while (0)
       if (d.nStates <= 256) { if (big) MAB_LAUNCH(1024, 1); else MAB_LAUNCH(512, 1); }
       else { if (big) MAB_LAUNCH(1024, 2); else MAB_LAUNCH(512, 2); }
@@ -166,6 +168,7 @@ hipError_t launchMatchAllK(const DevDfa &d, const Batch &b, uint64_t cap, uint64
       return hipGetLastError();
     }
   }
+  *kernelName = "k_matchall";
   const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
   hipError_t e = setLds(k_matchall<KIND, kThreads>, ldsBytes);
   if (e != hipSuccess) return e;

@@ -362,11 +362,12 @@ int collectDev(const redgpu_dfa *dfa, int listVerb, const uint8_t *data, const u
   if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
   Batch b{data, offsets, stride, n, result, start, end};
   LaunchCfg cfg{dfa->numCUs, (dfa->flags & REDGPU_F_FORCE_GENERIC) ? 1 : 0};
+  const char *name = "k_collect";
   hipError_t e = listVerb == kListCollect
                      ? launchCollect(dfa->im->dev, b, cap, counts, cfg, stream)
                      : launchMatchAll(dfa->im->dev, b, cap, counts, listVerb == kListMatchAllLeader,
-                                      cfg, stream);
-  tlsKernel = listVerb == kListCollect ? "k_collect" : "k_matchall";
+                                      cfg, stream, &name);
+  tlsKernel = name;
   if (e != hipSuccess) return failHip(e, "kernel launch");
   return REDGPU_OK;
 }

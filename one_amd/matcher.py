@@ -433,10 +433,65 @@ def search_batch(exe, data, style, do_leader=True, *, offsets=None, stride=0, n=
                 out)
 
 
-def collect_batch(exe, data, cap, *, offsets=None, stride=0, n=None):
+def _list_dev(entry, head, data, cap, offsets, stride, n, want_start, want_end, out):
+    """The device form of the record-list verbs (redgpu_collect_batch_dev,
+    redgpu_match_all_batch_dev) over torch CUDA tensors, asynchronous on the current stream ->
+    (counts int64[n], result int32[n,cap], start int64[n,cap] | None, end int64[n,cap] | None).
+    out = (counts, result, start, end): the caller's tensors instead of fresh ones (contiguous, on
+    the data's device, n / n * cap elements; result may be None when cap = 0, start / end None
+    for "not wanted"); they are returned as given."""
+    import torch
+    if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+        raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+    cap = int(cap)
+    if cap < 0:
+        raise RedExceptApi("cap must be >= 0")
+    dev = data.device
+    if offsets is not None:
+        if (not _is_torch(offsets) or offsets.dtype not in (torch.int64, torch.uint64)
+                or not offsets.is_cuda or not offsets.is_contiguous()):
+            raise RedExceptApi("device offsets must be a contiguous int64 CUDA tensor")
+        n = offsets.numel() - 1
+        stride = int(stride or 0)  # with offsets: trailing bytes to drop per line
+    elif n is None:
+        n = data.numel() // stride if stride else 0
+    if out is None:
+        counts = torch.empty(n, dtype=torch.int64, device=dev)
+        res = torch.empty((n, cap), dtype=torch.int32, device=dev)
+        st = torch.empty((n, cap), dtype=torch.int64, device=dev) if want_start else None
+        en = torch.empty((n, cap), dtype=torch.int64, device=dev) if want_end else None
+    else:
+        counts, res, st, en = out
+        need = [(counts, 8, n)] + ([(res, 4, n * cap)] if cap or res is not None else [])
+        need += [(t, 8, n * cap) for t in (st, en) if t is not None]
+        for t, size, room in need:
+            if (not _is_torch(t) or t.device != dev or not t.is_contiguous() or
+                    t.element_size() != size or t.numel() < room):
+                raise RedExceptApi("out tensors must be contiguous, on the data's device and hold "
+                                   "n counts / n * cap records")
+
+    def ptr(t):
+        return t.data_ptr() if t is not None and t.numel() else None
+
+    _check(entry(*head, ptr(data), offsets.data_ptr() if offsets is not None else None, stride, n,
+                 cap, ptr(counts), ptr(res), ptr(st), ptr(en),
+                 torch.cuda.current_stream(dev).cuda_stream))
+    return counts, res, st, en
+
+
+def collect_batch(exe, data, cap, *, offsets=None, stride=0, n=None, want_start=True,
+                  want_end=True, out=None):
     """Red::collect (lib/Red.cpp:103-116) over every line: all non-overlapping matches in order.
     Host arrays in, host arrays out: (counts uint64[n], result int32[n,cap], start uint64[n,cap],
-    end uint64[n,cap]); counts[i] may exceed cap (only the first cap records are kept)."""
+    end uint64[n,cap]); counts[i] may exceed cap (only the first cap records are kept).
+    torch CUDA tensors in (data uint8, offsets int64): redgpu_collect_batch_dev, asynchronous on
+    the current stream, CUDA tensors out (_list_dev: want_start / want_end = False pass that
+    array as NULL and return None for it; out = the caller's output tensors)."""
+    if _is_torch(data):
+        return _list_dev(_lib.lib().redgpu_collect_batch_dev, (exe._h,), data, cap, offsets, stride,
+                         n, want_start, want_end, out)
+    if out is not None or not (want_start and want_end):
+        raise RedExceptApi("out=, want_start= and want_end= go with CUDA tensor input")
     a = _host_u8(data)
     if offsets is not None:
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -560,10 +615,17 @@ def match_all_long(exe, text, cap=None, do_leader=True, *, chunk_bytes=0):
     return count, res[:k], st[:k], en[:k]
 
 
-def match_all_batch(exe, data, cap, do_leader=True, *, offsets=None, stride=0, n=None):
+def match_all_batch(exe, data, cap, do_leader=True, *, offsets=None, stride=0, n=None,
+                    want_start=True, want_end=True, out=None):
     """matchAll (include/Matcher.h:711-766; the reference's public entry, lib/Matcher.cpp:97-102,
     runs with doLeader = true) over every line: one anchored walk reporting each maximal run of
-    one accepted result.  Same return shape as collect_batch."""
+    one accepted result.  Same return shape as collect_batch, and the same device form for torch
+    CUDA tensors (redgpu_match_all_batch_dev)."""
+    if _is_torch(data):
+        return _list_dev(_lib.lib().redgpu_match_all_batch_dev, (exe._h, int(bool(do_leader))),
+                         data, cap, offsets, stride, n, want_start, want_end, out)
+    if out is not None or not (want_start and want_end):
+        raise RedExceptApi("out=, want_start= and want_end= go with CUDA tensor input")
     a = _host_u8(data)
     if offsets is not None:
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -638,10 +700,58 @@ def advance_batch(exe, data, state, *, offsets=None, stride=0, n=None, out=None)
 
 
 def replace_batch(exe, data, repl: bytes, style, do_leader=True, max_count=(1 << 62), *,
-                  offsets=None, stride=0, n=None):
+                  offsets=None, stride=0, n=None, out=None, out_cap=None, sizes=None):
     """replace<style,doLeader> (include/Matcher.h:643-706) over every line: each match replaced
     by `repl`, at most max_count per line.  Host arrays in and out:
-    (counts uint64[n], out_offsets uint64[n+1], out uint8[out_offsets[n]])."""
+    (counts uint64[n], out_offsets uint64[n+1], out uint8[out_offsets[n]]).
+    torch CUDA tensors in (data uint8, offsets int64): redgpu_replace_batch_dev in ONE call,
+    asynchronous on the current stream -> (counts int64[n], out_offsets int64[n+1], out).  out =
+    a contiguous uint8 CUDA tensor to write into and out_cap its capacity (default: its size):
+    every line that fits entirely below out_cap is written, nothing is retried; out = None gives
+    the sizes only.  sizes = (counts, out_offsets): the caller's tensors instead of fresh ones."""
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = data.device
+        if offsets is not None:
+            if (not _is_torch(offsets) or offsets.dtype not in (torch.int64, torch.uint64)
+                    or not offsets.is_cuda or not offsets.is_contiguous()):
+                raise RedExceptApi("device offsets must be a contiguous int64 CUDA tensor")
+            n = offsets.numel() - 1
+            stride = int(stride or 0)  # with offsets: trailing bytes to drop per line
+        elif n is None:
+            n = data.numel() // stride if stride else 0
+        if out is not None:
+            if (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
+                    not out.is_contiguous() or out.device != dev):
+                raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the data's device")
+            out_cap = out.numel() if out_cap is None else int(out_cap)
+            if not 0 <= out_cap <= out.numel():
+                raise RedExceptApi("out_cap runs past the out tensor")
+        elif out_cap:
+            raise RedExceptApi("out_cap goes with out=")
+        if sizes is None:
+            counts = torch.empty(n, dtype=torch.int64, device=dev)
+            ooff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        else:
+            counts, ooff = sizes
+            for t, room in ((counts, n), (ooff, n + 1)):
+                if (not _is_torch(t) or t.device != dev or not t.is_contiguous() or
+                        t.element_size() != 8 or t.numel() < room):
+                    raise RedExceptApi("sizes tensors must be contiguous, on the data's device and "
+                                       "hold n counts / n + 1 offsets")
+        r = np.frombuffer(bytes(repl), dtype=np.uint8)
+        drepl = torch.from_numpy(r.copy()).to(dev) if r.size else None
+        _check(_lib.lib().redgpu_replace_batch_dev(
+            exe._h, int(style), 1 if do_leader else 0, data.data_ptr() if data.numel() else None,
+            offsets.data_ptr() if offsets is not None else None, stride, n,
+            drepl.data_ptr() if drepl is not None else None, r.size, int(max_count),
+            counts.data_ptr(), ooff.data_ptr(), out.data_ptr() if out is not None else None,
+            out_cap if out is not None else 0, torch.cuda.current_stream(dev).cuda_stream))
+        return counts, ooff, out
+    if out is not None or out_cap is not None or sizes is not None:
+        raise RedExceptApi("out=, out_cap= and sizes= go with CUDA tensor input")
     a = _host_u8(data)
     if offsets is not None:
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)

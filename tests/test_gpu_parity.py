@@ -977,7 +977,8 @@ def test_replace_on_gpu():
     (test/matcher.cpp:648-691, every format) and its outputs in tests/golden/replace_vectors.npz
     (counts, lengths, FNV-1a-64 per rewritten line; one set byte for byte), every style x
     doLeader, three (replacement, max) cases, LDS and global table placements; the
-    delimiter-trimmed ragged form; output capacity too small."""
+    delimiter-trimmed ragged form.  An output capacity too small:
+    test_gpu_list_verbs.test_replace_batch_output_truncated."""
     import json
     import os
     from golden_util import GOLD
@@ -1671,7 +1672,7 @@ def test_stateful_matcher_on_gpu():
     assert np.array_equal(res3.cpu().numpy(), exp3)
 
 
-@pytest.mark.parametrize("mode", ["general", "hot", "cls", "long"])
+@pytest.mark.parametrize("mode", ["general", "hot", "cls", "long", "lists", "blocks"])
 def test_differential_fuzz_smoke(mode):
     """scripts/fuzz_gpu.py (random DFAs x line shapes x verbs x styles x placement / kernel flags
     vs the oracle), a short fixed-seed run of each bias; the open-ended campaign is run by hand."""
