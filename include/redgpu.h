@@ -534,6 +534,45 @@ int redgpu_grep_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int in
                          uint64_t *begin, uint64_t *finish, int32_t *result, uint64_t *start,
                          uint64_t *end, void *stream);
 
+/* grep -o: raw text in, every match of every line out - Red::collect (lib/Red.cpp:103-116) inside
+ * the line loop of tools/skim_red.cpp:36-46, over the lines lib/Util.cpp:109-130 cuts.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter are not a line (a match in them is not reported).
+ *  - The records are, for line k = 0, 1, ... in order, the Outcomes of Red::collect on that line
+ *    alone, in order: repeated search<styLast,false> (include/Matcher.h:557-640) from the end of
+ *    the previous match - exactly what redgpu_collect_batch gives for that line with an unbounded
+ *    cap.  Record j is line[j] = k, begin[j] = the offset in data of the line's first byte,
+ *    result[j], start[j], end[j].  start and end are ABSOLUTE offsets in data
+ *    (redgpu_collect_long's convention: the two verbs return the same record shape);
+ *    start[j] - begin[j] is the position in the line.
+ *  - *n_matches = the records FOUND over all lines; it may exceed cap, and then only the first
+ *    cap records are stored - slots from min(*n_matches, cap) on are not written.  The cap cuts
+ *    the global list, never a line's.  *n_lines = delimiters found.
+ *  - line, begin, result, start, end and n_lines may be NULL, each on its own; all five arrays
+ *    NULL, or cap == 0, gives the counts only, and then no line is walked a second time.
+ *  - REDGPU_EAPI for a NULL handle, a NULL n_matches or a NULL data with len > 0 (the two
+ *    argument checks run before the handle's device is looked at) and for a REDGPU_DEVICE_NONE
+ *    handle; REDGPU_ELIMIT for a text redgpu_split_lines refuses.  In every error case
+ *    *n_matches is untouched.
+ *  - An empty text, or one without a delimiter: *n_lines = 0 and *n_matches = 0 (the _dev form
+ *    writes them on the stream).
+ *  - The records of the lines that END in one aligned 16 MiB of the text are counted in 32 bits
+ *    (as the split counts its delimiters): only lines of gigabytes can hold more.
+ * redgpu_last_kernel() says "k_collect_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - no count is read
+ * back, and no per-line array is needed from the caller or in scratch (the lines are driven from
+ * the split's delimiter bitmap; scratch is what redgpu_grep_text_dev takes, len / 4 + 32 bytes
+ * per 16 KiB of text, from the thread's pool).
+ * redgpu_collect_text: host buffers - one upload of the text, then n_lines, n_matches and the
+ * filled prefixes back. */
+int redgpu_collect_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                        uint64_t cap, uint64_t *n_lines, uint64_t *n_matches, uint64_t *line,
+                        uint64_t *begin, int32_t *result, uint64_t *start, uint64_t *end);
+int redgpu_collect_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                            uint64_t cap, uint64_t *n_lines, uint64_t *n_matches, uint64_t *line,
+                            uint64_t *begin, int32_t *result, uint64_t *start, uint64_t *end,
+                            void *stream);
+
 /* Measurement aid, no counterpart in the reference: one streaming read of `bytes` of device
  * memory (16-byte aligned) on the handle's device, asynchronous on `stream` - the read-bandwidth
  * calibration bench.py reports beside the roofline.  `sink` is a device uint32 the kernel may

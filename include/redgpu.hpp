@@ -231,6 +231,47 @@ inline size_t grepCount(const Executable &exec, std::string_view text, Style sty
   return size_t(found);
 }
 
+// grep -o (Red::collect, lib/Red.cpp:103-116, inside tools/skim_red.cpp:36-46's line loop): every
+// match of every line of a text blob, in text order, at most cap of them.  line_ = the line's
+// 0-based index, begin_ = where it begins in `text`, outcome_ = the match with start_ / end_ as
+// offsets in `text` (collectLong's convention; start_ - begin_ is the position in the line).
+struct TextMatch {
+  size_t line_, begin_;
+  Outcome outcome_;
+};
+
+// room for text.size() / 64 + 16 records first, one retry with the exact count
+inline std::vector<TextMatch> collectText(const Executable &exec, std::string_view text,
+                                          char delim = '\n', size_t cap = SIZE_MAX) {
+  const Byte *p = reinterpret_cast<const Byte *>(text.data());
+  uint64_t room = text.size() / 64 + 16, found = 0;
+  if (room > cap) room = cap;
+  std::vector<uint64_t> ln, bg, s, e;
+  std::vector<Result> r;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    ln.resize(room); bg.resize(room); s.resize(room); e.resize(room); r.resize(room);
+    throwOnError(redgpu_collect_text(exec.handle(), p, text.size(), Byte(delim), room, nullptr,
+                                     &found, ln.data(), bg.data(), r.data(), s.data(), e.data()));
+    if (found <= room || room == cap) break;
+    room = found < cap ? found : cap;
+  }
+  std::vector<TextMatch> out(found < room ? found : room);
+  for (size_t i = 0; i < out.size(); ++i)
+    out[i] = TextMatch{size_t(ln[i]), size_t(bg[i]), Outcome{r[i], size_t(s[i]), size_t(e[i])}};
+  return out;
+}
+
+// the counts alone, no records: the matches of all lines; lines (optional) = delimiters found
+inline size_t collectTextCount(const Executable &exec, std::string_view text, char delim = '\n',
+                               size_t *lines = nullptr) {
+  uint64_t found = 0, nLines = 0;
+  throwOnError(redgpu_collect_text(exec.handle(), reinterpret_cast<const Byte *>(text.data()),
+                                   text.size(), Byte(delim), 0, &nLines, &found, nullptr, nullptr,
+                                   nullptr, nullptr, nullptr));
+  if (lines) *lines = size_t(nLines);
+  return size_t(found);
+}
+
 // ---- several GPUs of one node: one image per device, contiguous shards, results in the caller's
 // arrays - the device form of tools/thr_red.cpp:84-91 (N workers over one shared Red).  devices
 // may name a device more than once (the shards then share it). ----------------------------------

@@ -181,6 +181,11 @@ def lib() -> C.CDLL:
         l.redgpu_grep_text_dev.restype = C.c_int
         l.redgpu_grep_text_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, u64, C.c_uint8, u64,
                                            u64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        l.redgpu_collect_text.restype = C.c_int
+        l.redgpu_collect_text.argtypes = [vp, vp, u64, C.c_uint8, u64, vp, vp, vp, vp, vp, vp, vp]
+        l.redgpu_collect_text_dev.restype = C.c_int
+        l.redgpu_collect_text_dev.argtypes = [vp, vp, u64, C.c_uint8, u64, vp, vp, vp, vp, vp, vp,
+                                              vp, vp]
         l.redgpu_diag_read_dev.restype = C.c_int
         l.redgpu_diag_read_dev.argtypes = [vp, vp, u64, vp, vp]
         l.redgpu_diag_lds_dev.restype = C.c_int

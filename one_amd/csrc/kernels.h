@@ -205,6 +205,18 @@ hipError_t launchGrepText(const DevDfa &dfa, int style, int doLeader, int invert
                           void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                           const char **kernelName);
 
+// grep -o over a raw text (k_collect_text.h): Red::collect over every line of launchSplitLines' rule,
+// the records in text order: *nMatches = records found, the first min(*nMatches, cap) of them in
+// line / begin / result / start / end (each may be null, nLines too; start and end are offsets in
+// data).  scratch: collectTextScratchBytes(len) bytes of device memory, 16-byte aligned.
+// *kernelName = "k_collect_text".
+uint64_t collectTextScratchBytes(uint64_t len);
+hipError_t launchCollectText(const DevDfa &dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                             uint64_t cap, uint64_t *nLines, uint64_t *nMatches, uint64_t *line,
+                             uint64_t *begin, int32_t *result, uint64_t *start, uint64_t *end,
+                             void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                             const char **kernelName);
+
 // bench.py's read-bandwidth calibration: one streaming pass over `bytes` (16-byte aligned).
 hipError_t launchDiagRead(const void *data, uint64_t bytes, uint32_t *sink, int numCUs,
                           hipStream_t stream);

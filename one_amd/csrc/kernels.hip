@@ -40,6 +40,8 @@
 //   k_split.h         line splitting on the device
 //   k_grep.h          k_gp_*: grep over a raw text - the split's delimiter bitmap drives the lines,
 //                     a wave per 16 KiB chunk selects, a scan orders, a second pass writes records
+//   k_collect_text.h  k_ct_*: grep -o over a raw text - k_grep.h's line driver, Red::collect per line,
+//                     a count pass, a scan, and a write pass that puts record j at slot j
 //   k_diag.h          bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
@@ -52,11 +54,11 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled four times in parallel (Makefile: -DREDGPU_TU=1/2/3/4): the templates are
+// This file is compiled five times in parallel (Makefile: -DREDGPU_TU=1/2/3/4/5): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
-// 3 = everything else and the dispatch, 4 = k_grep.  REDGPU_TU undefined or 0 = all of it in one
-// unit.
+// 3 = everything else and the dispatch, 4 = k_grep, 5 = k_collect_text.  REDGPU_TU undefined or
+// 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
 #endif
@@ -64,6 +66,7 @@
 #define REDGPU_TU_RAGGED (REDGPU_TU == 0 || REDGPU_TU == 2)
 #define REDGPU_TU_GENERIC (REDGPU_TU == 0 || REDGPU_TU == 3)
 #define REDGPU_TU_GREP (REDGPU_TU == 0 || REDGPU_TU == 4)
+#define REDGPU_TU_COLLECT_TEXT (REDGPU_TU == 0 || REDGPU_TU == 5)
 
 namespace redgpu {
 
@@ -90,6 +93,7 @@ namespace {
 #include "k_diag.h"
 #include "launchers.h"
 #include "k_grep.h"
+#include "k_collect_text.h"
 
 } // namespace
 
@@ -970,6 +974,68 @@ hipError_t launchGrepText(const DevDfa &d, int style, int doLeader, int invert, 
 #undef GP_ARGS
 }
 #endif  // REDGPU_TU_GREP
+
+#if REDGPU_TU_COLLECT_TEXT
+// grep -o over a raw text (k_collect_text.h): the split's count and scan and grep's k_gp_last /
+// k_gp_open as they stand, then the k_ct_* passes.  scratch: collectTextScratchBytes(len) bytes,
+// 16-byte aligned - what grep takes: two bitmaps and 32 bytes per chunk.
+uint64_t collectTextScratchBytes(uint64_t len) {
+  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
+  return nChunks * 32 + 32 + 2 * nChunks * (kSplitChunk / 8);
+}
+
+hipError_t launchCollectText(const DevDfa &d, const uint8_t *data, uint64_t len, uint8_t delim,
+                             uint64_t cap, uint64_t *nLines, uint64_t *nMatches, uint64_t *line,
+                             uint64_t *begin, int32_t *result, uint64_t *start, uint64_t *end,
+                             void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                             const char **kernelName) {
+  *kernelName = "k_collect_text";
+  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
+  // [bases, open, matchBases: u64[nChunks] each][counts, matchCounts: u32[nChunks] each]
+  // [lines, dummy: u64, 16 spare][delimiter bitmap][hit bitmap]
+  uint8_t *q = static_cast<uint8_t *>(scratch);
+  uint64_t *bases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint64_t *open = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint64_t *matchBases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint32_t *counts = reinterpret_cast<uint32_t *>(q); q += nChunks * 4;
+  uint32_t *matchCounts = reinterpret_cast<uint32_t *>(q); q += nChunks * 4;
+  uint64_t *misc = reinterpret_cast<uint64_t *>(q); q += 32;
+  uint16_t *masks = reinterpret_cast<uint16_t *>(q); q += nChunks * (kSplitChunk / 8);
+  uint16_t *hitMasks = reinterpret_cast<uint16_t *>(q);
+  uint64_t *dummy = misc + 1;
+  if (nChunks) {
+    hipLaunchKernelGGL(k_split_count, dim3(uint32_t(nChunks)), dim3(kSplitThreads), 0, stream, data,
+                       len, uint32_t(delim), nChunks, counts, masks);
+  }
+  // (k_split_scan's offsets[0] store goes to a spare word)
+  hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, counts, nChunks, bases,
+                     nLines ? nLines : misc, dummy, uint64_t(0));
+  if (nChunks) {
+    uint64_t small = (nChunks + 3) / 4;
+    if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
+    hipLaunchKernelGGL(k_gp_last, dim3(uint32_t(small)), dim3(256), 0, stream, masks, counts,
+                       nChunks, open, hitMasks);
+    hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, open, nChunks);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const GpBufs b{masks, hitMasks, bases, open, matchCounts, matchBases, nChunks};
+  const CtOut out{cap, line, begin, result, start, end};
+  const bool write = cap > 0 && (line || begin || result || start || end);
+#define CT_CALL(K) \
+  launchCollectTextK<K>(d, data, b, out, write, nMatches, matchBases, dummy, cfg, stream)
+  switch (d.tableKind) {
+  case REDGPU_TAB_LDS_FUSED_U8: return CT_CALL(REDGPU_TAB_LDS_FUSED_U8);
+  case REDGPU_TAB_LDS_FUSED_U16: return CT_CALL(REDGPU_TAB_LDS_FUSED_U16);
+  case REDGPU_TAB_LDS_CLASS_U16: return CT_CALL(REDGPU_TAB_LDS_CLASS_U16);
+  case REDGPU_TAB_GLOBAL_U16: return CT_CALL(REDGPU_TAB_GLOBAL_U16);
+  case REDGPU_TAB_HOT_ROWS: return CT_CALL(REDGPU_TAB_HOT_ROWS);
+  case REDGPU_TAB_LDS_SPARSE: return CT_CALL(REDGPU_TAB_LDS_SPARSE);
+  default: return CT_CALL(REDGPU_TAB_GLOBAL_U32);
+  }
+#undef CT_CALL
+}
+#endif  // REDGPU_TU_COLLECT_TEXT
 
 #if REDGPU_TU_GENERIC
 hipError_t launchBatches(const DevDfa &d, const Batch *bs, uint32_t nb, int verb, int style,

@@ -1237,6 +1237,73 @@ int redgpu_grep_text(const redgpu_dfa *dfa, int style, int do_leader, int invert
   return call.wait();
 }
 
+// the arguments of both collect_text forms: what can be refused without a device first
+static int checkCollectText(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
+                            const uint64_t *nMatches) {
+  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
+  if (!nMatches) return fail(REDGPU_EAPI, "null n_matches buffer");
+  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
+  if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
+  return checkHandle(dfa);
+}
+
+// raw text -> every match of every line, as records in text order (k_collect_text.h): everything
+// on `stream`, no count read back
+int redgpu_collect_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                            uint64_t cap, uint64_t *n_lines, uint64_t *n_matches, uint64_t *line,
+                            uint64_t *begin, int32_t *result, uint64_t *start, uint64_t *end,
+                            void *stream) {
+  if (int rc = checkCollectText(dfa, data, len, n_matches)) return rc;
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // ONE allocation for the call, carved up by launchCollectText
+  void *scratch = nullptr;
+  HIP_TRY(scratchFor(s, size_t(collectTextScratchBytes(len)), &scratch), "hipMalloc scratch");
+  const LaunchCfg cfg = cfgOf(dfa);
+  const char *name = "";
+  const hipError_t e = launchCollectText(dfa->im->dev, data, len, delim, cap, n_lines, n_matches,
+                                         line, begin, result, start, end, scratch, cfg, s, &name);
+  tlsKernel = name;
+  if (e != hipSuccess) return failHip(e, "kernel launch");
+  return REDGPU_OK;
+}
+
+// host-buffer form: one upload of the text, then the two counts and the filled prefixes back
+int redgpu_collect_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                        uint64_t cap, uint64_t *n_lines, uint64_t *n_matches, uint64_t *line,
+                        uint64_t *begin, int32_t *result, uint64_t *start, uint64_t *end) {
+  if (int rc = checkCollectText(dfa, data, len, n_matches)) return rc;
+  if (cap > len) cap = len;  // a match has a byte of its own: no more records than bytes
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dN = call.buf<uint64_t>(kSlAux0, 2, "counts");
+  uint64_t *dLine = line && cap ? call.buf<uint64_t>(kSlOff, cap, "line") : nullptr;
+  uint64_t *dBegin = begin && cap ? call.buf<uint64_t>(kSlAux1, cap, "begin") : nullptr;
+  int32_t *dRes = result && cap ? call.buf<int32_t>(kSlRes, cap, "result") : nullptr;
+  uint64_t *dStart = start && cap ? call.buf<uint64_t>(kSlStart, cap, "start") : nullptr;
+  uint64_t *dEnd = end && cap ? call.buf<uint64_t>(kSlEnd, cap, "end") : nullptr;
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return redgpu_collect_text_dev(dfa, dData, len, delim, cap, dN, dN + 1, dLine, dBegin, dRes,
+                                   dStart, dEnd, call.stream());
+  });
+  uint64_t counts[2] = {0, 0};
+  call.download(counts, dN, 2, "counts");
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = counts[0];
+  *n_matches = counts[1];
+  const uint64_t got = counts[1] < cap ? counts[1] : cap;
+  if (got) {
+    if (dLine) call.download(line, dLine, got, "line");
+    if (dBegin) call.download(begin, dBegin, got, "begin");
+    if (dRes) call.download(result, dRes, got, "result");
+    if (dStart) call.download(start, dStart, got, "start");
+    if (dEnd) call.download(end, dEnd, got, "end");
+  }
+  return call.wait();
+}
+
 int redgpu_split_lines(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                        uint64_t *offsets, uint64_t cap, uint64_t *n_lines) {
   if (int rc = checkHandle(dfa)) return rc;

@@ -1031,6 +1031,65 @@ def grep_text(exe, data, style=styInstant, do_leader=True, *, invert=False, deli
     return (int(nl.value), int(ns.value), ln[:k], bg[:k], fn[:k], cut(res), cut(st), cut(en))
 
 
+def collect_text(exe, data, *, delim=b"\n", cap=None, want_positions=True):
+    """redgpu_collect_text[_dev]: grep -o - every match of every delimiter-terminated line of a raw
+    text buffer, as compact records in text order: Red::collect (lib/Red.cpp:103-116) inside
+    tools/skim_red.cpp:36-46's line loop.  Record j: line[j] = the line's 0-based index, begin[j] =
+    the offset of its first byte, result[j], and start[j] / end[j] as ABSOLUTE offsets in the text
+    (collect_long's convention; start[j] - begin[j] is the position in the line).  n_matches is the
+    number of records found and may exceed cap: the cap cuts the whole list, never a line's.
+    Host input -> (n_lines, n_matches, line, begin, result, start, end): numpy arrays trimmed to
+    min(n_matches, cap); cap=None sizes them with a counting call first (the text is then uploaded
+    twice - pass a cap to avoid that - unless nothing matches); cap=0 only counts.
+    want_positions=False leaves start / end None.
+    A CUDA uint8 tensor needs cap -> the same tuple as device tensors, n_lines and n_matches as
+    1-element int64 tensors, asynchronously on the current stream and without any read-back;
+    entries from min(n_matches, cap) on are untouched."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        if cap is None:
+            raise RedExceptApi("device collect_text needs cap (room in the output tensors)")
+        dev = data.device
+        cnt = torch.empty(2, dtype=torch.int64, device=dev)
+        ln, bg = (torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(2))
+        res = torch.empty(cap, dtype=torch.int32, device=dev)
+        st = torch.empty(cap, dtype=torch.int64, device=dev) if want_positions else None
+        en = torch.empty(cap, dtype=torch.int64, device=dev) if want_positions else None
+        _check(l.redgpu_collect_text_dev(
+            exe._h, data.data_ptr() if data.numel() else None, data.numel(), d, cap,
+            cnt.data_ptr(), cnt.data_ptr() + 8, ln.data_ptr(), bg.data_ptr(), res.data_ptr(),
+            st.data_ptr() if want_positions else None, en.data_ptr() if want_positions else None,
+            torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], ln, bg, res, st, en
+    a = _host_u8(data)
+    dp = a.ctypes.data if a.size else None
+    nl, nm = C.c_uint64(0), C.c_uint64(0)
+    if cap is None:
+        _check(l.redgpu_collect_text(exe._h, dp, a.size, d, 0, C.byref(nl), C.byref(nm), None, None,
+                                     None, None, None))
+        cap = int(nm.value)
+        if cap == 0:  # nothing matches: the counting call said it all
+            pos = lambda: np.zeros(0, dtype=np.uint64) if want_positions else None  # noqa: E731
+            u = np.zeros(0, dtype=np.uint64)
+            return int(nl.value), 0, u, u.copy(), np.zeros(0, dtype=np.int32), pos(), pos()
+    cap = int(cap)
+    ln, bg = (np.zeros(cap, dtype=np.uint64) for _ in range(2))
+    res = np.zeros(cap, dtype=np.int32)
+    st = np.zeros(cap, dtype=np.uint64) if want_positions else None
+    en = np.zeros(cap, dtype=np.uint64) if want_positions else None
+    _check(l.redgpu_collect_text(
+        exe._h, dp, a.size, d, cap, C.byref(nl), C.byref(nm), ln.ctypes.data, bg.ctypes.data,
+        res.ctypes.data, st.ctypes.data if want_positions else None,
+        en.ctypes.data if want_positions else None))
+    k = min(int(nm.value), cap)
+    cut = lambda x: x[:k] if x is not None else None  # noqa: E731
+    return int(nl.value), int(nm.value), ln[:k], bg[:k], res[:k], cut(st), cut(en)
+
+
 class StatefulMatcher:
     """Mirror of zezax::red::StatefulMatcher (include/Matcher.h:770-792): `advance(byte)` and
     `result()`; `advance_bytes` feeds a whole chunk in one kernel launch.  The executable must
