@@ -573,6 +573,54 @@ int redgpu_collect_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t
                             uint64_t *begin, int32_t *result, uint64_t *start, uint64_t *end,
                             void *stream);
 
+/* sed: raw text in, the text with every line rewritten out - replace<style,doLeader>
+ * (include/Matcher.h:186-191, core :643-706; what Red's replaceOne* / replaceAll* and
+ * Red::replace / Red::globalReplace, include/Red.h:139-251, end in) inside the line loop of
+ * tools/skim_red.cpp:36-46, over the lines lib/Util.cpp:109-130 cuts.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter (the tail) are not a line.
+ *  - only_changed == 0: the output is, for line k = 0, 1, ... in order,
+ *    replace<style,do_leader>(line k, repl, max_count) followed by the delimiter, and behind the
+ *    last line the tail, copied unchanged: the tail is never rewritten.  A line's rewritten bytes
+ *    are exactly what redgpu_replace_batch gives for that line.
+ *  - max_count is PER LINE: 1 is sed s/x/y/, 1 << 62 is s/x/y/g, 0 copies the text.
+ *  - only_changed != 0 (sed -n 's/x/y/p'): only the lines with at least one replacement are
+ *    emitted, each rewritten and followed by its delimiter; the tail is dropped.
+ *  - *n_replaced = the sum of the per-line return values of replace; *out_len = the length of the
+ *    whole output, whatever out_cap is; *n_lines = delimiters found.  n_lines and n_replaced may
+ *    be NULL, each on its own; out_len is required.
+ *  - out == NULL or out_cap == 0 gives the sizes only, and no line is walked a second time.
+ *    Otherwise exactly the first min(*out_len, out_cap) bytes of the output are written - the cut
+ *    may fall inside a line or inside a replacement - and bytes of out from there on are NOT
+ *    written (redgpu_collect_text's rule, not redgpu_replace_long's): out may be the middle of a
+ *    larger buffer.  out must not overlap data.  repl may be NULL when repl_len == 0.
+ *  - REDGPU_EAPI for a NULL handle, a NULL out_len, a NULL data with len > 0, a NULL repl with
+ *    repl_len > 0 (the argument checks run before the handle's device is looked at) and for a
+ *    REDGPU_DEVICE_NONE handle; REDGPU_EEXEC for a style that does not exist; REDGPU_ELIMIT for a
+ *    text redgpu_split_lines refuses.  In every error case the three counts are untouched.
+ *  - An empty text, or one without a delimiter: *n_lines = 0, *n_replaced = 0, *out_len = len (0
+ *    under only_changed), and the text is copied when out is given (the _dev form writes the
+ *    counts on the stream).
+ *  - A single line of megabytes is walked by one lane, and an unchanged stretch of megabytes that
+ *    ends in one 16 KiB chunk is copied by one wave: correct, and slow.
+ * redgpu_last_kernel() says "k_replace_text": there is no other route.
+ * _dev: every pointer device memory, repl too; asynchronous on `stream` from end to end - nothing
+ * is read back, and no per-line array is needed from the caller or in scratch (the lines are
+ * driven from the split's delimiter bitmap; scratch is the two bitmaps and a few words per 16 KiB
+ * chunk: len / 4 + 44 bytes per chunk + 8 bytes per 1,024 chunks + 72, rounded up to 16, from
+ * the thread's pool).
+ * redgpu_replace_text: host buffers, as redgpu_replace_long - one upload of the text, a sizes
+ * pass, a device output sized from *out_len, and min(*out_len, out_cap) bytes downloaded. */
+int redgpu_replace_text(const redgpu_dfa *dfa, int style, int do_leader, int only_changed,
+                        const uint8_t *data, uint64_t len, uint8_t delim, const uint8_t *repl,
+                        uint64_t repl_len, uint64_t max_count, uint64_t *n_lines,
+                        uint64_t *n_replaced, uint64_t *out_len, uint8_t *out, uint64_t out_cap);
+int redgpu_replace_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int only_changed,
+                            const uint8_t *data, uint64_t len, uint8_t delim, const uint8_t *repl,
+                            uint64_t repl_len, uint64_t max_count, uint64_t *n_lines,
+                            uint64_t *n_replaced, uint64_t *out_len, uint8_t *out, uint64_t out_cap,
+                            void *stream);
+
 /* Measurement aid, no counterpart in the reference: one streaming read of `bytes` of device
  * memory (16-byte aligned) on the handle's device, asynchronous on `stream` - the read-bandwidth
  * calibration bench.py reports beside the roofline.  `sink` is a device uint32 the kernel may

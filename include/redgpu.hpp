@@ -272,6 +272,29 @@ inline size_t collectTextCount(const Executable &exec, std::string_view text, ch
   return size_t(found);
 }
 
+// sed (replace<style,doLeader>, include/Matcher.h:186-191, inside tools/skim_red.cpp:36-46's line
+// loop): every line of a text blob rewritten and the text put back together in `out` - the lines,
+// their delimiters, and the tail behind the last delimiter unchanged.  max is per line (1 = sed
+// s/x/y/, SIZE_MAX = s/x/y/g); onlyChanged = sed -n 's/x/y/p': the changed lines alone, no tail.
+// Returns the replacements made.  `out` is sized from a first call that only sizes.
+inline size_t replaceText(const Executable &exec, Style style, bool doLeader,
+                          std::string_view text, std::string_view repl, std::string &out,
+                          size_t max = SIZE_MAX, bool onlyChanged = false, char delim = '\n') {
+  const Byte *p = reinterpret_cast<const Byte *>(text.data());
+  const Byte *r = reinterpret_cast<const Byte *>(repl.data());
+  const uint64_t most = max > (uint64_t(1) << 62) ? uint64_t(1) << 62 : uint64_t(max);
+  uint64_t made = 0, outLen = 0;
+  throwOnError(redgpu_replace_text(exec.handle(), style, doLeader, onlyChanged, p, text.size(),
+                                   Byte(delim), r, repl.size(), most, nullptr, &made, &outLen,
+                                   nullptr, 0));
+  out.resize(size_t(outLen));
+  if (outLen)
+    throwOnError(redgpu_replace_text(exec.handle(), style, doLeader, onlyChanged, p, text.size(),
+                                     Byte(delim), r, repl.size(), most, nullptr, &made, &outLen,
+                                     reinterpret_cast<Byte *>(out.data()), outLen));
+  return size_t(made);
+}
+
 // ---- several GPUs of one node: one image per device, contiguous shards, results in the caller's
 // arrays - the device form of tools/thr_red.cpp:84-91 (N workers over one shared Red).  devices
 // may name a device more than once (the shards then share it). ----------------------------------

@@ -53,15 +53,18 @@ k_advance(DevDfa d, Batch b, uint32_t *state) {
 
 // include/Matcher.h:643-706 replaceCore.  out == nullptr: only count and measure.
 // Returns the number of replacements; outLen = length of the rewritten line.
-template <class T>
-__device__ uint64_t replaceLane(const T &tab, const LaneCtx &c, const uint8_t *p, uint64_t n,
-                                int style, bool lead, const uint8_t *repl, uint64_t replLen,
-                                uint64_t max, uint8_t *out, uint64_t &outLen) {
+// kClamp: only out[0..room) is stored - the walk and outLen are those of the whole line
+// (k_replace_text.h: an output cut inside a line or inside a replacement).
+template <bool kClamp, class T>
+__device__ uint64_t replaceLaneT(const T &tab, const LaneCtx &c, const uint8_t *p, uint64_t n,
+                                 int style, bool lead, const uint8_t *repl, uint64_t replLen,
+                                 uint64_t max, uint8_t *out, uint64_t room, uint64_t &outLen) {
   uint64_t cnt = 0, w = 0, in = 0;
   while (in < n) {
     if (cnt >= max) {
       if (out)
-        for (uint64_t k = in; k < n; ++k) out[w + (k - in)] = p[k];
+        for (uint64_t k = in; k < n && (!kClamp || w + (k - in) < room); ++k)
+          out[w + (k - in)] = p[k];
       w += n - in;
       break;
     }
@@ -94,24 +97,32 @@ __device__ uint64_t replaceLane(const T &tab, const LaneCtx &c, const uint8_t *p
       // L = SIGMA* L: nothing matched on p[in..n), so nothing can at any later position (they read
       // suffixes of it) - the rest of the line is copied as the reference's loop would, byte by byte
       if (out)
-        for (uint64_t k = in; k < n; ++k) out[w + (k - in)] = p[k];
+        for (uint64_t k = in; k < n && (!kClamp || w + (k - in) < room); ++k)
+          out[w + (k - in)] = p[k];
       w += n - in;
       break;
     }
     if (found != ~0ull) {
       if (out)
-        for (uint64_t k = 0; k < replLen; ++k) out[w + k] = repl[k];
+        for (uint64_t k = 0; k < replLen && (!kClamp || w + k < room); ++k) out[w + k] = repl[k];
       w += replLen;
       in = found + 1;
       ++cnt;
     } else {
-      if (out) out[w] = p[in];
+      if (out && (!kClamp || w < room)) out[w] = p[in];
       ++w;
       ++in;
     }
   }
   outLen = w;
   return cnt;
+}
+
+template <class T>
+__device__ uint64_t replaceLane(const T &tab, const LaneCtx &c, const uint8_t *p, uint64_t n,
+                                int style, bool lead, const uint8_t *repl, uint64_t replLen,
+                                uint64_t max, uint8_t *out, uint64_t &outLen) {
+  return replaceLaneT<false>(tab, c, p, n, style, lead, repl, replLen, max, out, ~0ull, outLen);
 }
 
 // pass 1 (out == nullptr): counts[line], outLens[line].  pass 2: writes line i's rewritten

@@ -217,6 +217,22 @@ hipError_t launchCollectText(const DevDfa &dfa, const uint8_t *data, uint64_t le
                              void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                              const char **kernelName);
 
+// sed over a raw text (k_replace_text.h): replace<style, doLeader>(line, repl, max) over every line
+// of launchSplitLines' rule, the rewritten lines and their delimiters put back together (and the
+// tail behind them; under onlyChanged the changed lines alone, no tail): *outLen = the output's
+// length, *nReplaced = the replacements made, the first min(*outLen, outCap) bytes in out and
+// nothing behind them (out, nLines and nReplaced may be null; repl is device memory).  phases: 1 =
+// split, count and size, 2 = write out from what phase 1 left in scratch, 3 = both.  scratch:
+// replaceTextScratchBytes(len) bytes of device memory, 16-byte aligned.
+// *kernelName = "k_replace_text".
+uint64_t replaceTextScratchBytes(uint64_t len);
+hipError_t launchReplaceText(const DevDfa &dfa, int style, int doLeader, int onlyChanged,
+                             const uint8_t *data, uint64_t len, uint8_t delim, const uint8_t *repl,
+                             uint64_t replLen, uint64_t max, uint64_t *nLines, uint64_t *nReplaced,
+                             uint64_t *outLen, uint8_t *out, uint64_t outCap, int phases,
+                             void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                             const char **kernelName);
+
 // bench.py's read-bandwidth calibration: one streaming pass over `bytes` (16-byte aligned).
 hipError_t launchDiagRead(const void *data, uint64_t bytes, uint32_t *sink, int numCUs,
                           hipStream_t stream);

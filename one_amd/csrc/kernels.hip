@@ -42,6 +42,8 @@
 //                     a wave per 16 KiB chunk selects, a scan orders, a second pass writes records
 //   k_collect_text.h  k_ct_*: grep -o over a raw text - k_grep.h's line driver, Red::collect per line,
 //                     a count pass, a scan, and a write pass that puts record j at slot j
+//   k_replace_text.h  k_rt_*: sed over a raw text - the same line driver, replaceCore per line, a
+//                     sizing pass, a scan, and a write pass whose waves copy the unchanged bytes
 //   k_diag.h          bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
@@ -54,11 +56,11 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled five times in parallel (Makefile: -DREDGPU_TU=1/2/3/4/5): the templates are
+// This file is compiled six times in parallel (Makefile: -DREDGPU_TU=1/2/.../6): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
-// 3 = everything else and the dispatch, 4 = k_grep, 5 = k_collect_text.  REDGPU_TU undefined or
-// 0 = all of it in one unit.
+// 3 = everything else and the dispatch, 4 = k_grep, 5 = k_collect_text, 6 = k_replace_text.
+// REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
 #endif
@@ -67,6 +69,7 @@
 #define REDGPU_TU_GENERIC (REDGPU_TU == 0 || REDGPU_TU == 3)
 #define REDGPU_TU_GREP (REDGPU_TU == 0 || REDGPU_TU == 4)
 #define REDGPU_TU_COLLECT_TEXT (REDGPU_TU == 0 || REDGPU_TU == 5)
+#define REDGPU_TU_REPLACE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 6)
 
 namespace redgpu {
 
@@ -94,6 +97,7 @@ namespace {
 #include "launchers.h"
 #include "k_grep.h"
 #include "k_collect_text.h"
+#include "k_replace_text.h"
 
 } // namespace
 
@@ -1036,6 +1040,101 @@ hipError_t launchCollectText(const DevDfa &d, const uint8_t *data, uint64_t len,
 #undef CT_CALL
 }
 #endif  // REDGPU_TU_COLLECT_TEXT
+
+#if REDGPU_TU_REPLACE_TEXT
+// sed over a raw text (k_replace_text.h): the split's count and scan and grep's k_gp_last /
+// k_gp_open as they stand, then the k_rt_* passes around k_misc.h's 64-bit scan.  scratch:
+// replaceTextScratchBytes(len) bytes, 16-byte aligned: the two bitmaps, and 44 bytes per chunk, 8 per
+// 1,024 chunks and 72, rounded up to 16.
+uint64_t replaceTextScratchBytes(uint64_t len) {
+  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
+  const uint64_t nPart = (nChunks + 1023) / 1024;
+  const uint64_t head = (5 * nChunks + 1 + nPart + 8) * 8 + nChunks * 4;
+  return ((head + 15) & ~uint64_t(15)) + 2 * nChunks * (kSplitChunk / 8);
+}
+
+hipError_t launchReplaceText(const DevDfa &d, int style, int doLeader, int onlyChanged,
+                             const uint8_t *data, uint64_t len, uint8_t delim, const uint8_t *repl,
+                             uint64_t replLen, uint64_t max, uint64_t *nLines, uint64_t *nReplaced,
+                             uint64_t *outLen, uint8_t *out, uint64_t outCap, int phases,
+                             void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                             const char **kernelName) {
+  *kernelName = "k_replace_text";
+  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
+  const uint64_t nPart = (nChunks + 1023) / 1024;
+  // [bases, open, outBytes, replCounts: u64[nChunks] each][outBases: u64[nChunks + 1]]
+  // [partials: u64[nPart]][lines, dummy, replaced, tailAt[2]: u64, 24 spare][counts: u32[nChunks]]
+  // [pad to 16][delimiter bitmap][hit bitmap]
+  uint8_t *q = static_cast<uint8_t *>(scratch);
+  uint64_t *bases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint64_t *open = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint64_t *outBytes = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint64_t *replCounts = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint64_t *outBases = reinterpret_cast<uint64_t *>(q); q += (nChunks + 1) * 8;
+  uint64_t *partials = reinterpret_cast<uint64_t *>(q); q += nPart * 8;
+  uint64_t *misc = reinterpret_cast<uint64_t *>(q); q += 64;
+  uint32_t *counts = reinterpret_cast<uint32_t *>(q); q += nChunks * 4;
+  q = static_cast<uint8_t *>(scratch) + ((uint64_t(q - static_cast<uint8_t *>(scratch)) + 15) & ~uint64_t(15));
+  uint16_t *masks = reinterpret_cast<uint16_t *>(q); q += nChunks * (kSplitChunk / 8);
+  uint16_t *hitMasks = reinterpret_cast<uint16_t *>(q);
+  uint64_t *dummy = misc + 1, *tailAt = misc + 3;
+  const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
+  const GpBufs b{masks, hitMasks, bases, open, nullptr, nullptr, nChunks};
+  const RtBufs r{outBytes, replCounts, outBases};
+  const RtArgs a{style, lead, onlyChanged, uint32_t(delim), repl, replLen, max};
+#define RT_CALL(K) launchReplaceTextK<K>(d, data, b, r, a, count, out, outCap, cfg, stream)
+  auto pass = [&](bool count) {
+    switch (d.tableKind) {
+    case REDGPU_TAB_LDS_FUSED_U8: return RT_CALL(REDGPU_TAB_LDS_FUSED_U8);
+    case REDGPU_TAB_LDS_FUSED_U16: return RT_CALL(REDGPU_TAB_LDS_FUSED_U16);
+    case REDGPU_TAB_LDS_CLASS_U16: return RT_CALL(REDGPU_TAB_LDS_CLASS_U16);
+    case REDGPU_TAB_GLOBAL_U16: return RT_CALL(REDGPU_TAB_GLOBAL_U16);
+    case REDGPU_TAB_HOT_ROWS: return RT_CALL(REDGPU_TAB_HOT_ROWS);
+    case REDGPU_TAB_LDS_SPARSE: return RT_CALL(REDGPU_TAB_LDS_SPARSE);
+    default: return RT_CALL(REDGPU_TAB_GLOBAL_U32);
+    }
+  };
+#undef RT_CALL
+  if (phases & 1) {
+    if (nChunks) {
+      hipLaunchKernelGGL(k_split_count, dim3(uint32_t(nChunks)), dim3(kSplitThreads), 0, stream,
+                         data, len, uint32_t(delim), nChunks, counts, masks);
+    }
+    // (k_split_scan's offsets[0] store goes to a spare word)
+    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, counts, nChunks, bases,
+                       nLines ? nLines : misc, dummy, uint64_t(0));
+    if (nChunks) {
+      uint64_t small = (nChunks + 3) / 4;
+      if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
+      hipLaunchKernelGGL(k_gp_last, dim3(uint32_t(small)), dim3(256), 0, stream, masks, counts,
+                         nChunks, open, hitMasks);
+      hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, open, nChunks);
+      hipError_t e = hipGetLastError();
+      if (e == hipSuccess) e = pass(true);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(nPart)), dim3(256), 0, stream, outBytes,
+                         nChunks, partials);
+      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, partials, nPart);
+      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(nPart)), dim3(256), 0, stream, outBytes,
+                         nChunks, partials, outBases);
+    }
+    hipLaunchKernelGGL(k_rt_totals, dim3(1), dim3(1024), 0, stream, replCounts, nChunks,
+                       nChunks ? outBases + nChunks : nullptr, masks, open, len, onlyChanged,
+                       tailAt, outLen, nReplaced ? nReplaced : misc + 2);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if ((phases & 2) && out && outCap && nChunks) {
+    const hipError_t e = pass(false);
+    if (e != hipSuccess) return e;
+    if (!onlyChanged) {
+      hipLaunchKernelGGL(k_rt_tail, dim3(uint32_t(cfg.numCUs) * 4), dim3(256), 0, stream, data, len,
+                         tailAt, out, outCap);
+    }
+  }
+  return hipGetLastError();
+}
+#endif  // REDGPU_TU_REPLACE_TEXT
 
 #if REDGPU_TU_GENERIC
 hipError_t launchBatches(const DevDfa &d, const Batch *bs, uint32_t nb, int verb, int style,

@@ -1304,6 +1304,88 @@ int redgpu_collect_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len
   return call.wait();
 }
 
+// the arguments of both replace_text forms: what can be refused without a device first
+static int checkReplaceText(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
+                            const uint8_t *repl, uint64_t replLen, const uint64_t *outLen) {
+  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
+  if (!outLen) return fail(REDGPU_EAPI, "null out_len buffer");
+  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
+  if (replLen && !repl) return fail(REDGPU_EAPI, "null replacement");
+  if (int rc = checkStyle(style)) return rc;
+  if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
+  return checkHandle(dfa);
+}
+
+// raw text -> every line rewritten, the text put back together (k_replace_text.h): everything on
+// `stream`, nothing read back; phases as launchReplaceText's
+static int replaceTextDev(const redgpu_dfa *dfa, int style, int doLeader, int onlyChanged,
+                          const uint8_t *data, uint64_t len, uint8_t delim, const uint8_t *repl,
+                          uint64_t replLen, uint64_t maxCount, uint64_t *nLines,
+                          uint64_t *nReplaced, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                          int phases, hipStream_t s) {
+  if (int rc = checkReplaceText(dfa, style, data, len, repl, replLen, outLen)) return rc;
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  // ONE allocation for the call, carved up by launchReplaceText
+  void *scratch = nullptr;
+  HIP_TRY(scratchFor(s, size_t(replaceTextScratchBytes(len)), &scratch), "hipMalloc scratch");
+  const LaunchCfg cfg = cfgOf(dfa);
+  const char *name = "";
+  const hipError_t e = launchReplaceText(dfa->im->dev, style, doLeader ? 1 : 0, onlyChanged ? 1 : 0,
+                                         data, len, delim, repl, replLen, maxCount, nLines,
+                                         nReplaced, outLen, out, outCap, phases, scratch, cfg, s,
+                                         &name);
+  tlsKernel = name;
+  if (e != hipSuccess) return failHip(e, "kernel launch");
+  return REDGPU_OK;
+}
+
+int redgpu_replace_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int only_changed,
+                            const uint8_t *data, uint64_t len, uint8_t delim, const uint8_t *repl,
+                            uint64_t repl_len, uint64_t max_count, uint64_t *n_lines,
+                            uint64_t *n_replaced, uint64_t *out_len, uint8_t *out, uint64_t out_cap,
+                            void *stream) {
+  return replaceTextDev(dfa, style, do_leader, only_changed, data, len, delim, repl, repl_len,
+                        max_count, n_lines, n_replaced, out_len, out, out_cap, 3,
+                        static_cast<hipStream_t>(stream));
+}
+
+// host-buffer form: the text goes up once; phase 1 leaves the sizes, the bitmaps and the chunks'
+// output bases in the stream's scratch, the device output is sized from *out_len, phase 2
+// assembles it, and min(*out_len, out_cap) bytes come back
+int redgpu_replace_text(const redgpu_dfa *dfa, int style, int do_leader, int only_changed,
+                        const uint8_t *data, uint64_t len, uint8_t delim, const uint8_t *repl,
+                        uint64_t repl_len, uint64_t max_count, uint64_t *n_lines,
+                        uint64_t *n_replaced, uint64_t *out_len, uint8_t *out, uint64_t out_cap) {
+  if (int rc = checkReplaceText(dfa, style, data, len, repl, repl_len, out_len)) return rc;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint8_t *dRepl = call.buf<uint8_t>(kSlAux0, repl_len, "repl");
+  uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 3, "sizes");
+  call.upload(dData, data, len, "data");
+  call.upload(dRepl, repl, repl_len, "repl");
+  call.run([&] {
+    return replaceTextDev(dfa, style, do_leader, only_changed, dData, len, delim, dRepl, repl_len,
+                          max_count, dSizes, dSizes + 1, dSizes + 2, nullptr, 0, 1, call.stream());
+  });
+  uint64_t sizes[3] = {0, 0, 0};
+  call.download(sizes, dSizes, 3, "sizes");
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = sizes[0];
+  if (n_replaced) *n_replaced = sizes[1];
+  *out_len = sizes[2];
+  const uint64_t put = sizes[2] < out_cap ? sizes[2] : out_cap;
+  if (!out || !put) return REDGPU_OK;
+  // (the streams are drained: growing the slot waits for nothing)
+  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
+  call.run([&] {
+    return replaceTextDev(dfa, style, do_leader, only_changed, dData, len, delim, dRepl, repl_len,
+                          max_count, dSizes, dSizes + 1, dSizes + 2, dOut, put, 2, call.stream());
+  });
+  call.download(out, dOut, put, "out");
+  return call.wait();
+}
+
 int redgpu_split_lines(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                        uint64_t *offsets, uint64_t cap, uint64_t *n_lines) {
   if (int rc = checkHandle(dfa)) return rc;

@@ -1090,6 +1090,71 @@ def collect_text(exe, data, *, delim=b"\n", cap=None, want_positions=True):
     return int(nl.value), int(nm.value), ln[:k], bg[:k], res[:k], cut(st), cut(en)
 
 
+def replace_text(exe, data, repl, style=styLast, do_leader=True, max_count=1 << 62, *,
+                 only_changed=False, delim=b"\n", out=None, out_cap=None):
+    """redgpu_replace_text[_dev]: sed - every delimiter-terminated line of a raw text buffer
+    rewritten by replace<style,doLeader>(line, repl, max_count) (include/Matcher.h:186-191, core
+    :643-706, inside tools/skim_red.cpp:36-46's line loop) and the lines put back together as a
+    text: each rewritten line, its delimiter, and behind the last line the tail, unchanged.
+    max_count is per line: 1 is sed s/x/y/, the default s/x/y/g, 0 copies the text.
+    only_changed=True is sed -n 's/x/y/p': only the lines with a replacement, no tail.
+    Host input -> (n_lines, n_replaced, bytes).
+    A CUDA uint8 tensor needs out (a contiguous uint8 CUDA tensor to write into) or out_cap (one
+    of that size is made; 0 gives the sizes only) -> (n_lines, n_replaced, out_len, out): the
+    counts as 1-element int64 tensors, asynchronously on the current stream and without any
+    read-back; out_len may exceed the room, bytes of out from min(out_len, room) on are untouched.
+    repl is bytes or, for the device form, a uint8 CUDA tensor too."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    style, lead, oc = int(style), 1 if do_leader else 0, 1 if only_changed else 0
+    max_count = int(max_count)
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = data.device
+        if out is None and out_cap is None:
+            raise RedExceptApi("device replace_text needs out or out_cap (room for the output)")
+        if out is None:
+            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
+        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
+              not out.is_contiguous() or out.device != dev):
+            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
+        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        if _is_torch(repl):
+            if (not repl.is_cuda or repl.dtype != torch.uint8 or not repl.is_contiguous() or
+                    repl.device != dev):
+                raise RedExceptApi("repl must be bytes or a contiguous uint8 CUDA tensor")
+            drepl = repl
+        else:
+            r = np.frombuffer(bytes(repl), dtype=np.uint8)
+            drepl = torch.from_numpy(r.copy()).to(dev)
+        cnt = torch.empty(3, dtype=torch.int64, device=dev)
+        _check(l.redgpu_replace_text_dev(
+            exe._h, style, lead, oc, data.data_ptr() if data.numel() else None, data.numel(), d,
+            drepl.data_ptr() if drepl.numel() else None, drepl.numel(), max_count, cnt.data_ptr(),
+            cnt.data_ptr() + 8, cnt.data_ptr() + 16, out.data_ptr() if room else None, room,
+            torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], cnt[2:3], out
+    if out is not None or out_cap is not None:
+        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    a = _host_u8(data)
+    r = np.frombuffer(bytes(repl), dtype=np.uint8)
+    nl, nr, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    # first guess: output about as long as the input; once more with the exact size otherwise
+    cap = int(a.size + 64)
+    for _ in range(2):
+        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+        _check(l.redgpu_replace_text(
+            exe._h, style, lead, oc, a.ctypes.data if a.size else None, a.size, d,
+            r.ctypes.data if r.size else None, r.size, max_count, C.byref(nl), C.byref(nr),
+            C.byref(olen), buf.ctypes.data, cap))
+        if int(olen.value) <= cap:
+            break
+        cap = int(olen.value)
+    return int(nl.value), int(nr.value), buf[:int(olen.value)].tobytes()
+
+
 class StatefulMatcher:
     """Mirror of zezax::red::StatefulMatcher (include/Matcher.h:770-792): `advance(byte)` and
     `result()`; `advance_bytes` feeds a whole chunk in one kernel launch.  The executable must
