@@ -531,7 +531,9 @@ std::string buildImage(const void *reda, size_t len, uint32_t ldsTableMax, bool 
       for (uint32_t c = 0; c < nCls; ++c)
         push(img.next[size_t(x) * nCls + c], img.next[size_t(y) * nCls + c]);
     }
-    img.suffixClosed = closed;
+    // (the product walk takes the table as it stands; the walks STOP at a state flagged a pure dead
+    // end, so a flagged state with a way out makes the attempt at 0 end where a later one goes on)
+    img.suffixClosed = closed && img.deadAbsorbing;
     int32_t one = 0;
     bool uniform = true;
     for (uint32_t i = 0; i < n && uniform; ++i)

@@ -97,7 +97,9 @@ struct DfaImage {
   // with a loose start).  Then an attempt of scan / search that walked to the end of the line
   // without an accepting state proves that no later start position can accept either (the
   // text it would read is a suffix of what this attempt read), and the sliding loop can stop.
-  // Decided by language inclusion L(init) <= L(next(init, c)) for every class c (product walk).
+  // Decided by language inclusion L(init) <= L(next(init, c)) for every class c (product walk);
+  // never set when a state flagged a pure dead end has a way out (deadAbsorbing = false): an
+  // attempt stops at the flag, so the language of the table is not what the walks see.
   bool     suffixClosed = false;
   // every accepting state reports the same result (a single pattern, or several under one id):
   // check then answers the same for every style but styFull - whichever accepting state a style

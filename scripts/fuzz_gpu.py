@@ -1,13 +1,18 @@
 """Differential fuzz on the GPU: random DFAs x random line shapes x every verb / style / leader x
 random placement and kernel-selection flags, against the CPU oracle.  Not part of the pytest
 suite (it is open-ended); a failure prints the case and exits non-zero.
-usage: fuzz_gpu.py [cases] [seed] [hot | cls | lists | blocks | long]
+usage: fuzz_gpu.py [cases] [seed] [hot | cls | lists | blocks | long | text]
 long: the DFAs and placement flags of the general mode, one buffer of 2 KiB to 128 KiB as ONE
 text through collect_long, replace_long, search_long and match_all_long (random style, leader
 setting, chunk size, cap / max count and replacement).  Without a pure dead state an attempt that
 does not accept walks to the end of the text - quadratic on the CPU and on the device's one lane -
 so those DFAs get the first KiB of the buffer, and so do DFAs whose pure dead state the text's
-walks do not reach (walks_die); match_all_long is one anchored walk and always gets all of it."""
+walks do not reach (walks_die); match_all_long is one anchored walk and always gets all of it.
+text: the same DFAs and flags, one buffer of 0 to 96 KiB as a raw text through grep_text,
+collect_text, replace_text and match_text, each against sampleLines' loop (oracle.split_lines_loop)
+plus the oracle's verb on every line alone.  The delimiter is '\n', 0, ' ' or a byte of the data, put
+at a random density over whatever the data holds of it; where walks do not die (as above) a
+delimiter comes at least every 1024 bytes, since search over a line is quadratic there."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -25,6 +30,7 @@ LISTS = len(sys.argv) > 3 and sys.argv[3] == "lists"            # only the recor
 BLOCKS = len(sys.argv) > 3 and sys.argv[3] == "blocks"          # >= 4096 lines, check / match /
                                                                 # match_all: the block kernels
 LONG = len(sys.argv) > 3 and sys.argv[3] == "long"              # one text, the *_long verbs
+TEXT = len(sys.argv) > 3 and sys.argv[3] == "text"              # one raw text, the *_text verbs
 rng = np.random.default_rng(seed)
 ALPHA = np.frombuffer(b"abcdefghijklmnopqrstuvwxyz0123456789 ./:-_=&?%@[]", dtype=np.uint8)
 
@@ -117,6 +123,8 @@ def walks_die(cpu, data):
     """64 walks of 256 bytes from the initial state, spread over data: at most one in eight may
     still be alive (a state is a dead end when every byte leads back to it with result 0)"""
     k, L = 64, 256
+    if len(data) < L:
+        return False
     pos = np.linspace(0, len(data) - L, k).astype(np.int64)
     buf = np.concatenate([data[p:p + L] for p in pos])
     st = np.full(k, O.STATE_INITIAL, dtype=np.uint32)
@@ -176,12 +184,134 @@ def long_case(desc, blob, exe, cpu, data):
     return None
 
 
+REPLS = [b"", b"#", b"<<>>", b"0123456789" * 4]
+SENT = 0x55
+UNLIMITED = 1 << 62
+
+
+def text_case(desc, blob, exe, cpu, data):
+    """grep_text, collect_text, replace_text and match_text over data as a raw text; the failing
+    call or None"""
+    import torch
+    delim = [0x0A, 0x00, 0x20, int(data[int(rng.integers(0, len(data)))]) if len(data) else 0x0A][
+        int(rng.integers(0, 4))]
+    density = [0.0, 1 / 2000, 1 / 100, 1 / 8, 1.0][int(rng.integers(0, 5))]
+    data = data.copy()
+    data[rng.random(len(data)) < density] = delim
+    if exe.info["n_pure_dead"] == 0 or not walks_die(cpu, data):
+        data[1023::1024] = delim
+    text = data.tobytes()
+    # sampleLines' loop: line k = text[begins[k] : begins[k] + len(lines[k])], its delimiter behind it
+    lines = O.split_lines_loop(text, delim)
+    n = len(lines)
+    lens = np.array([len(x) for x in lines], dtype=np.int64)
+    begins = (np.cumsum(lens + 1) - (lens + 1)).astype(np.uint64)
+    tail = text[int(lens.sum()) + n:]
+    # ... and the lines back to back without their delimiters: the oracle's verb on each alone
+    bare = np.frombuffer(b"".join(lines) + b"\0", dtype=np.uint8)
+    boffs = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    shape = (len(text), delim, density, n)
+
+    def same(got, want):
+        return len(got) == len(want) and all(
+            (g is None and w is None) or (g is not None and w is not None and
+                                          np.array_equal(np.asarray(g).astype(np.int64),
+                                                         np.asarray(w).astype(np.int64)))
+            for g, w in zip(got, want))
+
+    for verb in ("grep_text", "collect_text", "replace_text", "match_text"):
+        sty = int(rng.integers(1, 6))
+        lead = int(rng.integers(0, 2))
+        if verb == "grep_text":
+            invert = bool(rng.integers(0, 2))
+            mx = int(rng.choice([0, 1, 7, UNLIMITED]))
+            cap = [None, 0, 3][int(rng.integers(0, 3))]
+            r, s, e = cpu.batch("search", sty, lead, bare, offsets=boffs, threads=4)
+            sel = np.flatnonzero((r > 0) != invert)
+            total = min(len(sel), mx)
+            sel = sel[:total if cap is None else min(total, cap)]
+            want = (n, total, sel, begins[sel], begins[sel] + lens[sel].astype(np.uint64),
+                    r[sel], s[sel], e[sel])
+            got = one_amd.grep_text(exe, data, sty, bool(lead), invert=invert, delim=delim, cap=cap,
+                                    max_count=mx)
+            ok = got[:2] == want[:2] and same(got[2:], want[2:])
+            what = (verb, sty, lead, invert, mx, cap)
+        elif verb == "collect_text":
+            cap = [None, 0, 5][int(rng.integers(0, 3))]
+            pos = bool(rng.integers(0, 2))
+            counts, r, s, e = cpu.collect_batch(bare, 8, offsets=boffs)
+            recs = []           # (line, result, start, end), positions relative to the line
+            for k in np.flatnonzero(counts).tolist():
+                c = int(counts[k])
+                if c <= 8:
+                    mine = list(zip(r[k, :c].tolist(), s[k, :c].tolist(), e[k, :c].tolist()))
+                else:
+                    mine, again = cpu.collect(lines[k], c)
+                    assert again == c
+                recs += [(k,) + m for m in mine]
+            total = len(recs)
+            recs = np.array(recs[:total if cap is None else cap], dtype=np.int64).reshape(-1, 4)
+            b = begins[recs[:, 0]].astype(np.int64)
+            want = (n, total, recs[:, 0], b, recs[:, 1], recs[:, 2] + b if pos else None,
+                    recs[:, 3] + b if pos else None)
+            got = one_amd.collect_text(exe, data, delim=delim, cap=cap, want_positions=pos)
+            ok = got[:2] == want[:2] and same(got[2:], want[2:])
+            what = (verb, cap, pos)
+        elif verb == "replace_text":
+            repl = REPLS[int(rng.integers(0, len(REPLS)))]
+            mx = int(rng.choice([0, 1, 3, UNLIMITED]))
+            oc = bool(rng.integers(0, 2))
+            out_cap = [None, 0, "half"][int(rng.integers(0, 3))]
+            memo = {}
+            for x in lines:
+                if x not in memo:
+                    memo[x] = cpu.replace(x, repl, sty, bool(lead), mx)
+            d = bytes([delim])
+            if oc:              # only the lines with a replacement, each with its delimiter; no tail
+                out = b"".join(memo[x][1] + d for x in lines if memo[x][0] > 0)
+            else:
+                out = b"".join(memo[x][1] + d for x in lines) + tail
+            n_repl = sum(memo[x][0] for x in lines)
+            if out_cap is None:
+                got = one_amd.replace_text(exe, data, repl, sty, bool(lead), mx, only_changed=oc,
+                                           delim=delim)
+                ok = got == (n, n_repl, out)
+            else:
+                # the device form into a sentinel-filled buffer: min(out_len, room) bytes written
+                room = 0 if out_cap == 0 else len(out) // 2
+                buf = torch.full((len(out) + 16,), SENT, dtype=torch.uint8, device="cuda")
+                dev = torch.from_numpy(data).cuda()
+                g = one_amd.replace_text(exe, dev, repl, sty, bool(lead), mx, only_changed=oc,
+                                         delim=delim, out=buf, out_cap=room)
+                torch.cuda.synchronize()
+                back = buf.cpu().numpy().tobytes()
+                ok = (int(g[0].item()), int(g[1].item()), int(g[2].item())) == (n, n_repl, len(out)) \
+                    and back[:room] == out[:room] and back[room:] == bytes([SENT]) * (len(back) - room)
+            what = (verb, sty, lead, repl, mx, oc, out_cap)
+        else:
+            check = bool(rng.integers(0, 2))
+            r, s, e = cpu.batch("check" if check else "match", sty, lead, bare, offsets=boffs, threads=4)
+            offs = np.concatenate([begins, [len(text) - len(tail)]]).astype(np.uint64)
+            want = (offs, r, None if check else s, None if check else e)
+            got = one_amd.match_text(exe, data, sty, bool(lead), delim=delim, want_start=not check,
+                                     want_end=not check)
+            ok = got[1] == n and same((got[0],) + got[2:], want)
+            what = (verb, sty, lead, "check" if check else "match")
+        kern = one_amd.last_kernel()
+        stats[kern] = stats.get(kern, 0) + 1
+        if not ok:
+            return what + shape + (kern,)
+    return None
+
+
 t0 = time.time()
 stats = {}
 for case in range(cases):
     name, blob = make_dfa()
     if LONG:
         shape, nbytes = {}, int(rng.integers(2048, 128 * 1024 + 1))
+    elif TEXT:
+        shape, nbytes = {}, int(rng.integers(0, 96 * 1024 + 1))
     else:
         shape, nbytes = make_lines()
     data = make_data(nbytes, name)
@@ -206,9 +336,9 @@ for case in range(cases):
         continue
     cpu = O.CpuOracle(blob)
     desc = (case, name, {k: (v if not hasattr(v, "shape") else "offsets[%d]" % (len(v) - 1)) for k, v in shape.items()}, flags, exe.info["table_kind"])
-    if LONG:
+    if LONG or TEXT:
         try:
-            bad = long_case(desc, blob, exe, cpu, data)
+            bad = (long_case if LONG else text_case)(desc, blob, exe, cpu, data)
         except one_amd.RedExcept as e:
             print("ERROR", desc, e)
             sys.exit(1)

@@ -3,7 +3,8 @@ as compact records in text order - all eight outputs exact against sampleLines' 
 (oracle.split_lines_loop) plus the CPU oracle's search per line (and the reference when present),
 for every style, leader setting, invert, table placement, the chunk-border shapes, truncation,
 limits, the device form at odd pointer offsets, concurrent streams and threads, and the C++
-mirror."""
+mirror.  test_grep_text_under_placement runs every (kind, verb) instantiation of k_gp_select and
+k_gp_write: the rows of test_gpu_long_placements (kinds 2 to 7) and three of test_gpu_list_verbs."""
 import ctypes as C
 import os
 import subprocess
@@ -17,6 +18,9 @@ import oracle as O
 from one_amd import _lib
 from one_amd import workloads as W
 from golden_util import load_dfa
+
+import test_gpu_list_verbs as LV
+import test_gpu_long_placements as LP
 
 pytestmark = pytest.mark.gpu
 
@@ -34,9 +38,16 @@ _texts = {}
 _wants = {}
 
 
+def _blob(name):
+    """the DFA of a placement row from the row's factory (test_gpu_collect_text keeps the one copy;
+    it imports this module, so it is imported here on first use), a golden DFA otherwise"""
+    import test_gpu_collect_text as CT
+    return CT._blob(name)
+
+
 def _orc(name):
     if name not in _oracles:
-        blob = load_dfa(name)
+        blob = _blob(name)
         _oracles[name] = (O.CpuOracle(blob), O.Reference(blob) if O.have_ref() else None)
     return _oracles[name]
 
@@ -193,6 +204,113 @@ def test_grep_text_every_table_placement(name, flags):
                 got = one_amd.grep_text(exe, text, style, bool(lead), invert=invert)
                 assert one_amd.last_kernel() == "k_grep_text"
                 _same(got, want, where=(name, flags, style, lead, invert))
+
+
+def _mixed_text(kind="random", seed=1, n=4 * CHUNK + 5):
+    """Random bytes (the random DFAs, syn256) or a / b / . (leaky) under _standard's delimiters,
+    then a delimiter at every fourth byte of every third line of 12 bytes and more - short lines
+    that mostly stay unselected, where the 1-199 byte lines are nearly all selected - and a 2-byte
+    line across every even multiple of 16384."""
+    import test_gpu_collect_text as CT
+    key = ("mixed", kind, seed, n)
+    if key not in _texts:
+        if kind == "leaky":
+            a = np.frombuffer(b"ab.", dtype=np.uint8)[
+                np.random.default_rng(seed + 1).integers(0, 3, n)].copy()
+        else:
+            a = W.random_bytes(n, seed).copy()
+            a[a == 0x0A] = 0x20
+        ends = CT._delims(n, 1)
+        a[ends] = 0x0A
+        begin = 0
+        for k, end in enumerate(ends):
+            if k % 3 == 0 and end - begin >= 12:
+                a[begin + 3:end:4] = 0x0A
+            begin = end + 1
+        for m in range(2 * CHUNK, n, 2 * CHUNK):
+            a[m - 2] = a[m + 1] = 0x0A
+        _texts[key] = bytes(a)
+    return _texts[key]
+
+
+def _placement_text(dfa):
+    """what a placement row runs over: the regex DFAs' dense text, the mixed text otherwise"""
+    import test_gpu_collect_text as CT
+    if dfa in LP.PIECES:
+        return CT._dense(LP.PIECES[dfa][0])
+    return _mixed_text("leaky" if dfa == "leaky" else "random")
+
+
+def _chunks_of(begins):
+    return set((begins // np.uint64(CHUNK)).tolist())
+
+
+def _placement_guard(dfa, text, style, lead):
+    """on the oracle's output alone: both sides of the selection are large, begin in every one of
+    the four chunks and have lines across a chunk border - k_gp_select's carried line and k_gp_write's
+    record slots are exercised whichever way invert points"""
+    yes = _want(dfa, text, style, lead, False)
+    no = _want(dfa, text, style, lead, True)
+    where = (dfa, style, lead)
+    assert yes[1] >= 150 and no[1] >= 20, where + (yes[1], no[1])
+    assert _chunks_of(yes[3]) >= {0, 1, 2, 3} and _chunks_of(no[3]) >= {0, 1, 2, 3}, where
+    assert _crossing(yes[3:5], text) >= 2, where
+    if dfa != "num3":       # (no line of num3's dense text that crosses a border stays unselected)
+        assert _crossing(no[3:5], text) >= 1, where
+    if dfa not in LP.PIECES and dfa != "leaky":
+        assert len(set(yes[5].tolist())) >= 2, where + (set(yes[5].tolist()),)
+
+
+_PLACEMENT_ROWS = LP.ROWS + [pytest.param(*p.values[:3], id=p.id) for p in LV.TABLE
+                             if p.values[0] in ("syn256", "rnd72", "leaky") and not p.values[1]]
+
+
+@pytest.mark.parametrize("dfa,opts,info", _PLACEMENT_ROWS)
+def test_grep_text_under_placement(dfa, opts, info):
+    """every table kind under both verbs of launchGrepText (search; match for a suffix-closed DFA
+    without a leader), hot tables with 0 to 254 hot rows, a leader with the table in L2, a DFA
+    without a pure dead state, u32 states with results in global memory"""
+    import torch
+    blob = _blob(dfa)
+    facts = one_amd.Executable(blob, device="none").info
+    for k, v in LP.FACTS.get(dfa, {}).items():
+        assert facts[k] == v, (dfa, k, facts[k], v)
+    text = _placement_text(dfa)
+    assert len(text) == 4 * CHUNK + 5 and text[-1] != 0x0A
+    for style in (1, 2, 3, 4):
+        for lead in (0, 1):
+            _placement_guard(dfa, text, style, lead)
+    exe = one_amd.Executable(blob, **opts)
+    got_info = exe.info
+    for k, v in info.items():
+        assert got_info[k] == v, (dfa, opts, k, got_info[k], v)
+    for style in STYLES:
+        for lead in (0, 1):
+            for invert in (False, True):
+                want = _want(dfa, text, style, lead, invert)
+                got = one_amd.grep_text(exe, text, style, bool(lead), invert=invert)
+                assert one_amd.last_kernel() == "k_grep_text"
+                _same(got, want, where=(dfa, opts, style, lead, invert))
+    # truncation, grep -m and the select pass alone; the device form one byte off a 16-byte boundary
+    style, lead = 4, 1
+    buf = torch.zeros(len(text) + 32, dtype=torch.uint8, device="cuda")
+    dev = buf[1:1 + len(text)]
+    dev.copy_(torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()))
+    assert dev.data_ptr() % 16 == 1
+    for invert in (False, True):
+        where = (dfa, opts, style, lead, invert)
+        want = _want(dfa, text, style, lead, invert)
+        cap = want[1] // 2
+        _same(one_amd.grep_text(exe, text, style, bool(lead), invert=invert, cap=cap), want,
+              upto=cap, where=where + ("cap",))
+        _same(one_amd.grep_text(exe, text, style, bool(lead), invert=invert, max_count=7),
+              _want(dfa, text, style, lead, invert, max_count=7), where=where + ("max_count",))
+        got = one_amd.grep_text(exe, text, style, bool(lead), invert=invert, want_outcome=False)
+        assert got[:2] == want[:2] and got[5] is None and got[6] is None and got[7] is None, where
+        for g, w in zip(got[2:5], want[2:5]):
+            assert np.array_equal(g, w), where + ("no outcome",)
+        _same(_dev_call(exe, dev, style, lead, invert, cap=want[0]), want, where=where + ("dev",))
+        assert one_amd.last_kernel() == "k_grep_text"
 
 
 @pytest.mark.parametrize("name", ["set5", "newyork"])

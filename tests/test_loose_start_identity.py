@@ -72,3 +72,18 @@ def test_check_styles_agree_on_single_result_dfas(name, uniform):
     same = all(np.array_equal(cpu.batch("check", st, 0, data, offsets=offsets, threads=4)[0], last)
                for st in (1, 2, 3))
     assert same == uniform, name
+
+
+def test_a_flagged_dead_end_with_a_way_out_is_not_suffix_closed():
+    """The table of test_gpu_match_all_long's leaky DFA accepts "a" behind anything, but its state
+    behind a "b" is flagged a pure dead end: match stops there, search goes on behind it.  The
+    flag must stay off, or search would run as match."""
+    from test_gpu_match_all_long import _leaky_dead_end_dfa
+    blob = _leaky_dead_end_dfa()
+    info = one_amd.Executable(blob, device="none").info
+    assert info["n_pure_dead"] == 1 and info["suffix_closed"] == 0
+    cpu = O.CpuOracle(blob)
+    for style in range(1, 5):
+        assert cpu.match(b"ba", style, False) == (0, 0, 0)
+        assert cpu.search(b"ba", style, False) == (1, 1, 2)
+        assert cpu.check(b"ba", style, False) == 0 and cpu.scan(b"ba", style, False) == 1
