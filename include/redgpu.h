@@ -573,6 +573,58 @@ int redgpu_collect_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t
                             uint64_t *begin, int32_t *result, uint64_t *start, uint64_t *end,
                             void *stream);
 
+/* grep -c per result, or grep -o | sort | uniq -c: raw text in, how many of each result out -
+ * search<style,doLeader> (include/Matcher.h:557-640) or Red::collect (lib/Red.cpp:103-116) inside
+ * the line loop of tools/skim_red.cpp:36-46, over the lines lib/Util.cpp:109-130 cuts, with only
+ * the histogram of the results leaving the device: its size does not depend on the text.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter are not a line and contribute nothing.
+ *  - what == REDGPU_TALLY_LINES: every line is one item, its value the result of
+ *    search<style,do_leader> on that line alone - exactly redgpu_search_batch's result for it
+ *    (and redgpu_grep_text's: the same verb and style normalisation).  A line that does not match
+ *    has value 0.
+ *  - what == REDGPU_TALLY_MATCHES: every record redgpu_collect_text would report is one item, its
+ *    value the record's result.  style and do_leader are not looked at.  No item has value 0.
+ *  - bins has n_bins + 1 slots.  An item of value r is counted in bins[r] when
+ *    (uint32_t)r < n_bins, else in bins[n_bins] ("everything else").  n_bins == 0 is legal: one
+ *    slot.  The slots sum to *n_lines (LINES) or to redgpu_collect_text's *n_matches (MATCHES).
+ *  - accumulate == 0: all n_bins + 1 slots are overwritten.  accumulate != 0: the call's counts
+ *    are added to what the slots hold - a stream of buffers tallied into one histogram.  n_lines
+ *    and n_items are always overwritten.
+ *  - *n_items = the items of value > 0: under LINES redgpu_grep_text's unbounded n_selected
+ *    (without invert), under MATCHES redgpu_collect_text's n_matches.  *n_lines = delimiters found.
+ *    n_lines and n_items may be NULL, each on its own; bins is required.
+ *  - Counts are 64-bit and exact: integer sums, so the result does not depend on scheduling and
+ *    is bit-identical from run to run.
+ *  - REDGPU_EAPI for a NULL handle, a NULL bins, a NULL data with len > 0, a `what` other than the
+ *    two above (the argument checks run before the handle's device is looked at) and for a
+ *    REDGPU_DEVICE_NONE handle; REDGPU_EEXEC for a style that does not exist (LINES only);
+ *    REDGPU_ELIMIT for a text redgpu_split_lines refuses or n_bins > 2^31.  In every error case
+ *    nothing the caller passed is written.
+ *  - An empty text, or one without a delimiter: *n_lines = 0, *n_items = 0, the bins zeroed (left
+ *    alone under accumulate); the _dev form does this on the stream.
+ * redgpu_last_kernel() says "k_tally_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - nothing is read
+ * back.  Scratch is what the line driver needs (ONE bitmap and 20 bytes per 16 KiB chunk: len / 8
+ * + 20 bytes per chunk + 32, from the thread's pool): no selected or hit bitmap, nothing
+ * proportional to n_bins.
+ * redgpu_tally_text: host buffers - one upload of the text, device bins of its own, n_bins + 1
+ * counts and the two totals back; under accumulate they are added on the host.
+ * redgpu_tally_lds_bins: how many leading bins the kernel keeps in on-chip memory (LDS) for this
+ * handle, for texts below 4 GiB: min(4096, what the table leaves of a workgroup's share of the
+ * LDS), 0 when the table leaves no room; values from there on are counted in device memory
+ * directly.  A pure host function, valid for REDGPU_DEVICE_NONE handles too; 0 for a NULL handle. */
+#define REDGPU_TALLY_LINES   0  /* one item per line: search<style,do_leader> on the line */
+#define REDGPU_TALLY_MATCHES 1  /* one item per match: Red::collect on the line */
+int redgpu_tally_text(const redgpu_dfa *dfa, int what, int style, int do_leader,
+                      const uint8_t *data, uint64_t len, uint8_t delim, uint64_t n_bins,
+                      int accumulate, uint64_t *n_lines, uint64_t *n_items, uint64_t *bins);
+int redgpu_tally_text_dev(const redgpu_dfa *dfa, int what, int style, int do_leader,
+                          const uint8_t *data, uint64_t len, uint8_t delim, uint64_t n_bins,
+                          int accumulate, uint64_t *n_lines, uint64_t *n_items, uint64_t *bins,
+                          void *stream);
+uint32_t redgpu_tally_lds_bins(const redgpu_dfa *dfa);
+
 /* sed: raw text in, the text with every line rewritten out - replace<style,doLeader>
  * (include/Matcher.h:186-191, core :643-706; what Red's replaceOne* / replaceAll* and
  * Red::replace / Red::globalReplace, include/Red.h:139-251, end in) inside the line loop of

@@ -272,6 +272,21 @@ inline size_t collectTextCount(const Executable &exec, std::string_view text, ch
   return size_t(found);
 }
 
+// grep -c per result / grep -o | sort | uniq -c (redgpu_tally_text): nBins + 1 counts, [r] = the
+// items of value r < nBins, [nBins] = everything else.  matches = true: one item per match of
+// every line (collectText's records, style and doLeader not looked at); false: one item per line,
+// its value the result of search<style,doLeader> on it, 0 when it does not match.
+inline std::vector<uint64_t> tallyText(const Executable &exec, std::string_view text, size_t nBins,
+                                       bool matches = true, Style style = styInstant,
+                                       bool doLeader = true, char delim = '\n') {
+  std::vector<uint64_t> bins(nBins + 1);
+  throwOnError(redgpu_tally_text(exec.handle(), matches ? REDGPU_TALLY_MATCHES : REDGPU_TALLY_LINES,
+                                 style, doLeader, reinterpret_cast<const Byte *>(text.data()),
+                                 text.size(), Byte(delim), nBins, 0, nullptr, nullptr,
+                                 bins.data()));
+  return bins;
+}
+
 // sed (replace<style,doLeader>, include/Matcher.h:186-191, inside tools/skim_red.cpp:36-46's line
 // loop): every line of a text blob rewritten and the text put back together in `out` - the lines,
 // their delimiters, and the tail behind the last delimiter unchanged.  max is per line (1 = sed

@@ -165,16 +165,19 @@ struct GpChunk {
 };
 
 // per chunk: the position behind its last delimiter (0 = it has none); its selected bits zeroed
+// (selMasks may be null: nothing is zeroed then)
 __global__ void __launch_bounds__(256)
 k_gp_last(const uint16_t *masks, const uint32_t *counts, uint64_t nChunks, uint64_t *open,
           uint16_t *selMasks) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t waves = uint64_t(gridDim.x) * 4;
   for (uint64_t ch = uint64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); ch < nChunks; ch += waves) {
-    uint4 *z = reinterpret_cast<uint4 *>(reinterpret_cast<uint8_t *>(selMasks) +
-                                         ch * (kSplitChunk / 8) + lane * 32u);
-    z[0] = make_uint4(0, 0, 0, 0);
-    z[1] = make_uint4(0, 0, 0, 0);
+    if (selMasks) {  // (uniform; k_tally_text.h has no selected bitmap)
+      uint4 *z = reinterpret_cast<uint4 *>(reinterpret_cast<uint8_t *>(selMasks) +
+                                           ch * (kSplitChunk / 8) + lane * 32u);
+      z[0] = make_uint4(0, 0, 0, 0);
+      z[1] = make_uint4(0, 0, 0, 0);
+    }
     uint32_t last = 0;
     if (counts[ch]) {  // (uniform)
       const uint32_t mine = gpLoadBits(masks, ch, lane).last();

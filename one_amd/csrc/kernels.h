@@ -217,6 +217,22 @@ hipError_t launchCollectText(const DevDfa &dfa, const uint8_t *data, uint64_t le
                              void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                              const char **kernelName);
 
+// grep -c per result over a raw text (k_tally_text.h): one item per line of launchSplitLines' rule
+// (what = REDGPU_TALLY_LINES: its value the result of search<style, doLeader> on the line, by
+// launchGrepText's normalisation) or per record launchCollectText would report (REDGPU_TALLY_MATCHES:
+// its value the record's result), counted in bins[value] for (uint32_t)value < nBins, else in
+// bins[nBins]: overwritten, or added to under accumulate.  *nItems = items of value > 0; nLines and
+// nItems may be null.  plain != 0: an atomic per item (the form the ballot / peel form is measured
+// against).  scratch: tallyTextScratchBytes(len) bytes of device memory, 16-byte aligned.
+// *kernelName = "k_tally_text".  tallyLdsBins: the leading bins the kernel keeps in LDS for a DFA of
+// this table kind, staged table size (DevDfa::tableBytes) and state count - a host function.
+uint64_t tallyTextScratchBytes(uint64_t len);
+uint32_t tallyLdsBins(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates);
+hipError_t launchTallyText(const DevDfa &dfa, int what, int style, int doLeader, const uint8_t *data,
+                           uint64_t len, uint8_t delim, uint64_t nBins, int accumulate, int plain,
+                           uint64_t *nLines, uint64_t *nItems, uint64_t *bins, void *scratch,
+                           const LaunchCfg &cfg, hipStream_t stream, const char **kernelName);
+
 // sed over a raw text (k_replace_text.h): replace<style, doLeader>(line, repl, max) over every line
 // of launchSplitLines' rule, the rewritten lines and their delimiters put back together (and the
 // tail behind them; under onlyChanged the changed lines alone, no tail): *outLen = the output's

@@ -42,6 +42,8 @@
 //                     a wave per 16 KiB chunk selects, a scan orders, a second pass writes records
 //   k_collect_text.h  k_ct_*: grep -o over a raw text - k_grep.h's line driver, Red::collect per line,
 //                     a count pass, a scan, and a write pass that puts record j at slot j
+//   k_tally_text.h    k_tally_text: grep -c per result over a raw text - the same line driver, ONE pass,
+//                     the counts in a privatised LDS histogram flushed once per workgroup
 //   k_replace_text.h  k_rt_*: sed over a raw text - the same line driver, replaceCore per line, a
 //                     sizing pass, a scan, and a write pass whose waves copy the unchanged bytes
 //   k_diag.h          bench.py's calibration kernels
@@ -56,10 +58,11 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled six times in parallel (Makefile: -DREDGPU_TU=1/2/.../6): the templates are
+// This file is compiled seven times in parallel (Makefile: -DREDGPU_TU=1/2/.../7): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
-// 3 = everything else and the dispatch, 4 = k_grep, 5 = k_collect_text, 6 = k_replace_text.
+// 3 = everything else and the dispatch, 4 = k_grep, 5 = k_collect_text, 6 = k_replace_text,
+// 7 = k_tally_text.
 // REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
@@ -70,6 +73,7 @@
 #define REDGPU_TU_GREP (REDGPU_TU == 0 || REDGPU_TU == 4)
 #define REDGPU_TU_COLLECT_TEXT (REDGPU_TU == 0 || REDGPU_TU == 5)
 #define REDGPU_TU_REPLACE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 6)
+#define REDGPU_TU_TALLY_TEXT (REDGPU_TU == 0 || REDGPU_TU == 7)
 
 namespace redgpu {
 
@@ -97,6 +101,7 @@ namespace {
 #include "launchers.h"
 #include "k_grep.h"
 #include "k_collect_text.h"
+#include "k_tally_text.h"
 #include "k_replace_text.h"
 
 } // namespace
@@ -1040,6 +1045,96 @@ hipError_t launchCollectText(const DevDfa &d, const uint8_t *data, uint64_t len,
 #undef CT_CALL
 }
 #endif  // REDGPU_TU_COLLECT_TEXT
+
+#if REDGPU_TU_TALLY_TEXT
+// grep -c per result over a raw text (k_tally_text.h): the split's count and scan and grep's
+// k_gp_last / k_gp_open as they stand, then k_tl_zero and the one pass of k_tally_text.  scratch:
+// tallyTextScratchBytes(len) bytes, 16-byte aligned: ONE bitmap and 20 bytes per chunk.
+uint64_t tallyTextScratchBytes(uint64_t len) {
+  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
+  return nChunks * 16 + 32 + nChunks * (kSplitChunk / 8) + ((nChunks * 4 + 15) & ~uint64_t(15));
+}
+
+#define TL_KINDS(F)                                                       \
+  switch (tableKind) {                                                    \
+  case REDGPU_TAB_LDS_FUSED_U8: return F(REDGPU_TAB_LDS_FUSED_U8);        \
+  case REDGPU_TAB_LDS_FUSED_U16: return F(REDGPU_TAB_LDS_FUSED_U16);      \
+  case REDGPU_TAB_LDS_CLASS_U16: return F(REDGPU_TAB_LDS_CLASS_U16);      \
+  case REDGPU_TAB_GLOBAL_U16: return F(REDGPU_TAB_GLOBAL_U16);            \
+  case REDGPU_TAB_HOT_ROWS: return F(REDGPU_TAB_HOT_ROWS);                \
+  case REDGPU_TAB_LDS_SPARSE: return F(REDGPU_TAB_LDS_SPARSE);            \
+  default: return F(REDGPU_TAB_GLOBAL_U32);                               \
+  }
+
+uint32_t tallyLdsBins(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates) {
+  DevDfa d{};
+  d.tableKind = tableKind;
+  d.tableBytes = tableBytes;
+  d.nStates = nStates;
+#define TL_BINS(K) tallyLdsBinsK<K>(d)
+  TL_KINDS(TL_BINS)
+#undef TL_BINS
+}
+
+hipError_t launchTallyText(const DevDfa &d, int what, int style, int doLeader, const uint8_t *data,
+                           uint64_t len, uint8_t delim, uint64_t nBins, int accumulate, int plain,
+                           uint64_t *nLines, uint64_t *nItems, uint64_t *bins, void *scratch,
+                           const LaunchCfg &cfg, hipStream_t stream, const char **kernelName) {
+  *kernelName = "k_tally_text";
+  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
+  // [bases, open: u64[nChunks] each][lines, dummy, items: u64, 8 spare][delimiter bitmap]
+  // [counts: u32[nChunks]]
+  uint8_t *q = static_cast<uint8_t *>(scratch);
+  uint64_t *bases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint64_t *open = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
+  uint64_t *misc = reinterpret_cast<uint64_t *>(q); q += 32;
+  uint16_t *masks = reinterpret_cast<uint16_t *>(q); q += nChunks * (kSplitChunk / 8);
+  uint32_t *counts = reinterpret_cast<uint32_t *>(q);
+  uint64_t *dummy = misc + 1;
+  if (nChunks) {
+    hipLaunchKernelGGL(k_split_count, dim3(uint32_t(nChunks)), dim3(kSplitThreads), 0, stream, data,
+                       len, uint32_t(delim), nChunks, counts, masks);
+  }
+  // (k_split_scan's offsets[0] store goes to a spare word)
+  hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, counts, nChunks, bases,
+                     nLines ? nLines : misc, dummy, uint64_t(0));
+  if (nChunks) {
+    uint64_t small = (nChunks + 3) / 4;
+    if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
+    // (no selected bitmap to zero)
+    hipLaunchKernelGGL(k_gp_last, dim3(uint32_t(small)), dim3(256), 0, stream, masks, counts,
+                       nChunks, open, static_cast<uint16_t *>(nullptr));
+    hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, open, nChunks);
+  }
+  const uint64_t toZero = accumulate ? 0 : nBins + 1;
+  uint64_t zb = (toZero + 255) / 256;
+  if (zb > uint64_t(cfg.numCUs) * 8) zb = uint64_t(cfg.numCUs) * 8;
+  TallyOut o{reinterpret_cast<unsigned long long *>(bins),
+             reinterpret_cast<unsigned long long *>(nItems ? nItems : misc + 2), uint32_t(nBins), 0};
+  hipLaunchKernelGGL(k_tl_zero, dim3(uint32_t(zb ? zb : 1)), dim3(256), 0, stream, o.bins, toZero,
+                     o.nItems);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || nChunks == 0) return e;
+  const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
+  int verb = kSearch;
+  if (what == REDGPU_TALLY_LINES) normalizeVerbStyle(d, cfg, lead != 0, verb, style);
+  // L: the leading bins kept in LDS.  32-bit counters hold a text below 4 GiB whatever it is
+  // (k_tally_text.h: tallyAdd); a longer text counts in global memory alone
+  const uint32_t room = len < (1ull << 32) ? tallyLdsBins(d.tableKind, d.tableBytes, d.nStates) : 0u;
+  o.ldsBins = nBins + 1 < room ? uint32_t(nBins + 1) : room;
+  const GpBufs b{masks, nullptr, bases, open, nullptr, nullptr, nChunks};
+  const uint32_t tableKind = d.tableKind;
+#define TL_ARGS d, data, b, style, lead, plain, o, cfg, stream
+#define TL_CALL(K)                                                                    \
+  (what == REDGPU_TALLY_MATCHES ? launchTallyK<K, kTallyMatches>(TL_ARGS)             \
+   : verb == kSearch            ? launchTallyK<K, kTallyLines>(TL_ARGS)               \
+                                : launchTallyK<K, kTallyLinesMatch>(TL_ARGS))
+  TL_KINDS(TL_CALL)
+#undef TL_CALL
+#undef TL_ARGS
+}
+#undef TL_KINDS
+#endif  // REDGPU_TU_TALLY_TEXT
 
 #if REDGPU_TU_REPLACE_TEXT
 // sed over a raw text (k_replace_text.h): the split's count and scan and grep's k_gp_last /

@@ -1304,6 +1304,92 @@ int redgpu_collect_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len
   return call.wait();
 }
 
+// the arguments of both tally_text forms: what can be refused without a device first
+static int checkTallyText(const redgpu_dfa *dfa, int what, int style, const uint8_t *data,
+                          uint64_t len, uint64_t nBins, const uint64_t *bins) {
+  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
+  if (!bins) return fail(REDGPU_EAPI, "null bins buffer");
+  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
+  if (what != REDGPU_TALLY_LINES && what != REDGPU_TALLY_MATCHES)
+    return fail(REDGPU_EAPI, "what is neither REDGPU_TALLY_LINES nor REDGPU_TALLY_MATCHES");
+  if (what == REDGPU_TALLY_LINES)
+    if (int rc = checkStyle(style)) return rc;
+  if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
+  if (nBins > (1ull << 31)) return fail(REDGPU_ELIMIT, "n_bins too large");
+  return checkHandle(dfa);
+}
+
+// raw text -> how many lines / matches report each result (k_tally_text.h): everything on
+// `stream`, nothing read back
+int redgpu_tally_text_dev(const redgpu_dfa *dfa, int what, int style, int do_leader,
+                          const uint8_t *data, uint64_t len, uint8_t delim, uint64_t n_bins,
+                          int accumulate, uint64_t *n_lines, uint64_t *n_items, uint64_t *bins,
+                          void *stream) {
+  if (int rc = checkTallyText(dfa, what, style, data, len, n_bins, bins)) return rc;
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // ONE allocation for the call, carved up by launchTallyText
+  void *scratch = nullptr;
+  HIP_TRY(scratchFor(s, size_t(tallyTextScratchBytes(len)), &scratch), "hipMalloc scratch");
+  const LaunchCfg cfg = cfgOf(dfa);
+  // REDGPU_TALLY_PLAIN=1: an atomic per item, no ballot and no peel (measurements)
+  const char *env = getenv("REDGPU_TALLY_PLAIN");
+  const int plain = env && env[0] == '1';
+  const char *name = "";
+  const hipError_t e = launchTallyText(dfa->im->dev, what, style, do_leader ? 1 : 0, data, len,
+                                       delim, n_bins, accumulate ? 1 : 0, plain, n_lines, n_items,
+                                       bins, scratch, cfg, s, &name);
+  tlsKernel = name;
+  if (e != hipSuccess) return failHip(e, "kernel launch");
+  return REDGPU_OK;
+}
+
+// host-buffer form: one upload of the text, device bins of the call's own, then the two counts
+// and the n_bins + 1 slots back - added to the caller's on the host under accumulate
+int redgpu_tally_text(const redgpu_dfa *dfa, int what, int style, int do_leader,
+                      const uint8_t *data, uint64_t len, uint8_t delim, uint64_t n_bins,
+                      int accumulate, uint64_t *n_lines, uint64_t *n_items, uint64_t *bins) {
+  if (int rc = checkTallyText(dfa, what, style, data, len, n_bins, bins)) return rc;
+  std::vector<uint64_t> got;
+  if (accumulate) {
+    try {
+      got.resize(size_t(n_bins + 1));
+    } catch (const std::bad_alloc &) {
+      return fail(REDGPU_ELIMIT, "out of host memory");
+    }
+  }
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dN = call.buf<uint64_t>(kSlAux0, 2, "counts");
+  uint64_t *dBins = call.buf<uint64_t>(kSlAux1, n_bins + 1, "bins");
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return redgpu_tally_text_dev(dfa, what, style, do_leader, dData, len, delim, n_bins, 0, dN,
+                                 dN + 1, dBins, call.stream());
+  });
+  uint64_t counts[2] = {0, 0};
+  call.download(counts, dN, 2, "counts");
+  // (nothing of the caller's is written before the last copy has arrived)
+  if (accumulate) call.download(got.data(), dBins, n_bins + 1, "bins");
+  if (int rc = call.wait()) return rc;
+  if (!accumulate) {
+    call.download(bins, dBins, n_bins + 1, "bins");
+    if (int rc = call.wait()) return rc;
+  } else {
+    for (uint64_t i = 0; i <= n_bins; ++i) bins[i] += got[size_t(i)];
+  }
+  if (n_lines) *n_lines = counts[0];
+  if (n_items) *n_items = counts[1];
+  return REDGPU_OK;
+}
+
+uint32_t redgpu_tally_lds_bins(const redgpu_dfa *dfa) {
+  if (!dfa) return 0;
+  const DfaImage &img = dfa->im->img;
+  return tallyLdsBins(img.tableKind, (img.primaryBytes + 15u) & ~15u, img.nStates);
+}
+
 // the arguments of both replace_text forms: what can be refused without a device first
 static int checkReplaceText(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
                             const uint8_t *repl, uint64_t replLen, const uint64_t *outLen) {

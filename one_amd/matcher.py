@@ -1090,6 +1090,66 @@ def collect_text(exe, data, *, delim=b"\n", cap=None, want_positions=True):
     return int(nl.value), int(nm.value), ln[:k], bg[:k], res[:k], cut(st), cut(en)
 
 
+TALLY_LINES, TALLY_MATCHES = 0, 1
+
+
+def tally_text(exe, data, n_bins=None, *, matches=True, style=styInstant, do_leader=True,
+               delim=b"\n", into=None):
+    """redgpu_tally_text[_dev]: grep -c per result (matches=False: one item per delimiter-terminated
+    line, its value the result of search<style,doLeader> on the line, 0 when it does not match) or
+    grep -o | sort | uniq -c (matches=True: one item per record collect_text would report, its
+    value the record's result) - only the histogram leaves the device.  bins has n_bins + 1 slots:
+    bins[r] counts the items of value r < n_bins, bins[n_bins] everything else; n_bins=None means
+    exe.info["max_result"] + 1, so that every result has a slot of its own.  n_items = the items of
+    value > 0 (the selected lines / the matches).  Counts are exact 64-bit integer sums.
+    Host input -> (n_lines, n_items, bins): bins a uint64 array of n_bins + 1; into= takes such an
+    array and ADDS to it (a stream of buffers tallied into one histogram) and returns it.
+    A CUDA uint8 tensor -> the same tuple as device tensors, n_lines and n_items as 1-element int64
+    tensors and bins as int64 (into= an int64 CUDA tensor of n_bins + 1), asynchronously on the
+    current stream and without any read-back."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    what = TALLY_MATCHES if matches else TALLY_LINES
+    style, lead = int(style), 1 if do_leader else 0
+    n_bins = int(exe.info["max_result"]) + 1 if n_bins is None else int(n_bins)
+    if n_bins < 0:
+        raise RedExceptApi("n_bins must not be negative")
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = data.device
+        if into is None:
+            bins = torch.empty(n_bins + 1, dtype=torch.int64, device=dev)
+        else:
+            if (not _is_torch(into) or not into.is_cuda or into.device != dev or
+                    into.dtype != torch.int64 or not into.is_contiguous() or
+                    into.numel() != n_bins + 1):
+                raise RedExceptApi("into must be a contiguous int64 CUDA tensor of n_bins + 1 on "
+                                   "the input's device")
+            bins = into
+        cnt = torch.empty(2, dtype=torch.int64, device=dev)
+        _check(l.redgpu_tally_text_dev(
+            exe._h, what, style, lead, data.data_ptr() if data.numel() else None, data.numel(), d,
+            n_bins, 0 if into is None else 1, cnt.data_ptr(), cnt.data_ptr() + 8, bins.data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], bins
+    a = _host_u8(data)
+    dp = a.ctypes.data if a.size else None
+    if into is None:
+        bins = np.zeros(n_bins + 1, dtype=np.uint64)
+    else:
+        if (not isinstance(into, np.ndarray) or into.dtype != np.uint64 or into.ndim != 1 or
+                into.size != n_bins + 1 or not into.flags.c_contiguous):
+            raise RedExceptApi("into must be a contiguous uint64 array of n_bins + 1")
+        bins = into
+    nl, ni = C.c_uint64(0), C.c_uint64(0)
+    _check(l.redgpu_tally_text(exe._h, what, style, lead, dp, a.size, d, n_bins,
+                               0 if into is None else 1, C.byref(nl), C.byref(ni),
+                               bins.ctypes.data))
+    return int(nl.value), int(ni.value), bins
+
+
 def replace_text(exe, data, repl, style=styLast, do_leader=True, max_count=1 << 62, *,
                  only_changed=False, delim=b"\n", out=None, out_cap=None):
     """redgpu_replace_text[_dev]: sed - every delimiter-terminated line of a raw text buffer
