@@ -3,21 +3,21 @@
 // the lines lib/Util.cpp:109-130 cuts)
 // (included by kernels.hip inside namespace redgpu { namespace { ... } }, after k_grep.h).
 //
-// The lines are driven as k_grep.h drives them - from the split's delimiter bitmap, a wave per
+// The lines are driven as k_text.h drives them - from the split's delimiter bitmap, a wave per
 // 16 KiB chunk, a chunk owning the lines that END in it - so nothing is proportional to the line
 // count or to the record count, and nothing waits for either.  All queued on the caller's stream:
 //   k_split_count / k_split_scan / k_gp_last / k_gp_open   as they stand: the delimiter bitmap,
 //                   bases[chunk], open[chunk], and the HIT bitmap (the selected bitmap's layout) zeroed;
 //   k_ct_count      table staged once per workgroup, a wave per chunk, chunks grid-strided, rounds of
-//                   64 lines as in k_gp_select.  A lane runs the collect chain (collectLane) over its
+//                   64 lines (k_text.h: textLines).  A lane runs the collect chain (collectLane) over its
 //                   line, counts its matches and sets the line's bit in the hit bitmap when it has
 //                   one; matchCounts[chunk] = the wave's sum;
 //   k_split_scan    again, over matchCounts: matchBases[chunk] = records in front of the chunk, and
 //                   the total straight into *n_matches (its thread 0 stores it);
 //   k_ct_write      (skipped when the call only counts) a wave per chunk over the HIT bitmap; chunks
 //                   without a hit, or whose matchBases is at or past the cap, are skipped.  Per round
-//                   of 64 hit lines a lane finds its line's begin / finish / index as k_gp_write
-//                   does, walks the line to count its matches, the wave takes an exclusive prefix of
+//                   of 64 hit lines a lane finds its line's begin / finish / index (k_text.h:
+//                   TextHits), walks the line to count its matches, the wave takes an exclusive prefix of
 //                   the counts (shuffles) plus the carry of the earlier rounds, and the lane walks
 //                   its line again and stores record matchBases[chunk] + prefix + i while that is
 //                   below the cap - the walk ends where the cap does.
@@ -89,19 +89,8 @@ k_ct_count(DevDfa d, const uint8_t *data, GpBufs b) {
   const uint64_t waves = uint64_t(gridDim.x) * (kThreads / 64);
   for (uint64_t ch = uint64_t(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6); ch < b.nChunks;
        ch += waves) {
-    GpChunk g;
-    g.m = gpLoadBits(b.masks, ch, lane);
-    g.scan(lane);
-    const uint64_t base = ch * kSplitChunk;
-    uint64_t begin0 = b.open[ch];  // where the round's first line begins
     uint64_t mine = 0;
-    for (uint32_t k0 = 0; k0 < g.total; k0 += 64) {
-      const uint32_t k = k0 + lane;
-      const bool have = k < g.total;
-      const uint64_t fin = base + g.select(have ? k : g.total - 1);
-      uint64_t beg = __shfl_up(fin, 1) + 1;
-      if (lane == 0) beg = begin0;
-      begin0 = __shfl(fin, 63) + 1;
+    textLines(b, ch, lane, [&](bool have, uint64_t beg, uint64_t fin) {
       if (have) {
         const uint64_t found = collectLane(tab, c, data + beg, fin - beg,
                                            [](uint32_t, uint64_t, uint64_t) { return true; });
@@ -110,7 +99,7 @@ k_ct_count(DevDfa d, const uint8_t *data, GpBufs b) {
           mine += found;
         }
       }
-    }
+    });
     for (int o = 32; o; o >>= 1) mine += __shfl_xor(mine, o);
     if (lane == 0) b.selCounts[ch] = uint32_t(mine);
   }
@@ -135,44 +124,14 @@ k_ct_write(DevDfa d, const uint8_t *data, GpBufs b, CtOut out) {
        ch += waves) {
     const uint64_t first = b.selBases[ch];
     if (first >= out.limit || b.selCounts[ch] == 0) continue;  // (uniform)
-    GpChunk s, g;
-    s.m = gpLoadBits(b.selMasks, ch, lane);
-    s.scan(lane);
-    g.m = gpLoadBits(b.masks, ch, lane);
-    g.scan(lane);
-    // position behind the last delimiter in front of this lane's bits (k_gp_write's)
-    const uint32_t own = g.m.last();
-    uint64_t behind = own ? ch * kSplitChunk + lane * 256u + own : 0;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t v = __shfl_up(behind, o);
-      if (lane >= uint32_t(o) && v > behind) behind = v;
-    }
-    behind = __shfl_up(behind, 1);
-    if (lane == 0) behind = 0;
-    const uint64_t opened = b.open[ch];
-    if (opened > behind) behind = opened;
-    const uint64_t base = ch * kSplitChunk;
+    const TextHits h(b, ch, lane);
     uint64_t carry = first;  // index of the round's first record
-    for (uint32_t k0 = 0; k0 < s.total && carry < out.limit; k0 += 64) {
+    for (uint32_t k0 = 0; k0 < h.s.total && carry < out.limit; k0 += 64) {
       const uint32_t k = k0 + lane;
-      const bool have = k < s.total;
-      const uint32_t pos = s.select(have ? k : s.total - 1);  // the hit line's delimiter
-      // the lane that holds it: the delimiters below it there, and the one just below
-      const uint32_t holder = pos >> 8, inLane = pos & 255u;
-      const GpBits o = gpShflBits(g.m, holder);
-      const uint32_t oExcl = __shfl(g.excl, int(holder));
-      const uint64_t oBehind = __shfl(behind, int(holder));
-      uint32_t rank = 0, prev = 0;  // prev = 1 + the highest delimiter bit below inLane
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const uint32_t lo = uint32_t(64 * w);
-        uint64_t x = o.w[w];
-        if (inLane < lo + 64) x = inLane > lo ? x & ((1ull << (inLane - lo)) - 1) : 0;
-        rank += uint32_t(__popcll(x));
-        if (x) prev = lo + 64 - uint32_t(__clzll(static_cast<long long>(x)));
-      }
-      const uint64_t fin = base + pos;
-      const uint64_t beg = prev ? base + holder * 256u + prev : oBehind;
+      const bool have = k < h.s.total;
+      uint64_t beg, fin;
+      uint32_t index;
+      h.line(h.s.select(have ? k : h.s.total - 1), beg, fin, index);  // the hit line
       // the counting walk, then the lanes' exclusive prefix
       uint64_t cnt = 0;
       if (have)
@@ -186,7 +145,7 @@ k_ct_write(DevDfa d, const uint8_t *data, GpBufs b, CtOut out) {
       uint64_t rec = carry + (incl - cnt);
       carry += __shfl(incl, 63);
       if (cnt && rec < out.limit) {  // (every lane is back at the next round's shuffles)
-        const uint64_t lineNo = b.bases[ch] + oExcl + rank;
+        const uint64_t lineNo = b.bases[ch] + index;
         collectLane(tab, c, data + beg, fin - beg, [&](uint32_t accS, uint64_t mS, uint64_t mE) {
           if (out.line) out.line[rec] = lineNo;
           if (out.begin) out.begin[rec] = beg;
@@ -204,32 +163,27 @@ template <int KIND>
 hipError_t launchCollectTextK(const DevDfa &d, const uint8_t *data, const GpBufs &b,
                               const CtOut &out, bool write, uint64_t *nMatches, uint64_t *matchBases,
                               uint64_t *dummy, const LaunchCfg &cfg, hipStream_t stream) {
-  // threads and resident workgroups by launchGrepK's rule, but for the write pass of the LDS
-  // placements: it holds two chunk views and the prefix beside the chain, and at 1024 threads (128
-  // VGPRs) it spills 22-27 of them (92-112 bytes of private memory per lane), where k_ct_count and
-  // k_gp_select spill none - so it runs 512 threads (158 VGPRs, no spill)
-  constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
-  constexpr int kThreads = kLds ? 1024 : 256;
-  constexpr int kWriteThreads = kLds ? 512 : 256;
+  // threads and resident workgroups by k_text.h's rule (textBlocks), but for the write pass of the
+  // LDS placements: it holds two chunk views and the prefix beside the chain, and at 1024 threads
+  // (128 VGPRs) it spills 22-27 of them (92-112 bytes of private memory per lane), where k_ct_count
+  // and k_gp_select spill none - so it runs 512 threads (158 VGPRs, no spill)
+  constexpr int kThreads = kTextThreads<KIND>;
+  constexpr int kWriteThreads = kTextLds<KIND> ? 512 : 256;
   const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
   hipError_t e = setLds(k_ct_count<KIND, kThreads>, ldsBytes);
   if (e == hipSuccess) e = setLds(k_ct_write<KIND, kWriteThreads>, ldsBytes);
   if (e != hipSuccess) return e;
-  // the table is staged per workgroup: at most one wave of workgroups, a chunk per wave
-  const uint64_t perCu = kLds ? (ldsBytes <= 80 * 1024 ? 2 : 1) : 8;
-  auto blocksOf = [&](uint64_t waves) {
-    const uint64_t blocks = (b.nChunks + waves - 1) / waves;
-    return uint32_t(blocks > uint64_t(cfg.numCUs) * perCu ? uint64_t(cfg.numCUs) * perCu : blocks);
-  };
   if (b.nChunks) {
-    hipLaunchKernelGGL((k_ct_count<KIND, kThreads>), dim3(blocksOf(kThreads / 64)), dim3(kThreads),
+    hipLaunchKernelGGL((k_ct_count<KIND, kThreads>),
+                       dim3(textBlocks<KIND>(b.nChunks, ldsBytes, kThreads, cfg)), dim3(kThreads),
                        ldsBytes, stream, d, data, b);
   }
   // (the scan's total is *n_matches; its offsets[0] store goes to a spare word)
   hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, b.selCounts, b.nChunks,
                      matchBases, nMatches, dummy, uint64_t(0));
   if (write && b.nChunks) {
-    hipLaunchKernelGGL((k_ct_write<KIND, kWriteThreads>), dim3(blocksOf(kWriteThreads / 64)),
+    hipLaunchKernelGGL((k_ct_write<KIND, kWriteThreads>),
+                       dim3(textBlocks<KIND>(b.nChunks, ldsBytes, kWriteThreads, cfg)),
                        dim3(kWriteThreads), ldsBytes, stream, d, data, b, out);
   }
   return hipGetLastError();

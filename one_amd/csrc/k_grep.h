@@ -2,235 +2,27 @@
 // order (include/Red.h:65 "searchInstant() - appropriate for grep"; tools/skim_red.cpp:36-46's loop
 // over the lines lib/Util.cpp:109-130 cuts, search<style,doLeader> of include/Matcher.h:557-640 per
 // line)
-// (included by kernels.hip inside namespace redgpu { namespace { ... } }).
+// (included by kernels.hip inside namespace redgpu { namespace { ... } }, after k_text.h).
 //
-// Lines are never listed: they are driven from the split's delimiter bitmap (k_split.h: one bit per
-// byte, which k_split_count leaves as u16 per 16 bytes in byte order - read here as a plain
-// bitmap), so nothing is proportional to the line count and nothing waits for it.  All queued on the
-// caller's stream:
-//   k_split_count   (k_split.h, as it stands) the delimiter bitmap and counts[chunk];
-//   k_split_scan    (likewise) bases[chunk] = lines that end in front of the chunk, *n_lines;
-//   k_gp_last       per 16 KiB split chunk the position behind its last delimiter (0 = none), and
-//                   the chunk's part of the SELECTED bitmap zeroed;
-//   k_gp_open       one workgroup, an exclusive max-scan of those in place: open[chunk] = where the
-//                   line that is in progress at the chunk's first byte begins (it may begin many
-//                   chunks back);
-//   k_gp_select     table staged once per workgroup, then a WAVE per chunk, chunks grid-strided.
-//                   A chunk owns the lines that END in it.  A lane holds 256 bits of the chunk's
-//                   bitmap (four u64); per round the wave takes the chunk's next 64 delimiters, lane j
-//                   the j-th: it finds the lane that holds it (binary search over the lanes' prefix
-//                   counts, through shuffles), fetches that lane's words, selects the bit; the line
-//                   begins behind the delimiter of the lane below (round 0, lane 0: open[chunk]).
-//                   Registers and shuffles only - no LDS beside the table, so 1 line or 16,384
-//                   lines per chunk differ in the number of rounds (1 .. 256) alone.  The lane walks
-//                   its line (searchLane, or what launchBatch's normalisation makes of it) however
-//                   long it is, and sets the line's bit in the selected bitmap (atomic or, at the
-//                   line's delimiter); selCounts[chunk] = lines selected;
+// The lines are driven from the split's delimiter bitmap (k_text.h), so nothing is proportional to
+// the line count and nothing waits for it.  All queued on the caller's stream:
+//   k_split_count / k_split_scan / k_gp_last / k_gp_open   the line index (k_text.h), and the
+//                   SELECTED bitmap zeroed;
+//   k_gp_select     table staged once per workgroup, then a WAVE per chunk, chunks grid-strided,
+//                   rounds of 64 lines (k_text.h: textLines).  No LDS beside the table.  The lane
+//                   walks its line (searchLane, or what launchBatch's normalisation makes of it)
+//                   however long it is, and sets the line's bit in the selected bitmap (atomic or,
+//                   at the line's delimiter); selCounts[chunk] = lines selected;
 //   k_split_scan    again, over selCounts: selBases[chunk] = records in front of the chunk;
 //   k_gp_total      *n_selected = min(total, max_count);
 //   k_gp_write      (skipped when the call only counts) a wave per chunk again, over the SELECTED
 //                   bitmap; record index = selBases[chunk] + rank, placed when below min(cap,
-//                   max_count); line / begin / finish from the delimiter bitmap (rank and
-//                   predecessor of the bit inside the lane that holds it) and bases / open; the
-//                   Outcome by walking the selected line again - under invert it is (0, 0, 0) and
-//                   nothing is walked.
+//                   max_count); line / begin / finish from the delimiter bitmap (k_text.h:
+//                   TextHits - rank and predecessor of the bit inside the lane that holds it) and
+//                   bases / open; the Outcome by walking the selected line again - under invert it
+//                   is (0, 0, 0) and nothing is walked.
 // No workgroup waits for another: the order of the records comes from the passes.
 #pragma once
-
-// lane context for the lane functions, with the start-byte filters searchLane reads (k_generic's)
-template <int KIND>
-__device__ __forceinline__ LaneCtx gpCtx(const DevDfa &d, uint8_t *lds) {
-  LaneCtx c{lds, lds + 256, resOf<KIND>(d, lds), d.init, d.leaderNext, d.nPureDead, d.firstAccept,
-            d.leaderLen};
-  c.startWord[0] = d.startFreeWord; c.startCount[0] = d.startFreeCount;
-  c.startWord[1] = d.startLeadWord; c.startCount[1] = d.startLeadCount;
-  c.start2Word[0] = d.start2FreeWord; c.start2Count[0] = d.start2FreeCount;
-  c.start2Word[1] = d.start2LeadWord; c.start2Count[1] = d.start2LeadCount;
-  c.suffixClosed = d.suffixClosed;
-  return c;
-}
-
-// the verb launchBatch would run for search over this DFA (normalizeVerbStyle), on one line.
-// match<styLast> goes through matchLastLane's form WITH the exit test for every DFA: k_generic
-// picks the no-exit form (walkAllBytes) under deadAbsorbing && !earlyDeath, which gives the same
-// Outcome (past an absorbing dead end nothing accepts) but needs more registers than a
-// 1024-thread k_gp_select has (137 VGPRs, 40 bytes of private memory per lane when built in)
-template <int VERB, class T>
-__device__ __forceinline__ int32_t gpLine(const T &tab, const LaneCtx &c, const uint8_t *p,
-                                          uint64_t n, int style, bool lead, uint64_t &st,
-                                          uint64_t &en) {
-  if constexpr (VERB == kSearch) return searchLane(tab, c, p, n, style, lead, st, en);
-  else
-    return style == kStyLast ? matchLastLane(tab, c, p, n, lead, st, en)
-                             : matchLane(tab, c, p, n, style, lead, st, en);
-}
-
-// a lane's 256 bits of a chunk's bitmap: bit b of w[k] = byte 256 * lane + 64 * k + b of the chunk
-struct GpBits {
-  uint64_t w[4];
-  __device__ __forceinline__ uint32_t count() const {
-    return __popcll(w[0]) + __popcll(w[1]) + __popcll(w[2]) + __popcll(w[3]);
-  }
-  // 1 + the highest set bit (0 = none)
-  __device__ __forceinline__ uint32_t last() const {
-    uint32_t r = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (w[k]) r = uint32_t(64 * k + 64 - __clzll(static_cast<long long>(w[k])));
-    return r;
-  }
-};
-
-__device__ __forceinline__ GpBits gpLoadBits(const uint16_t *bitmap, uint64_t chunk, uint32_t lane) {
-  // (the bitmap is 16-byte aligned and a chunk has 2048 bytes of it: two aligned 16-byte loads)
-  const uint4 *q = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(bitmap) +
-                                                   chunk * (kSplitChunk / 8) + lane * 32u);
-  const uint4 a = q[0], b = q[1];
-  GpBits r;
-  r.w[0] = uint64_t(a.x) | (uint64_t(a.y) << 32);
-  r.w[1] = uint64_t(a.z) | (uint64_t(a.w) << 32);
-  r.w[2] = uint64_t(b.x) | (uint64_t(b.y) << 32);
-  r.w[3] = uint64_t(b.z) | (uint64_t(b.w) << 32);
-  return r;
-}
-
-__device__ __forceinline__ GpBits gpShflBits(const GpBits &m, uint32_t from) {
-  GpBits r;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t lo = __shfl(uint32_t(m.w[k]), int(from));
-    const uint32_t hi = __shfl(uint32_t(m.w[k] >> 32), int(from));
-    r.w[k] = uint64_t(lo) | (uint64_t(hi) << 32);
-  }
-  return r;
-}
-
-// position of the k-th (0-based) set bit of x, which has more than k
-__device__ __forceinline__ uint32_t gpSelect64(uint64_t x, uint32_t k) {
-  uint32_t pos = 0;
-  uint32_t v = uint32_t(x);
-  uint32_t c = __popc(v);
-  if (k >= c) { k -= c; pos = 32; v = uint32_t(x >> 32); }
-  c = __popc(v & 0xffffu);
-  if (k >= c) { k -= c; pos += 16; v >>= 16; }
-  v &= 0xffffu;
-  c = __popc(v & 0xffu);
-  if (k >= c) { k -= c; pos += 8; v >>= 8; }
-  v &= 0xffu;
-  for (uint32_t i = 0; i < k; ++i) v &= v - 1;  // (at most 7 times)
-  return pos + uint32_t(__ffs(int(v))) - 1;
-}
-
-// position, inside the 256 bits, of their k-th set bit
-__device__ __forceinline__ uint32_t gpSelect256(const GpBits &m, uint32_t k) {
-  uint32_t pos = 0;
-  uint64_t x = m.w[0];
-  bool found = false;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const uint32_t c = __popcll(m.w[i]);
-    if (!found && k >= c) { k -= c; pos = 64 * (i + 1); x = m.w[i + 1]; }
-    else found = true;
-  }
-  return pos + gpSelect64(x, k);
-}
-
-// the wave's view of one chunk's bitmap: every lane's bits, the lanes' exclusive prefix counts
-struct GpChunk {
-  GpBits m;
-  uint32_t excl, total;
-  __device__ __forceinline__ void scan(uint32_t lane) {
-    const uint32_t c = m.count();
-    uint32_t incl = c;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t v = __shfl_up(incl, o);
-      if (lane >= uint32_t(o)) incl += v;
-    }
-    excl = incl - c;
-    total = __shfl(incl, 63);
-  }
-  // chunk-relative position of the chunk's k-th set bit (k < total; every lane calls)
-  __device__ __forceinline__ uint32_t select(uint32_t k) const {
-    // the last lane whose prefix count is <= k
-    uint32_t lo = 0;
-#pragma unroll
-    for (int step = 32; step; step >>= 1) {
-      const uint32_t e = __shfl(excl, int(lo + step));
-      if (e <= k) lo += step;
-    }
-    const uint32_t e = __shfl(excl, int(lo));
-    const GpBits o = gpShflBits(m, lo);
-    return lo * 256u + gpSelect256(o, k - e);
-  }
-};
-
-// per chunk: the position behind its last delimiter (0 = it has none); its selected bits zeroed
-// (selMasks may be null: nothing is zeroed then)
-__global__ void __launch_bounds__(256)
-k_gp_last(const uint16_t *masks, const uint32_t *counts, uint64_t nChunks, uint64_t *open,
-          uint16_t *selMasks) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t waves = uint64_t(gridDim.x) * 4;
-  for (uint64_t ch = uint64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); ch < nChunks; ch += waves) {
-    if (selMasks) {  // (uniform; k_tally_text.h has no selected bitmap)
-      uint4 *z = reinterpret_cast<uint4 *>(reinterpret_cast<uint8_t *>(selMasks) +
-                                           ch * (kSplitChunk / 8) + lane * 32u);
-      z[0] = make_uint4(0, 0, 0, 0);
-      z[1] = make_uint4(0, 0, 0, 0);
-    }
-    uint32_t last = 0;
-    if (counts[ch]) {  // (uniform)
-      const uint32_t mine = gpLoadBits(masks, ch, lane).last();
-      last = mine ? lane * 256u + mine : 0u;
-      for (int o = 32; o; o >>= 1) {
-        const uint32_t v = __shfl_xor(last, o);
-        last = v > last ? v : last;
-      }
-    }
-    if (lane == 0) open[ch] = last ? ch * kSplitChunk + last : 0;
-  }
-}
-
-// one workgroup: open[chunk] = max of the chunks' values in front of it (exclusive, in place):
-// the position behind the last delimiter in front of the chunk
-__global__ void __launch_bounds__(1024) k_gp_open(uint64_t *open, uint64_t nChunks) {
-  __shared__ uint64_t waveMax[2][16];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint64_t carry = 0;
-  int buf = 0;
-  for (uint64_t tile = 0; tile < nChunks; tile += 1024, buf ^= 1) {
-    const uint64_t i = tile + threadIdx.x;
-    const uint64_t own = i < nChunks ? open[i] : 0;
-    uint64_t incl = own;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t v = __shfl_up(incl, o);
-      if (lane >= uint32_t(o) && v > incl) incl = v;
-    }
-    if (lane == 63) waveMax[buf][wave] = incl;
-    __syncthreads();  // (the other buffer is rewritten only after the next tile's barrier)
-    uint64_t before = carry, all = carry;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      const uint64_t v = waveMax[buf][w];
-      if (w < int(wave) && v > before) before = v;
-      if (v > all) all = v;
-    }
-    uint64_t below = __shfl_up(incl, 1);  // the lanes in front of this one, inside the wave
-    if (lane == 0) below = 0;
-    if (i < nChunks) open[i] = below > before ? below : before;
-    carry = all;
-  }
-}
-
-struct GpBufs {
-  const uint16_t *masks;    // the delimiter bitmap (k_split_count)
-  uint16_t *selMasks;       // the selected lines' delimiters, same layout
-  const uint64_t *bases;    // [nChunks] lines that end in front of the chunk
-  const uint64_t *open;     // [nChunks] where the line in progress at the chunk's first byte begins
-  uint32_t *selCounts;      // [nChunks] lines of the chunk that are selected
-  const uint64_t *selBases; // [nChunks] records in front of the chunk
-  uint64_t nChunks;
-};
 
 template <int KIND, int kThreads, int VERB>
 __global__ void __launch_bounds__(kThreads)
@@ -242,19 +34,8 @@ k_gp_select(DevDfa d, const uint8_t *data, GpBufs b, int style, int lead, int in
   const uint64_t waves = uint64_t(gridDim.x) * (kThreads / 64);
   for (uint64_t ch = uint64_t(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6); ch < b.nChunks;
        ch += waves) {
-    GpChunk g;
-    g.m = gpLoadBits(b.masks, ch, lane);
-    g.scan(lane);
-    const uint64_t base = ch * kSplitChunk;
-    uint64_t begin0 = b.open[ch];  // where the round's first line begins
     uint32_t selected = 0;
-    for (uint32_t k0 = 0; k0 < g.total; k0 += 64) {
-      const uint32_t k = k0 + lane;
-      const bool have = k < g.total;
-      const uint64_t fin = base + g.select(have ? k : g.total - 1);
-      uint64_t beg = __shfl_up(fin, 1) + 1;
-      if (lane == 0) beg = begin0;
-      begin0 = __shfl(fin, 63) + 1;
+    textLines(b, ch, lane, [&](bool have, uint64_t beg, uint64_t fin) {
       bool sel = false;
       if (have) {
         uint64_t st, en;
@@ -266,7 +47,7 @@ k_gp_select(DevDfa d, const uint8_t *data, GpBufs b, int style, int lead, int in
         }
       }
       selected += uint32_t(__popcll(__ballot(sel)));
-    }
+    });
     if (lane == 0) b.selCounts[ch] = selected;
   }
 }
@@ -297,46 +78,16 @@ k_gp_write(DevDfa d, const uint8_t *data, GpBufs b, int style, int lead, int wal
        ch += waves) {
     const uint64_t first = b.selBases[ch];
     if (first >= out.limit || b.selCounts[ch] == 0) continue;  // (uniform)
-    GpChunk s, g;
-    s.m = gpLoadBits(b.selMasks, ch, lane);
-    s.scan(lane);
-    g.m = gpLoadBits(b.masks, ch, lane);
-    g.scan(lane);
-    // position behind the last delimiter in front of this lane's bits
-    const uint32_t own = g.m.last();
-    uint64_t behind = own ? ch * kSplitChunk + lane * 256u + own : 0;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t v = __shfl_up(behind, o);
-      if (lane >= uint32_t(o) && v > behind) behind = v;
-    }
-    behind = __shfl_up(behind, 1);
-    if (lane == 0) behind = 0;
-    const uint64_t opened = b.open[ch];
-    if (opened > behind) behind = opened;
-    const uint64_t base = ch * kSplitChunk;
-    for (uint32_t k0 = 0; k0 < s.total && first + k0 < out.limit; k0 += 64) {
+    const TextHits h(b, ch, lane);
+    for (uint32_t k0 = 0; k0 < h.s.total && first + k0 < out.limit; k0 += 64) {
       const uint32_t k = k0 + lane;
-      const bool have = k < s.total;
-      const uint32_t pos = s.select(have ? k : s.total - 1);  // the selected line's delimiter
-      // the lane that holds it: the delimiters below it there, and the one just below
-      const uint32_t holder = pos >> 8, inLane = pos & 255u;
-      const GpBits o = gpShflBits(g.m, holder);
-      const uint32_t oExcl = __shfl(g.excl, int(holder));
-      const uint64_t oBehind = __shfl(behind, int(holder));
-      uint32_t rank = 0, prev = 0;  // prev = 1 + the highest delimiter bit below inLane
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const uint32_t lo = uint32_t(64 * w);
-        uint64_t x = o.w[w];
-        if (inLane < lo + 64) x = inLane > lo ? x & ((1ull << (inLane - lo)) - 1) : 0;
-        rank += uint32_t(__popcll(x));
-        if (x) prev = lo + 64 - uint32_t(__clzll(static_cast<long long>(x)));
-      }
+      const bool have = k < h.s.total;
+      uint64_t beg, fin;
+      uint32_t index;
+      h.line(h.s.select(have ? k : h.s.total - 1), beg, fin, index);  // the selected line
       const uint64_t rec = first + k;
       if (have && rec < out.limit) {  // (every lane is back at the next round's shuffles)
-        const uint64_t fin = base + pos;
-        const uint64_t beg = prev ? base + holder * 256u + prev : oBehind;
-        if (out.line) out.line[rec] = b.bases[ch] + oExcl + rank;
+        if (out.line) out.line[rec] = b.bases[ch] + index;
         if (out.begin) out.begin[rec] = beg;
         if (out.finish) out.finish[rec] = fin;
         int32_t r = 0;
@@ -355,20 +106,15 @@ hipError_t launchGrepK(const DevDfa &d, const uint8_t *data, const GpBufs &b, in
                        int invert, const GpOut &out, bool write, uint64_t *total,
                        uint64_t maxCount, uint64_t *nSelected, uint64_t *selBases,
                        uint64_t *dummy, const LaunchCfg &cfg, hipStream_t stream) {
-  constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
-  constexpr int kThreads = kLds ? 1024 : 256;
-  constexpr uint64_t kWaves = kThreads / 64;
+  constexpr int kThreads = kTextThreads<KIND>;
   const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
   hipError_t e = setLds(k_gp_select<KIND, kThreads, VERB>, ldsBytes);
   if (e == hipSuccess) e = setLds(k_gp_write<KIND, kThreads, VERB>, ldsBytes);
   if (e != hipSuccess) return e;
-  // the table is staged per workgroup: at most one wave of workgroups, a chunk per wave
-  const uint64_t perCu = kLds ? (ldsBytes <= 80 * 1024 ? 2 : 1) : 8;
-  uint64_t blocks = (b.nChunks + kWaves - 1) / kWaves;
-  if (blocks > uint64_t(cfg.numCUs) * perCu) blocks = uint64_t(cfg.numCUs) * perCu;
+  const uint32_t blocks = textBlocks<KIND>(b.nChunks, ldsBytes, kThreads, cfg);
   if (b.nChunks) {
-    hipLaunchKernelGGL((k_gp_select<KIND, kThreads, VERB>), dim3(uint32_t(blocks)), dim3(kThreads),
-                       ldsBytes, stream, d, data, b, style, lead, invert);
+    hipLaunchKernelGGL((k_gp_select<KIND, kThreads, VERB>), dim3(blocks), dim3(kThreads), ldsBytes,
+                       stream, d, data, b, style, lead, invert);
   }
   hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, b.selCounts, b.nChunks, selBases,
                      total, dummy, uint64_t(0));
@@ -376,7 +122,7 @@ hipError_t launchGrepK(const DevDfa &d, const uint8_t *data, const GpBufs &b, in
   if (write && b.nChunks) {
     const bool outcome = out.result || out.start || out.end;
     const int walk = outcome && !invert ? 1 : 0;
-    hipLaunchKernelGGL((k_gp_write<KIND, kThreads, VERB>), dim3(uint32_t(blocks)), dim3(kThreads),
+    hipLaunchKernelGGL((k_gp_write<KIND, kThreads, VERB>), dim3(blocks), dim3(kThreads),
                        walk ? ldsBytes : 0, stream, d, data, b, style, lead, walk, out);
   }
   return hipGetLastError();

@@ -3,13 +3,13 @@
 // loop of tools/skim_red.cpp:36-46 over the lines lib/Util.cpp:109-130 cuts)
 // (included by kernels.hip inside namespace redgpu { namespace { ... } }, after k_grep.h).
 //
-// The lines are driven as k_grep.h drives them - from the split's delimiter bitmap, a wave per
+// The lines are driven as k_text.h drives them - from the split's delimiter bitmap, a wave per
 // 16 KiB chunk, a chunk owning the lines that END in it - so nothing is proportional to the line
 // count, and nothing waits for it.  All queued on the caller's stream:
 //   k_split_count / k_split_scan / k_gp_last / k_gp_open   as they stand: the delimiter bitmap,
 //                   bases[chunk], open[chunk], and the HIT bitmap (the selected bitmap's layout) zeroed;
 //   k_rt_count      table staged once per workgroup, a wave per chunk, chunks grid-strided, rounds of
-//                   64 lines as in k_ct_count.  A lane runs replaceLane without an output over its
+//                   64 lines (k_text.h: textLines).  A lane runs replaceLane without an output over its
 //                   line; outBytes[chunk] = the sum of (rewritten length + 1) over the chunk's lines
 //                   (under only_changed: over its changed lines), replCounts[chunk] = the sum of the
 //                   lines' replacement counts, both u64; a line with a replacement sets its
@@ -21,7 +21,7 @@
 //   k_rt_write      (skipped when the call only sizes) a wave per chunk; chunks without a line or
 //                   with outBases[chunk] >= out_cap are skipped.  The chunk's source is
 //                   [open[chunk], behind its last delimiter).  Per round of 64 HIT lines a lane finds
-//                   its line's begin / finish as k_ct_write does and sizes it again (replaceLane, no
+//                   its line's begin / finish (k_text.h: TextHits) and sizes it again (replaceLane, no
 //                   output); the wave's exclusive prefix over (unchanged bytes in front of the line +
 //                   rewritten length + 1) plus the carry of the earlier rounds places the unchanged
 //                   stretch in front of every hit line and the line itself.  The stretches - and
@@ -59,19 +59,8 @@ k_rt_count(DevDfa d, const uint8_t *data, GpBufs b, RtBufs r, RtArgs a) {
   const uint64_t waves = uint64_t(gridDim.x) * (kThreads / 64);
   for (uint64_t ch = uint64_t(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6); ch < b.nChunks;
        ch += waves) {
-    GpChunk g;
-    g.m = gpLoadBits(b.masks, ch, lane);
-    g.scan(lane);
-    const uint64_t base = ch * kSplitChunk;
-    uint64_t begin0 = b.open[ch];  // where the round's first line begins
     uint64_t bytes = 0, repls = 0;
-    for (uint32_t k0 = 0; k0 < g.total; k0 += 64) {
-      const uint32_t k = k0 + lane;
-      const bool have = k < g.total;
-      const uint64_t fin = base + g.select(have ? k : g.total - 1);
-      uint64_t beg = __shfl_up(fin, 1) + 1;
-      if (lane == 0) beg = begin0;
-      begin0 = __shfl(fin, 63) + 1;
+    textLines(b, ch, lane, [&](bool have, uint64_t beg, uint64_t fin) {
       if (have) {
         uint64_t len = 0;
         const uint64_t cnt = replaceLane(tab, c, data + beg, fin - beg, a.style, a.lead != 0,
@@ -82,7 +71,7 @@ k_rt_count(DevDfa d, const uint8_t *data, GpBufs b, RtBufs r, RtArgs a) {
         }
         if (cnt || !a.onlyChanged) bytes += len + 1;
       }
-    }
+    });
     for (int o = 32; o; o >>= 1) {
       bytes += __shfl_xor(bytes, o);
       repls += __shfl_xor(repls, o);
@@ -176,45 +165,16 @@ k_rt_write(DevDfa d, const uint8_t *data, GpBufs b, RtBufs r, RtArgs a, uint8_t 
        ch += waves) {
     const uint64_t first = r.outBases[ch];
     if (first >= cap || r.outBytes[ch] == 0) continue;  // (uniform; a line gives a byte at least)
-    GpChunk s, g;
-    s.m = gpLoadBits(b.selMasks, ch, lane);
-    s.scan(lane);
-    g.m = gpLoadBits(b.masks, ch, lane);
-    g.scan(lane);
-    // position behind the last delimiter in front of this lane's bits (k_gp_write's), and behind
-    // the chunk's last delimiter: where its source ends
-    const uint32_t own = g.m.last();
-    uint64_t behind = own ? ch * kSplitChunk + lane * 256u + own : 0;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t v = __shfl_up(behind, o);
-      if (lane >= uint32_t(o) && v > behind) behind = v;
-    }
-    const uint64_t srcEnd = __shfl(behind, 63);
-    behind = __shfl_up(behind, 1);
-    if (lane == 0) behind = 0;
-    const uint64_t opened = b.open[ch];
-    if (opened > behind) behind = opened;
-    const uint64_t base = ch * kSplitChunk;
-    uint64_t srcAt = opened;  // the source behind the lines placed so far ...
-    uint64_t dstAt = first;   // ... and where it goes
-    for (uint32_t k0 = 0; k0 < s.total && dstAt < cap; k0 += 64) {
+    // (h.srcEnd, behind the chunk's last delimiter, is where its source ends)
+    const TextHits h(b, ch, lane);
+    uint64_t srcAt = b.open[ch];  // the source behind the lines placed so far ...
+    uint64_t dstAt = first;       // ... and where it goes
+    for (uint32_t k0 = 0; k0 < h.s.total && dstAt < cap; k0 += 64) {
       const uint32_t k = k0 + lane;
-      const bool have = k < s.total;
-      const uint32_t pos = s.select(have ? k : s.total - 1);  // the hit line's delimiter
-      // the lane that holds it, and the delimiter just below it there
-      const uint32_t holder = pos >> 8, inLane = pos & 255u;
-      const GpBits o = gpShflBits(g.m, holder);
-      const uint64_t oBehind = __shfl(behind, int(holder));
-      uint32_t prev = 0;  // 1 + the highest delimiter bit below inLane
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const uint32_t lo = uint32_t(64 * w);
-        uint64_t x = o.w[w];
-        if (inLane < lo + 64) x = inLane > lo ? x & ((1ull << (inLane - lo)) - 1) : 0;
-        if (x) prev = lo + 64 - uint32_t(__clzll(static_cast<long long>(x)));
-      }
-      const uint64_t fin = base + pos;
-      const uint64_t beg = prev ? base + holder * 256u + prev : oBehind;
+      const bool have = k < h.s.total;
+      uint64_t beg, fin;
+      uint32_t index;  // (not needed here)
+      h.line(h.s.select(have ? k : h.s.total - 1), beg, fin, index);  // the hit line
       // the unchanged bytes between the hit line below and this one
       uint64_t gapSrc = __shfl_up(fin, 1) + 1;
       if (lane == 0) gapSrc = srcAt;
@@ -231,7 +191,7 @@ k_rt_write(DevDfa d, const uint8_t *data, GpBufs b, RtBufs r, RtArgs a, uint8_t 
         if (lane >= uint32_t(sh)) incl += v;
       }
       const uint64_t gapDst = dstAt + (incl - mine);
-      const uint32_t lastLane = (s.total - k0 < 64 ? s.total - k0 : 64u) - 1;
+      const uint32_t lastLane = (h.s.total - k0 < 64 ? h.s.total - k0 : 64u) - 1;
       srcAt = __shfl(fin, int(lastLane)) + 1;
       dstAt += __shfl(incl, 63);
       // the stretches, one after the other, by the whole wave
@@ -252,7 +212,7 @@ k_rt_write(DevDfa d, const uint8_t *data, GpBufs b, RtBufs r, RtArgs a, uint8_t 
       }
     }
     // the unchanged lines behind the chunk's last hit line
-    if (!a.onlyChanged) rtCopyWave(out, dstAt, data + srcAt, srcEnd - srcAt, cap, lane);
+    if (!a.onlyChanged) rtCopyWave(out, dstAt, data + srcAt, h.srcEnd - srcAt, cap, lane);
   }
 }
 
@@ -283,27 +243,22 @@ template <int KIND>
 hipError_t launchReplaceTextK(const DevDfa &d, const uint8_t *data, const GpBufs &b,
                               const RtBufs &r, const RtArgs &a, bool count, uint8_t *out,
                               uint64_t cap, const LaunchCfg &cfg, hipStream_t stream) {
-  // threads and resident workgroups by launchCollectTextK's rule: the count pass as k_ct_count,
+  // threads and resident workgroups by k_text.h's rule (textBlocks): the count pass as k_ct_count,
   // the write pass - two chunk views, the prefix and the stretch beside replaceCore - at 512
   // threads under the LDS placements so that it does not spill (DESIGN 4.3h has the report)
-  constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
-  constexpr int kThreads = kLds ? 1024 : 256;
-  constexpr int kWriteThreads = kLds ? 512 : 256;
+  constexpr int kThreads = kTextThreads<KIND>;
+  constexpr int kWriteThreads = kTextLds<KIND> ? 512 : 256;
   const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
   hipError_t e = setLds(k_rt_count<KIND, kThreads>, ldsBytes);
   if (e == hipSuccess) e = setLds(k_rt_write<KIND, kWriteThreads>, ldsBytes);
   if (e != hipSuccess) return e;
-  // the table is staged per workgroup: at most one wave of workgroups, a chunk per wave
-  const uint64_t perCu = kLds ? (ldsBytes <= 80 * 1024 ? 2 : 1) : 8;
-  auto blocksOf = [&](uint64_t waves) {
-    const uint64_t blocks = (b.nChunks + waves - 1) / waves;
-    return uint32_t(blocks > uint64_t(cfg.numCUs) * perCu ? uint64_t(cfg.numCUs) * perCu : blocks);
-  };
   if (count) {
-    hipLaunchKernelGGL((k_rt_count<KIND, kThreads>), dim3(blocksOf(kThreads / 64)), dim3(kThreads),
+    hipLaunchKernelGGL((k_rt_count<KIND, kThreads>),
+                       dim3(textBlocks<KIND>(b.nChunks, ldsBytes, kThreads, cfg)), dim3(kThreads),
                        ldsBytes, stream, d, data, b, r, a);
   } else {
-    hipLaunchKernelGGL((k_rt_write<KIND, kWriteThreads>), dim3(blocksOf(kWriteThreads / 64)),
+    hipLaunchKernelGGL((k_rt_write<KIND, kWriteThreads>),
+                       dim3(textBlocks<KIND>(b.nChunks, ldsBytes, kWriteThreads, cfg)),
                        dim3(kWriteThreads), ldsBytes, stream, d, data, b, r, a, out, cap);
   }
   return hipGetLastError();

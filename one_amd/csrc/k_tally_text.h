@@ -5,13 +5,13 @@
 // (included by kernels.hip inside namespace redgpu { namespace { ... } }, after k_collect_text.h;
 // DESIGN 4.3i).
 //
-// The lines are driven as k_grep.h drives them - from the split's delimiter bitmap, a wave per
+// The lines are driven as k_text.h drives them - from the split's delimiter bitmap, a wave per
 // 16 KiB chunk, a chunk owning the lines that END in it.  All queued on the caller's stream:
 //   k_split_count / k_split_scan / k_gp_last / k_gp_open   as they stand: the delimiter bitmap,
 //                   bases[chunk] (unused here), open[chunk]; no selected / hit bitmap exists;
 //   k_tl_zero       the caller's bins zeroed (not under accumulate) and the item count zeroed;
 //   k_tally_text    ONE pass: table staged once per workgroup, a wave per chunk, chunks
-//                   grid-strided, rounds of 64 lines as in k_ct_count / k_gp_select.  A lane runs
+//                   grid-strided, rounds of 64 lines (k_text.h: textLines).  A lane runs
 //                   gpLine<VERB> (LINES: one item per line, its value the line's result) or
 //                   collectLane (MATCHES: one item per match) and counts its items by value.
 // The histogram: bins [0, L) are 32-bit counters in LDS behind the table (where k_scan_marked and
@@ -42,12 +42,11 @@ struct TallyOut {
   uint32_t ldsBins;            // L: the bins kept in LDS
 };
 
-// the resident workgroups launchCollectTextK's rule gives k_ct_count for this DFA, and the LDS a
+// the resident workgroups k_text.h's rule (textPerCu) gives k_ct_count for this DFA, and the LDS a
 // workgroup may take without lowering them
 template <int KIND>
 __host__ inline uint64_t tallyPerCu(const DevDfa &d) {
-  constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
-  return kLds ? (512 + ldsTableBytes<KIND>(d) <= 80 * 1024 ? 2 : 1) : 8;
+  return textPerCu<KIND>(512 + ldsTableBytes<KIND>(d));
 }
 
 // where the counters begin, and what follows them: 16 bytes (the workgroup's item count)
@@ -140,18 +139,7 @@ k_tally_text(DevDfa d, const uint8_t *data, GpBufs b, int style, int lead, int p
   uint64_t zeros = 0;  // LINES: the wave's lines of value 0 (uniform)
   for (uint64_t ch = uint64_t(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6); ch < b.nChunks;
        ch += waves) {
-    GpChunk g;
-    g.m = gpLoadBits(b.masks, ch, lane);
-    g.scan(lane);
-    const uint64_t base = ch * kSplitChunk;
-    uint64_t begin0 = b.open[ch];  // where the round's first line begins
-    for (uint32_t k0 = 0; k0 < g.total; k0 += 64) {
-      const uint32_t k = k0 + lane;
-      const bool have = k < g.total;
-      const uint64_t fin = base + g.select(have ? k : g.total - 1);
-      uint64_t beg = __shfl_up(fin, 1) + 1;
-      if (lane == 0) beg = begin0;
-      begin0 = __shfl(fin, 63) + 1;
+    textLines(b, ch, lane, [&](bool have, uint64_t beg, uint64_t fin) {
       if constexpr (MODE == kTallyMatches) {
         int32_t runVal = 0;
         uint32_t run = 0;
@@ -185,7 +173,7 @@ k_tally_text(DevDfa d, const uint8_t *data, GpBufs b, int style, int lead, int p
           tallyWave<true>(o, hist, lane, have && r != 0, r, 1u);
         }
       }
-    }
+    });
   }
   if (MODE != kTallyMatches && !plain && lane == 0 && zeros) {
     // value 0 lands in slot 0 whatever nBins is (nBins == 0: slot 0 IS "everything else"); the
@@ -206,18 +194,15 @@ k_tally_text(DevDfa d, const uint8_t *data, GpBufs b, int style, int lead, int p
 template <int KIND, int MODE>
 hipError_t launchTallyK(const DevDfa &d, const uint8_t *data, const GpBufs &b, int style, int lead,
                         int plain, const TallyOut &o, const LaunchCfg &cfg, hipStream_t stream) {
-  // threads and resident workgroups by launchCollectTextK's rule for k_ct_count; the counters fit
-  // in what that rule leaves of the LDS (tallyLdsBinsK), so the rule holds here as well
-  constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
-  constexpr int kThreads = kLds ? 1024 : 256;
+  // threads and resident workgroups by k_text.h's rule (textBlocks) for k_ct_count's LDS; the
+  // counters fit in what that rule leaves of the LDS (tallyLdsBinsK), so the rule holds here as well
+  constexpr int kThreads = kTextThreads<KIND>;
   const size_t ldsBytes = tallyLdsOff<KIND>(d) + ((size_t(o.ldsBins) * 4 + 15) & ~size_t(15)) + 16;
   const hipError_t e = setLds(k_tally_text<KIND, kThreads, MODE>, ldsBytes);
   if (e != hipSuccess) return e;
-  // the table is staged per workgroup: at most one wave of workgroups, a chunk per wave
-  const uint64_t perCu = tallyPerCu<KIND>(d), waves = kThreads / 64;
-  uint64_t blocks = (b.nChunks + waves - 1) / waves;
-  if (blocks > uint64_t(cfg.numCUs) * perCu) blocks = uint64_t(cfg.numCUs) * perCu;
-  hipLaunchKernelGGL((k_tally_text<KIND, kThreads, MODE>), dim3(uint32_t(blocks)), dim3(kThreads),
-                     ldsBytes, stream, d, data, b, style, lead, plain, o);
+  const uint32_t blocks =
+      textBlocks<KIND>(b.nChunks, 512 + ldsTableBytes<KIND>(d), kThreads, cfg);
+  hipLaunchKernelGGL((k_tally_text<KIND, kThreads, MODE>), dim3(blocks), dim3(kThreads), ldsBytes,
+                     stream, d, data, b, style, lead, plain, o);
   return hipGetLastError();
 }

@@ -192,6 +192,14 @@ hipError_t launchSplitLines(const uint8_t *data, uint64_t len, uint8_t delim, ui
                             uint64_t cap, uint64_t *nLines, uint32_t *counts, uint64_t *bases,
                             uint16_t *masks, hipStream_t stream);
 
+// The line index of the raw-text verbs (k_text.h): launchSplitLines' count and scan without the
+// scatter (counts, bases, masks as there; *nLines, or spare[0] when nLines is null), then
+// open[chunk] = where the line in progress at the chunk's first byte begins (uint64[splitChunks(len)])
+// and, unless zeroMasks is null, a second bitmap of masks' size zeroed.  spare: uint64[2].
+hipError_t launchTextIndex(const uint8_t *data, uint64_t len, uint8_t delim, uint64_t *nLines,
+                           uint32_t *counts, uint64_t *bases, uint16_t *masks, uint64_t *open,
+                           uint16_t *zeroMasks, uint64_t *spare, int numCUs, hipStream_t stream);
+
 // grep over a raw text (k_grep.h): the lines of launchSplitLines' rule that search<style, doLeader>
 // selects (result > 0, or the others under invert), as records in text order: *nSelected =
 // min(selected, maxCount), the first min(*nSelected, cap) records in line / begin / finish /

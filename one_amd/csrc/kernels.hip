@@ -38,6 +38,8 @@
 //   k_style_blocks.h  k_style_blocks: early-exit styles and odd strides over the block walk
 //   k_misc.h          k_advance, k_replace (+ scan), k_visits, k_walked
 //   k_split.h         line splitting on the device
+//   k_text.h          what the raw-text verbs share: the bitmap views, the line index (k_gp_last,
+//                     k_gp_open), the line walk, the hit-line lookup, launch geometry, scratch cursor
 //   k_grep.h          k_gp_*: grep over a raw text - the split's delimiter bitmap drives the lines,
 //                     a wave per 16 KiB chunk selects, a scan orders, a second pass writes records
 //   k_collect_text.h  k_ct_*: grep -o over a raw text - k_grep.h's line driver, Red::collect per line,
@@ -75,6 +77,18 @@
 #define REDGPU_TU_REPLACE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 6)
 #define REDGPU_TU_TALLY_TEXT (REDGPU_TU == 0 || REDGPU_TU == 7)
 
+// return CALL(KIND) for the table kind of the DevDfa `d` in scope: a launcher's instantiation per kind
+#define REDGPU_KIND_SWITCH(CALL)                                                          \
+  switch (d.tableKind) {                                                                  \
+  case REDGPU_TAB_LDS_FUSED_U8: return CALL(REDGPU_TAB_LDS_FUSED_U8);                     \
+  case REDGPU_TAB_LDS_FUSED_U16: return CALL(REDGPU_TAB_LDS_FUSED_U16);                   \
+  case REDGPU_TAB_LDS_CLASS_U16: return CALL(REDGPU_TAB_LDS_CLASS_U16);                   \
+  case REDGPU_TAB_GLOBAL_U16: return CALL(REDGPU_TAB_GLOBAL_U16);                         \
+  case REDGPU_TAB_HOT_ROWS: return CALL(REDGPU_TAB_HOT_ROWS);                               \
+  case REDGPU_TAB_LDS_SPARSE: return CALL(REDGPU_TAB_LDS_SPARSE);                         \
+  default: return CALL(REDGPU_TAB_GLOBAL_U32);                                            \
+  }
+
 namespace redgpu {
 
 namespace {
@@ -99,6 +113,7 @@ namespace {
 #include "k_split.h"
 #include "k_diag.h"
 #include "launchers.h"
+#include "k_text.h"
 #include "k_grep.h"
 #include "k_collect_text.h"
 #include "k_tally_text.h"
@@ -489,34 +504,10 @@ hipError_t launchRaggedFamily(const DevDfa &d, const Batch &b, int verb, int sty
 hipError_t launchCollect(const DevDfa &d, const Batch &b, uint64_t cap, uint64_t *counts,
                          const LaunchCfg &cfg, hipStream_t stream) {
   if (b.n == 0) return hipSuccess;
-  switch (d.tableKind) {
-  case REDGPU_TAB_LDS_FUSED_U8:
-    return launchCollectK<REDGPU_TAB_LDS_FUSED_U8>(d, b, cap, counts, cfg, stream);
-  case REDGPU_TAB_LDS_FUSED_U16:
-    return launchCollectK<REDGPU_TAB_LDS_FUSED_U16>(d, b, cap, counts, cfg, stream);
-  case REDGPU_TAB_LDS_CLASS_U16:
-    return launchCollectK<REDGPU_TAB_LDS_CLASS_U16>(d, b, cap, counts, cfg, stream);
-  case REDGPU_TAB_GLOBAL_U16:
-    return launchCollectK<REDGPU_TAB_GLOBAL_U16>(d, b, cap, counts, cfg, stream);
-  case REDGPU_TAB_HOT_ROWS:
-    return launchCollectK<REDGPU_TAB_HOT_ROWS>(d, b, cap, counts, cfg, stream);
-  case REDGPU_TAB_LDS_SPARSE:
-    return launchCollectK<REDGPU_TAB_LDS_SPARSE>(d, b, cap, counts, cfg, stream);
-  default:
-    return launchCollectK<REDGPU_TAB_GLOBAL_U32>(d, b, cap, counts, cfg, stream);
-  }
+#define CO_CALL(K) launchCollectK<K>(d, b, cap, counts, cfg, stream)
+  REDGPU_KIND_SWITCH(CO_CALL)
+#undef CO_CALL
 }
-
-#define REDGPU_KIND_SWITCH(CALL)                                                          \
-  switch (d.tableKind) {                                                                  \
-  case REDGPU_TAB_LDS_FUSED_U8: return CALL(REDGPU_TAB_LDS_FUSED_U8);                     \
-  case REDGPU_TAB_LDS_FUSED_U16: return CALL(REDGPU_TAB_LDS_FUSED_U16);                   \
-  case REDGPU_TAB_LDS_CLASS_U16: return CALL(REDGPU_TAB_LDS_CLASS_U16);                   \
-  case REDGPU_TAB_GLOBAL_U16: return CALL(REDGPU_TAB_GLOBAL_U16);                         \
-  case REDGPU_TAB_HOT_ROWS: return CALL(REDGPU_TAB_HOT_ROWS);                               \
-  case REDGPU_TAB_LDS_SPARSE: return CALL(REDGPU_TAB_LDS_SPARSE);                         \
-  default: return CALL(REDGPU_TAB_GLOBAL_U32);                                            \
-  }
 
 // Red::collect over one text (k_collect_long.h): the chunked chain, the suffix-closed route or
 // the one-lane k_collect - the same records either way.
@@ -795,11 +786,16 @@ uint64_t splitChunks(uint64_t len) { return (len + kSplitChunk - 1) / kSplitChun
 
 uint64_t splitMaskBytes(uint64_t len) { return splitChunks(len) * (kSplitChunk / 8); }
 
+// the grid of k_split_count and k_split_scatter: a workgroup takes kSplitGroup chunks
+static uint32_t splitGroups(uint64_t nChunks) {
+  return uint32_t((nChunks + kSplitGroup - 1) / kSplitGroup);
+}
+
 hipError_t launchSplitLines(const uint8_t *data, uint64_t len, uint8_t delim, uint64_t *offsets,
                             uint64_t cap, uint64_t *nLines, uint32_t *counts, uint64_t *bases,
                             uint16_t *masks, hipStream_t stream) {
   const uint64_t nChunks = splitChunks(len);
-  const uint32_t groups = uint32_t((nChunks + kSplitGroup - 1) / kSplitGroup);
+  const uint32_t groups = splitGroups(nChunks);
   if (nChunks)
     hipLaunchKernelGGL(k_split_count, dim3(groups), dim3(kSplitThreads), 0, stream, data, len,
                        uint32_t(delim), nChunks, counts, masks);
@@ -808,6 +804,27 @@ hipError_t launchSplitLines(const uint8_t *data, uint64_t len, uint8_t delim, ui
   if (nChunks)
     hipLaunchKernelGGL(k_split_scatter, dim3(groups), dim3(kSplitThreads), 0, stream, masks,
                        nChunks, bases, offsets, cap);
+  return hipGetLastError();
+}
+
+hipError_t launchTextIndex(const uint8_t *data, uint64_t len, uint8_t delim, uint64_t *nLines,
+                           uint32_t *counts, uint64_t *bases, uint16_t *masks, uint64_t *open,
+                           uint16_t *zeroMasks, uint64_t *spare, int numCUs, hipStream_t stream) {
+  const uint64_t nChunks = splitChunks(len);
+  if (nChunks) {
+    hipLaunchKernelGGL(k_split_count, dim3(splitGroups(nChunks)), dim3(kSplitThreads), 0, stream,
+                       data, len, uint32_t(delim), nChunks, counts, masks);
+  }
+  // (k_split_scan's offsets[0] store goes to a spare word)
+  hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, counts, nChunks, bases,
+                     nLines ? nLines : spare, spare + 1, uint64_t(0));
+  if (nChunks) {
+    uint64_t small = (nChunks + 3) / 4;
+    if (small > uint64_t(numCUs) * 8) small = uint64_t(numCUs) * 8;
+    hipLaunchKernelGGL(k_gp_last, dim3(uint32_t(small)), dim3(256), 0, stream, masks, counts,
+                       nChunks, open, zeroMasks);
+    hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, open, nChunks);
+  }
   return hipGetLastError();
 }
 
@@ -916,13 +933,35 @@ hipError_t launchAdvance(const DevDfa &d, const Batch &b, uint32_t *state, const
     style = kStyLast;
 }
 
+#if REDGPU_TU_GREP || REDGPU_TU_COLLECT_TEXT
+// the scratch of grep and of grep -o, for a text of nChunks split chunks: what launchTextIndex
+// fills, a count and a base per chunk for the records, four spare words, the two bitmaps
+struct RecordScratch {
+  uint64_t *bases, *open, *recBases;  // [nChunks] each
+  uint32_t *counts, *recCounts;       // [nChunks] each
+  uint64_t *misc;                     // [4]: lines, the scans' spare word, two of the verb's
+  uint16_t *masks, *hitMasks;         // the delimiter bitmap, the selected / hit bitmap
+  uint64_t bytes;
+  RecordScratch(void *scratch, uint64_t nChunks) {
+    Carve c{static_cast<uint8_t *>(scratch)};
+    bases = c.take<uint64_t>(nChunks);
+    open = c.take<uint64_t>(nChunks);
+    recBases = c.take<uint64_t>(nChunks);
+    counts = c.take<uint32_t>(nChunks);
+    recCounts = c.take<uint32_t>(nChunks);
+    misc = c.take<uint64_t>(4);
+    c.align(16);
+    masks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    hitMasks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    bytes = c.at;
+  }
+};
+#endif
+
 #if REDGPU_TU_GREP
-// grep over a raw text (k_grep.h): the split's count and scan as they stand, then the k_gp_* passes.
+// grep over a raw text (k_grep.h): the line index (launchTextIndex), then the k_gp_* passes.
 // scratch: grepScratchBytes(len) bytes, 16-byte aligned.
-uint64_t grepScratchBytes(uint64_t len) {
-  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
-  return nChunks * 32 + 32 + 2 * nChunks * (kSplitChunk / 8);
-}
+uint64_t grepScratchBytes(uint64_t len) { return RecordScratch(nullptr, splitChunks(len)).bytes; }
 
 hipError_t launchGrepText(const DevDfa &d, int style, int doLeader, int invert, const uint8_t *data,
                           uint64_t len, uint8_t delim, uint64_t maxCount, uint64_t cap,
@@ -931,66 +970,33 @@ hipError_t launchGrepText(const DevDfa &d, int style, int doLeader, int invert, 
                           void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                           const char **kernelName) {
   *kernelName = "k_grep_text";
-  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
-  // [bases, open, selBases: u64[nChunks] each][counts, selCounts: u32[nChunks] each]
-  // [lines, total, dummy: u64, 8 spare][delimiter bitmap][selected bitmap]
-  uint8_t *q = static_cast<uint8_t *>(scratch);
-  uint64_t *bases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint64_t *open = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint64_t *selBases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint32_t *counts = reinterpret_cast<uint32_t *>(q); q += nChunks * 4;
-  uint32_t *selCounts = reinterpret_cast<uint32_t *>(q); q += nChunks * 4;
-  uint64_t *misc = reinterpret_cast<uint64_t *>(q); q += 32;
-  uint16_t *masks = reinterpret_cast<uint16_t *>(q); q += nChunks * (kSplitChunk / 8);
-  uint16_t *selMasks = reinterpret_cast<uint16_t *>(q);
-  uint64_t *total = misc + 1, *dummy = misc + 2;
-  if (nChunks) {
-    hipLaunchKernelGGL(k_split_count, dim3(uint32_t(nChunks)), dim3(kSplitThreads), 0, stream, data,
-                       len, uint32_t(delim), nChunks, counts, masks);
-  }
-  // (k_split_scan's offsets[0] store goes to a spare word)
-  hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, counts, nChunks, bases,
-                     nLines ? nLines : misc, dummy, uint64_t(0));
-  if (nChunks) {
-    uint64_t small = (nChunks + 3) / 4;
-    if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
-    hipLaunchKernelGGL(k_gp_last, dim3(uint32_t(small)), dim3(256), 0, stream, masks, counts,
-                       nChunks, open, selMasks);
-    hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, open, nChunks);
-  }
-  hipError_t e = hipGetLastError();
+  const uint64_t nChunks = splitChunks(len);
+  const RecordScratch m(scratch, nChunks);
+  uint64_t *dummy = m.misc + 1, *total = m.misc + 2;
+  const hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                       m.hitMasks, m.misc, cfg.numCUs, stream);
   if (e != hipSuccess) return e;
   const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
   int verb = kSearch;
   normalizeVerbStyle(d, cfg, lead != 0, verb, style);
-  const GpBufs b{masks, selMasks, bases, open, selCounts, selBases, nChunks};
+  const GpBufs b{m.masks, m.hitMasks, m.bases, m.open, m.recCounts, m.recBases, nChunks};
   const GpOut out{cap < maxCount ? cap : maxCount, line, begin, finish, result, start, end};
   const bool write = out.limit > 0 && (line || begin || finish || result || start || end);
-#define GP_ARGS d, data, b, style, lead, invert, out, write, total, maxCount, nSelected, selBases, \
+#define GP_ARGS d, data, b, style, lead, invert, out, write, total, maxCount, nSelected, m.recBases, \
                 dummy, cfg, stream
 #define GP_CALL(K) \
   (verb == kSearch ? launchGrepK<K, kSearch>(GP_ARGS) : launchGrepK<K, kMatch>(GP_ARGS))
-  switch (d.tableKind) {
-  case REDGPU_TAB_LDS_FUSED_U8: return GP_CALL(REDGPU_TAB_LDS_FUSED_U8);
-  case REDGPU_TAB_LDS_FUSED_U16: return GP_CALL(REDGPU_TAB_LDS_FUSED_U16);
-  case REDGPU_TAB_LDS_CLASS_U16: return GP_CALL(REDGPU_TAB_LDS_CLASS_U16);
-  case REDGPU_TAB_GLOBAL_U16: return GP_CALL(REDGPU_TAB_GLOBAL_U16);
-  case REDGPU_TAB_HOT_ROWS: return GP_CALL(REDGPU_TAB_HOT_ROWS);
-  case REDGPU_TAB_LDS_SPARSE: return GP_CALL(REDGPU_TAB_LDS_SPARSE);
-  default: return GP_CALL(REDGPU_TAB_GLOBAL_U32);
-  }
+  REDGPU_KIND_SWITCH(GP_CALL)
 #undef GP_CALL
 #undef GP_ARGS
 }
 #endif  // REDGPU_TU_GREP
 
 #if REDGPU_TU_COLLECT_TEXT
-// grep -o over a raw text (k_collect_text.h): the split's count and scan and grep's k_gp_last /
-// k_gp_open as they stand, then the k_ct_* passes.  scratch: collectTextScratchBytes(len) bytes,
-// 16-byte aligned - what grep takes: two bitmaps and 32 bytes per chunk.
+// grep -o over a raw text (k_collect_text.h): the line index (launchTextIndex), then the k_ct_*
+// passes.  scratch: collectTextScratchBytes(len) bytes, 16-byte aligned - what grep takes.
 uint64_t collectTextScratchBytes(uint64_t len) {
-  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
-  return nChunks * 32 + 32 + 2 * nChunks * (kSplitChunk / 8);
+  return RecordScratch(nullptr, splitChunks(len)).bytes;
 }
 
 hipError_t launchCollectText(const DevDfa &d, const uint8_t *data, uint64_t len, uint8_t delim,
@@ -999,72 +1005,48 @@ hipError_t launchCollectText(const DevDfa &d, const uint8_t *data, uint64_t len,
                              void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                              const char **kernelName) {
   *kernelName = "k_collect_text";
-  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
-  // [bases, open, matchBases: u64[nChunks] each][counts, matchCounts: u32[nChunks] each]
-  // [lines, dummy: u64, 16 spare][delimiter bitmap][hit bitmap]
-  uint8_t *q = static_cast<uint8_t *>(scratch);
-  uint64_t *bases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint64_t *open = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint64_t *matchBases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint32_t *counts = reinterpret_cast<uint32_t *>(q); q += nChunks * 4;
-  uint32_t *matchCounts = reinterpret_cast<uint32_t *>(q); q += nChunks * 4;
-  uint64_t *misc = reinterpret_cast<uint64_t *>(q); q += 32;
-  uint16_t *masks = reinterpret_cast<uint16_t *>(q); q += nChunks * (kSplitChunk / 8);
-  uint16_t *hitMasks = reinterpret_cast<uint16_t *>(q);
-  uint64_t *dummy = misc + 1;
-  if (nChunks) {
-    hipLaunchKernelGGL(k_split_count, dim3(uint32_t(nChunks)), dim3(kSplitThreads), 0, stream, data,
-                       len, uint32_t(delim), nChunks, counts, masks);
-  }
-  // (k_split_scan's offsets[0] store goes to a spare word)
-  hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, counts, nChunks, bases,
-                     nLines ? nLines : misc, dummy, uint64_t(0));
-  if (nChunks) {
-    uint64_t small = (nChunks + 3) / 4;
-    if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
-    hipLaunchKernelGGL(k_gp_last, dim3(uint32_t(small)), dim3(256), 0, stream, masks, counts,
-                       nChunks, open, hitMasks);
-    hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, open, nChunks);
-  }
-  hipError_t e = hipGetLastError();
+  const uint64_t nChunks = splitChunks(len);
+  const RecordScratch m(scratch, nChunks);
+  uint64_t *dummy = m.misc + 1;
+  const hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                       m.hitMasks, m.misc, cfg.numCUs, stream);
   if (e != hipSuccess) return e;
-  const GpBufs b{masks, hitMasks, bases, open, matchCounts, matchBases, nChunks};
+  const GpBufs b{m.masks, m.hitMasks, m.bases, m.open, m.recCounts, m.recBases, nChunks};
   const CtOut out{cap, line, begin, result, start, end};
   const bool write = cap > 0 && (line || begin || result || start || end);
 #define CT_CALL(K) \
-  launchCollectTextK<K>(d, data, b, out, write, nMatches, matchBases, dummy, cfg, stream)
-  switch (d.tableKind) {
-  case REDGPU_TAB_LDS_FUSED_U8: return CT_CALL(REDGPU_TAB_LDS_FUSED_U8);
-  case REDGPU_TAB_LDS_FUSED_U16: return CT_CALL(REDGPU_TAB_LDS_FUSED_U16);
-  case REDGPU_TAB_LDS_CLASS_U16: return CT_CALL(REDGPU_TAB_LDS_CLASS_U16);
-  case REDGPU_TAB_GLOBAL_U16: return CT_CALL(REDGPU_TAB_GLOBAL_U16);
-  case REDGPU_TAB_HOT_ROWS: return CT_CALL(REDGPU_TAB_HOT_ROWS);
-  case REDGPU_TAB_LDS_SPARSE: return CT_CALL(REDGPU_TAB_LDS_SPARSE);
-  default: return CT_CALL(REDGPU_TAB_GLOBAL_U32);
-  }
+  launchCollectTextK<K>(d, data, b, out, write, nMatches, m.recBases, dummy, cfg, stream)
+  REDGPU_KIND_SWITCH(CT_CALL)
 #undef CT_CALL
 }
 #endif  // REDGPU_TU_COLLECT_TEXT
 
 #if REDGPU_TU_TALLY_TEXT
-// grep -c per result over a raw text (k_tally_text.h): the split's count and scan and grep's
-// k_gp_last / k_gp_open as they stand, then k_tl_zero and the one pass of k_tally_text.  scratch:
-// tallyTextScratchBytes(len) bytes, 16-byte aligned: ONE bitmap and 20 bytes per chunk.
-uint64_t tallyTextScratchBytes(uint64_t len) {
-  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
-  return nChunks * 16 + 32 + nChunks * (kSplitChunk / 8) + ((nChunks * 4 + 15) & ~uint64_t(15));
-}
-
-#define TL_KINDS(F)                                                       \
-  switch (tableKind) {                                                    \
-  case REDGPU_TAB_LDS_FUSED_U8: return F(REDGPU_TAB_LDS_FUSED_U8);        \
-  case REDGPU_TAB_LDS_FUSED_U16: return F(REDGPU_TAB_LDS_FUSED_U16);      \
-  case REDGPU_TAB_LDS_CLASS_U16: return F(REDGPU_TAB_LDS_CLASS_U16);      \
-  case REDGPU_TAB_GLOBAL_U16: return F(REDGPU_TAB_GLOBAL_U16);            \
-  case REDGPU_TAB_HOT_ROWS: return F(REDGPU_TAB_HOT_ROWS);                \
-  case REDGPU_TAB_LDS_SPARSE: return F(REDGPU_TAB_LDS_SPARSE);            \
-  default: return F(REDGPU_TAB_GLOBAL_U32);                               \
+// grep -c per result over a raw text (k_tally_text.h): the line index (launchTextIndex), then
+// k_tl_zero and the one pass of k_tally_text.  scratch: tallyTextScratchBytes(len) bytes, 16-byte
+// aligned: ONE bitmap and 20 bytes per chunk.
+struct TallyScratch {
+  uint64_t *bases, *open;  // [nChunks] each
+  uint64_t *misc;          // [4]: lines, the scan's spare word, items, one spare
+  uint16_t *masks;         // the delimiter bitmap
+  uint32_t *counts;        // [nChunks]
+  uint64_t bytes;
+  TallyScratch(void *scratch, uint64_t nChunks) {
+    Carve c{static_cast<uint8_t *>(scratch)};
+    bases = c.take<uint64_t>(nChunks);
+    open = c.take<uint64_t>(nChunks);
+    misc = c.take<uint64_t>(4);
+    c.align(16);
+    masks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    counts = c.take<uint32_t>(nChunks);
+    c.align(16);
+    bytes = c.at;
   }
+};
+
+uint64_t tallyTextScratchBytes(uint64_t len) {
+  return TallyScratch(nullptr, splitChunks(len)).bytes;
+}
 
 uint32_t tallyLdsBins(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates) {
   DevDfa d{};
@@ -1072,7 +1054,7 @@ uint32_t tallyLdsBins(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates)
   d.tableBytes = tableBytes;
   d.nStates = nStates;
 #define TL_BINS(K) tallyLdsBinsK<K>(d)
-  TL_KINDS(TL_BINS)
+  REDGPU_KIND_SWITCH(TL_BINS)
 #undef TL_BINS
 }
 
@@ -1081,39 +1063,21 @@ hipError_t launchTallyText(const DevDfa &d, int what, int style, int doLeader, c
                            uint64_t *nLines, uint64_t *nItems, uint64_t *bins, void *scratch,
                            const LaunchCfg &cfg, hipStream_t stream, const char **kernelName) {
   *kernelName = "k_tally_text";
-  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
-  // [bases, open: u64[nChunks] each][lines, dummy, items: u64, 8 spare][delimiter bitmap]
-  // [counts: u32[nChunks]]
-  uint8_t *q = static_cast<uint8_t *>(scratch);
-  uint64_t *bases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint64_t *open = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint64_t *misc = reinterpret_cast<uint64_t *>(q); q += 32;
-  uint16_t *masks = reinterpret_cast<uint16_t *>(q); q += nChunks * (kSplitChunk / 8);
-  uint32_t *counts = reinterpret_cast<uint32_t *>(q);
-  uint64_t *dummy = misc + 1;
-  if (nChunks) {
-    hipLaunchKernelGGL(k_split_count, dim3(uint32_t(nChunks)), dim3(kSplitThreads), 0, stream, data,
-                       len, uint32_t(delim), nChunks, counts, masks);
-  }
-  // (k_split_scan's offsets[0] store goes to a spare word)
-  hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, counts, nChunks, bases,
-                     nLines ? nLines : misc, dummy, uint64_t(0));
-  if (nChunks) {
-    uint64_t small = (nChunks + 3) / 4;
-    if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
-    // (no selected bitmap to zero)
-    hipLaunchKernelGGL(k_gp_last, dim3(uint32_t(small)), dim3(256), 0, stream, masks, counts,
-                       nChunks, open, static_cast<uint16_t *>(nullptr));
-    hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, open, nChunks);
-  }
+  const uint64_t nChunks = splitChunks(len);
+  const TallyScratch m(scratch, nChunks);
+  // (no selected bitmap to zero)
+  hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                 nullptr, m.misc, cfg.numCUs, stream);
+  if (e != hipSuccess) return e;
   const uint64_t toZero = accumulate ? 0 : nBins + 1;
   uint64_t zb = (toZero + 255) / 256;
   if (zb > uint64_t(cfg.numCUs) * 8) zb = uint64_t(cfg.numCUs) * 8;
   TallyOut o{reinterpret_cast<unsigned long long *>(bins),
-             reinterpret_cast<unsigned long long *>(nItems ? nItems : misc + 2), uint32_t(nBins), 0};
+             reinterpret_cast<unsigned long long *>(nItems ? nItems : m.misc + 2), uint32_t(nBins),
+             0};
   hipLaunchKernelGGL(k_tl_zero, dim3(uint32_t(zb ? zb : 1)), dim3(256), 0, stream, o.bins, toZero,
                      o.nItems);
-  hipError_t e = hipGetLastError();
+  e = hipGetLastError();
   if (e != hipSuccess || nChunks == 0) return e;
   const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
   int verb = kSearch;
@@ -1122,30 +1086,49 @@ hipError_t launchTallyText(const DevDfa &d, int what, int style, int doLeader, c
   // (k_tally_text.h: tallyAdd); a longer text counts in global memory alone
   const uint32_t room = len < (1ull << 32) ? tallyLdsBins(d.tableKind, d.tableBytes, d.nStates) : 0u;
   o.ldsBins = nBins + 1 < room ? uint32_t(nBins + 1) : room;
-  const GpBufs b{masks, nullptr, bases, open, nullptr, nullptr, nChunks};
-  const uint32_t tableKind = d.tableKind;
+  const GpBufs b{m.masks, nullptr, m.bases, m.open, nullptr, nullptr, nChunks};
 #define TL_ARGS d, data, b, style, lead, plain, o, cfg, stream
 #define TL_CALL(K)                                                                    \
   (what == REDGPU_TALLY_MATCHES ? launchTallyK<K, kTallyMatches>(TL_ARGS)             \
    : verb == kSearch            ? launchTallyK<K, kTallyLines>(TL_ARGS)               \
                                 : launchTallyK<K, kTallyLinesMatch>(TL_ARGS))
-  TL_KINDS(TL_CALL)
+  REDGPU_KIND_SWITCH(TL_CALL)
 #undef TL_CALL
 #undef TL_ARGS
 }
-#undef TL_KINDS
 #endif  // REDGPU_TU_TALLY_TEXT
 
 #if REDGPU_TU_REPLACE_TEXT
-// sed over a raw text (k_replace_text.h): the split's count and scan and grep's k_gp_last /
-// k_gp_open as they stand, then the k_rt_* passes around k_misc.h's 64-bit scan.  scratch:
-// replaceTextScratchBytes(len) bytes, 16-byte aligned: the two bitmaps, and 44 bytes per chunk, 8 per
-// 1,024 chunks and 72, rounded up to 16.
+// sed over a raw text (k_replace_text.h): the line index (launchTextIndex), then the k_rt_* passes
+// around k_misc.h's 64-bit scan.  scratch: replaceTextScratchBytes(len) bytes, 16-byte aligned:
+// the two bitmaps, and 44 bytes per chunk, 8 per 1,024 chunks and 72, rounded up to 16.
+struct ReplaceScratch {
+  uint64_t *bases, *open, *outBytes, *replCounts;  // [nChunks] each
+  uint64_t *outBases;                              // [nChunks + 1]
+  uint64_t *partials;                              // [nPart]
+  uint64_t *misc;               // [8]: lines, the scan's spare word, replaced, tailAt[2], 3 spare
+  uint32_t *counts;             // [nChunks]
+  uint16_t *masks, *hitMasks;   // the delimiter bitmap, the hit bitmap
+  uint64_t nPart, bytes;
+  ReplaceScratch(void *scratch, uint64_t nChunks) : nPart((nChunks + 1023) / 1024) {
+    Carve c{static_cast<uint8_t *>(scratch)};
+    bases = c.take<uint64_t>(nChunks);
+    open = c.take<uint64_t>(nChunks);
+    outBytes = c.take<uint64_t>(nChunks);
+    replCounts = c.take<uint64_t>(nChunks);
+    outBases = c.take<uint64_t>(nChunks + 1);
+    partials = c.take<uint64_t>(nPart);
+    misc = c.take<uint64_t>(8);
+    counts = c.take<uint32_t>(nChunks);
+    c.align(16);
+    masks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    hitMasks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    bytes = c.at;
+  }
+};
+
 uint64_t replaceTextScratchBytes(uint64_t len) {
-  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
-  const uint64_t nPart = (nChunks + 1023) / 1024;
-  const uint64_t head = (5 * nChunks + 1 + nPart + 8) * 8 + nChunks * 4;
-  return ((head + 15) & ~uint64_t(15)) + 2 * nChunks * (kSplitChunk / 8);
+  return ReplaceScratch(nullptr, splitChunks(len)).bytes;
 }
 
 hipError_t launchReplaceText(const DevDfa &d, int style, int doLeader, int onlyChanged,
@@ -1155,68 +1138,33 @@ hipError_t launchReplaceText(const DevDfa &d, int style, int doLeader, int onlyC
                              void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                              const char **kernelName) {
   *kernelName = "k_replace_text";
-  const uint64_t nChunks = (len + kSplitChunk - 1) / kSplitChunk;
-  const uint64_t nPart = (nChunks + 1023) / 1024;
-  // [bases, open, outBytes, replCounts: u64[nChunks] each][outBases: u64[nChunks + 1]]
-  // [partials: u64[nPart]][lines, dummy, replaced, tailAt[2]: u64, 24 spare][counts: u32[nChunks]]
-  // [pad to 16][delimiter bitmap][hit bitmap]
-  uint8_t *q = static_cast<uint8_t *>(scratch);
-  uint64_t *bases = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint64_t *open = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint64_t *outBytes = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint64_t *replCounts = reinterpret_cast<uint64_t *>(q); q += nChunks * 8;
-  uint64_t *outBases = reinterpret_cast<uint64_t *>(q); q += (nChunks + 1) * 8;
-  uint64_t *partials = reinterpret_cast<uint64_t *>(q); q += nPart * 8;
-  uint64_t *misc = reinterpret_cast<uint64_t *>(q); q += 64;
-  uint32_t *counts = reinterpret_cast<uint32_t *>(q); q += nChunks * 4;
-  q = static_cast<uint8_t *>(scratch) + ((uint64_t(q - static_cast<uint8_t *>(scratch)) + 15) & ~uint64_t(15));
-  uint16_t *masks = reinterpret_cast<uint16_t *>(q); q += nChunks * (kSplitChunk / 8);
-  uint16_t *hitMasks = reinterpret_cast<uint16_t *>(q);
-  uint64_t *dummy = misc + 1, *tailAt = misc + 3;
+  const uint64_t nChunks = splitChunks(len);
+  const ReplaceScratch m(scratch, nChunks);
+  uint64_t *tailAt = m.misc + 3;
   const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
-  const GpBufs b{masks, hitMasks, bases, open, nullptr, nullptr, nChunks};
-  const RtBufs r{outBytes, replCounts, outBases};
+  const GpBufs b{m.masks, m.hitMasks, m.bases, m.open, nullptr, nullptr, nChunks};
+  const RtBufs r{m.outBytes, m.replCounts, m.outBases};
   const RtArgs a{style, lead, onlyChanged, uint32_t(delim), repl, replLen, max};
 #define RT_CALL(K) launchReplaceTextK<K>(d, data, b, r, a, count, out, outCap, cfg, stream)
-  auto pass = [&](bool count) {
-    switch (d.tableKind) {
-    case REDGPU_TAB_LDS_FUSED_U8: return RT_CALL(REDGPU_TAB_LDS_FUSED_U8);
-    case REDGPU_TAB_LDS_FUSED_U16: return RT_CALL(REDGPU_TAB_LDS_FUSED_U16);
-    case REDGPU_TAB_LDS_CLASS_U16: return RT_CALL(REDGPU_TAB_LDS_CLASS_U16);
-    case REDGPU_TAB_GLOBAL_U16: return RT_CALL(REDGPU_TAB_GLOBAL_U16);
-    case REDGPU_TAB_HOT_ROWS: return RT_CALL(REDGPU_TAB_HOT_ROWS);
-    case REDGPU_TAB_LDS_SPARSE: return RT_CALL(REDGPU_TAB_LDS_SPARSE);
-    default: return RT_CALL(REDGPU_TAB_GLOBAL_U32);
-    }
-  };
+  auto pass = [&](bool count) { REDGPU_KIND_SWITCH(RT_CALL) };
 #undef RT_CALL
   if (phases & 1) {
+    hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                   m.hitMasks, m.misc, cfg.numCUs, stream);
+    if (e != hipSuccess) return e;
     if (nChunks) {
-      hipLaunchKernelGGL(k_split_count, dim3(uint32_t(nChunks)), dim3(kSplitThreads), 0, stream,
-                         data, len, uint32_t(delim), nChunks, counts, masks);
-    }
-    // (k_split_scan's offsets[0] store goes to a spare word)
-    hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, counts, nChunks, bases,
-                       nLines ? nLines : misc, dummy, uint64_t(0));
-    if (nChunks) {
-      uint64_t small = (nChunks + 3) / 4;
-      if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
-      hipLaunchKernelGGL(k_gp_last, dim3(uint32_t(small)), dim3(256), 0, stream, masks, counts,
-                         nChunks, open, hitMasks);
-      hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, open, nChunks);
-      hipError_t e = hipGetLastError();
-      if (e == hipSuccess) e = pass(true);
+      e = pass(true);
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(nPart)), dim3(256), 0, stream, outBytes,
-                         nChunks, partials);
-      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, partials, nPart);
-      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(nPart)), dim3(256), 0, stream, outBytes,
-                         nChunks, partials, outBases);
+      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream,
+                         m.outBytes, nChunks, m.partials);
+      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
+      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.outBytes,
+                         nChunks, m.partials, m.outBases);
     }
-    hipLaunchKernelGGL(k_rt_totals, dim3(1), dim3(1024), 0, stream, replCounts, nChunks,
-                       nChunks ? outBases + nChunks : nullptr, masks, open, len, onlyChanged,
-                       tailAt, outLen, nReplaced ? nReplaced : misc + 2);
-    const hipError_t e = hipGetLastError();
+    hipLaunchKernelGGL(k_rt_totals, dim3(1), dim3(1024), 0, stream, m.replCounts, nChunks,
+                       nChunks ? m.outBases + nChunks : nullptr, m.masks, m.open, len, onlyChanged,
+                       tailAt, outLen, nReplaced ? nReplaced : m.misc + 2);
+    e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   if ((phases & 2) && out && outCap && nChunks) {
@@ -1327,22 +1275,9 @@ hipError_t launchBatch(const DevDfa &d, const Batch &b, int verb, int style, int
                           !cfg.forceGeneric
                       ? "k_scan_marked" : "k_generic";
   }
-  switch (d.tableKind) {
-  case REDGPU_TAB_LDS_FUSED_U8:
-    return launchGeneric<REDGPU_TAB_LDS_FUSED_U8>(d, b, verb, style, lead, cfg, stream);
-  case REDGPU_TAB_LDS_FUSED_U16:
-    return launchGeneric<REDGPU_TAB_LDS_FUSED_U16>(d, b, verb, style, lead, cfg, stream);
-  case REDGPU_TAB_LDS_CLASS_U16:
-    return launchGeneric<REDGPU_TAB_LDS_CLASS_U16>(d, b, verb, style, lead, cfg, stream);
-  case REDGPU_TAB_GLOBAL_U16:
-    return launchGeneric<REDGPU_TAB_GLOBAL_U16>(d, b, verb, style, lead, cfg, stream);
-  case REDGPU_TAB_HOT_ROWS:
-    return launchGeneric<REDGPU_TAB_HOT_ROWS>(d, b, verb, style, lead, cfg, stream);
-  case REDGPU_TAB_LDS_SPARSE:
-    return launchGeneric<REDGPU_TAB_LDS_SPARSE>(d, b, verb, style, lead, cfg, stream);
-  default:
-    return launchGeneric<REDGPU_TAB_GLOBAL_U32>(d, b, verb, style, lead, cfg, stream);
-  }
+#define GE_CALL(K) launchGeneric<K>(d, b, verb, style, lead, cfg, stream)
+  REDGPU_KIND_SWITCH(GE_CALL)
+#undef GE_CALL
 }
 
 #endif  // REDGPU_TU_GENERIC

@@ -220,6 +220,52 @@ class HostCall {
   int rc_ = REDGPU_OK;
 };
 
+// The _dev form of a raw-text verb behind its argument check: the device, ONE allocation of
+// scratchBytes for the call - carved up by the verb's launcher, which launch(scratch, cfg, &name)
+// calls - everything on `s`, nothing read back
+template <class F>
+int rawTextDev(const redgpu_dfa *dfa, hipStream_t s, uint64_t scratchBytes, F &&launch) {
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  void *scratch = nullptr;
+  HIP_TRY(scratchFor(s, size_t(scratchBytes), &scratch), "hipMalloc scratch");
+  const LaunchCfg cfg = cfgOf(dfa);
+  const char *name = "";
+  const hipError_t e = launch(scratch, cfg, &name);
+  tlsKernel = name;
+  if (e != hipSuccess) return failHip(e, "kernel launch");
+  return REDGPU_OK;
+}
+
+// The optional record columns of the grep_text / collect_text host forms: device buffers of cap
+// records for the columns the caller asked for, and the filled prefixes back
+struct RecordCols {
+  uint64_t *line, *begin, *finish;
+  int32_t *result;
+  uint64_t *start, *end;
+
+  RecordCols onDevice(HostCall &call, uint64_t cap) const {
+    RecordCols d{};
+    if (line && cap) d.line = call.buf<uint64_t>(kSlOff, cap, "line");
+    if (begin && cap) d.begin = call.buf<uint64_t>(kSlAux1, cap, "begin");
+    if (finish && cap) d.finish = call.buf<uint64_t>(kSlAux2, cap, "finish");
+    if (result && cap) d.result = call.buf<int32_t>(kSlRes, cap, "result");
+    if (start && cap) d.start = call.buf<uint64_t>(kSlStart, cap, "start");
+    if (end && cap) d.end = call.buf<uint64_t>(kSlEnd, cap, "end");
+    return d;
+  }
+  // (this = the caller's columns, d = onDevice's)
+  void download(HostCall &call, const RecordCols &d, uint64_t got) const {
+    if (!got) return;
+    if (d.line) call.download(line, d.line, got, "line");
+    if (d.begin) call.download(begin, d.begin, got, "begin");
+    if (d.finish) call.download(finish, d.finish, got, "finish");
+    if (d.result) call.download(result, d.result, got, "result");
+    if (d.start) call.download(start, d.start, got, "start");
+    if (d.end) call.download(end, d.end, got, "end");
+  }
+};
+
 // offsets of a chunk that does not start at byte 0, rebased to the chunk's own buffer: the
 // kernels may read data[0, offsets[n]) anywhere (lanes without a line re-read block 0), so a
 // chunk is always presented as a batch of its own
@@ -1161,14 +1207,21 @@ int redgpu_match_text(const redgpu_dfa *dfa, int style, int do_leader, const uin
   return call.wait();
 }
 
-// the arguments of both grep forms: what can be refused without a device first
-static int checkGrepText(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
-                         const uint64_t *nSelected) {
+// The arguments of both forms of a raw-text verb (grep_text, collect_text, tally_text,
+// replace_text): what can be refused without a device first, in this order - no handle, no `need`
+// buffer (needError), no data, the verb's own refusal (ownError, null = none), a bad style (style
+// null: the verb takes none), a text or (tally_text) a bin count too large, a handle that is not one.
+static int checkRawText(const redgpu_dfa *dfa, const void *need, const char *needError,
+                        const uint8_t *data, uint64_t len, const char *ownError, const int *style,
+                        uint64_t nBins = 0) {
   if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (!nSelected) return fail(REDGPU_EAPI, "null n_selected buffer");
+  if (!need) return fail(REDGPU_EAPI, needError);
   if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  if (int rc = checkStyle(style)) return rc;
+  if (ownError) return fail(REDGPU_EAPI, ownError);
+  if (style)
+    if (int rc = checkStyle(*style)) return rc;
   if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
+  if (nBins > (1ull << 31)) return fail(REDGPU_ELIMIT, "n_bins too large");
   return checkHandle(dfa);
 }
 
@@ -1179,21 +1232,15 @@ int redgpu_grep_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int in
                          uint64_t cap, uint64_t *n_lines, uint64_t *n_selected, uint64_t *line,
                          uint64_t *begin, uint64_t *finish, int32_t *result, uint64_t *start,
                          uint64_t *end, void *stream) {
-  if (int rc = checkGrepText(dfa, style, data, len, n_selected)) return rc;
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  if (int rc = checkRawText(dfa, n_selected, "null n_selected buffer", data, len, nullptr, &style))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // ONE allocation for the call, carved up by launchGrepText: the split's pieces and the grep's own
-  void *scratch = nullptr;
-  HIP_TRY(scratchFor(s, size_t(grepScratchBytes(len)), &scratch), "hipMalloc scratch");
-  const LaunchCfg cfg = cfgOf(dfa);
-  const char *name = "";
-  const hipError_t e = launchGrepText(dfa->im->dev, style, do_leader ? 1 : 0, invert ? 1 : 0, data,
-                                      len, delim, max_count, cap, n_lines, n_selected, line, begin,
-                                      finish, result, start, end, scratch, cfg, s, &name);
-  tlsKernel = name;
-  if (e != hipSuccess) return failHip(e, "kernel launch");
-  return REDGPU_OK;
+  return rawTextDev(dfa, s, grepScratchBytes(len),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchGrepText(dfa->im->dev, style, do_leader ? 1 : 0, invert ? 1 : 0, data, len, delim,
+                          max_count, cap, n_lines, n_selected, line, begin, finish, result, start,
+                          end, scratch, cfg, s, name);
+  });
 }
 
 // host-buffer form: one upload of the text, then the two counts and the filled prefixes back
@@ -1202,22 +1249,19 @@ int redgpu_grep_text(const redgpu_dfa *dfa, int style, int do_leader, int invert
                      uint64_t cap, uint64_t *n_lines, uint64_t *n_selected, uint64_t *line,
                      uint64_t *begin, uint64_t *finish, int32_t *result, uint64_t *start,
                      uint64_t *end) {
-  if (int rc = checkGrepText(dfa, style, data, len, n_selected)) return rc;
+  if (int rc = checkRawText(dfa, n_selected, "null n_selected buffer", data, len, nullptr, &style))
+    return rc;
   if (cap > len) cap = len;  // a buffer holds no more lines than bytes
   if (cap > max_count) cap = max_count;
   HostCall call(dfa, len);
   uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
   uint64_t *dN = call.buf<uint64_t>(kSlAux0, 2, "counts");
-  uint64_t *dLine = line && cap ? call.buf<uint64_t>(kSlOff, cap, "line") : nullptr;
-  uint64_t *dBegin = begin && cap ? call.buf<uint64_t>(kSlAux1, cap, "begin") : nullptr;
-  uint64_t *dFinish = finish && cap ? call.buf<uint64_t>(kSlAux2, cap, "finish") : nullptr;
-  int32_t *dRes = result && cap ? call.buf<int32_t>(kSlRes, cap, "result") : nullptr;
-  uint64_t *dStart = start && cap ? call.buf<uint64_t>(kSlStart, cap, "start") : nullptr;
-  uint64_t *dEnd = end && cap ? call.buf<uint64_t>(kSlEnd, cap, "end") : nullptr;
+  const RecordCols host{line, begin, finish, result, start, end};
+  const RecordCols d = host.onDevice(call, cap);
   call.upload(dData, data, len, "data");
   call.run([&] {
     return redgpu_grep_text_dev(dfa, style, do_leader, invert, dData, len, delim, max_count, cap,
-                                dN, dN + 1, dLine, dBegin, dFinish, dRes, dStart, dEnd,
+                                dN, dN + 1, d.line, d.begin, d.finish, d.result, d.start, d.end,
                                 call.stream());
   });
   uint64_t counts[2] = {0, 0};
@@ -1225,26 +1269,8 @@ int redgpu_grep_text(const redgpu_dfa *dfa, int style, int do_leader, int invert
   if (int rc = call.wait()) return rc;
   if (n_lines) *n_lines = counts[0];
   *n_selected = counts[1];
-  const uint64_t got = counts[1] < cap ? counts[1] : cap;
-  if (got) {
-    if (dLine) call.download(line, dLine, got, "line");
-    if (dBegin) call.download(begin, dBegin, got, "begin");
-    if (dFinish) call.download(finish, dFinish, got, "finish");
-    if (dRes) call.download(result, dRes, got, "result");
-    if (dStart) call.download(start, dStart, got, "start");
-    if (dEnd) call.download(end, dEnd, got, "end");
-  }
+  host.download(call, d, counts[1] < cap ? counts[1] : cap);
   return call.wait();
-}
-
-// the arguments of both collect_text forms: what can be refused without a device first
-static int checkCollectText(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
-                            const uint64_t *nMatches) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (!nMatches) return fail(REDGPU_EAPI, "null n_matches buffer");
-  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
-  return checkHandle(dfa);
 }
 
 // raw text -> every match of every line, as records in text order (k_collect_text.h): everything
@@ -1253,70 +1279,51 @@ int redgpu_collect_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t
                             uint64_t cap, uint64_t *n_lines, uint64_t *n_matches, uint64_t *line,
                             uint64_t *begin, int32_t *result, uint64_t *start, uint64_t *end,
                             void *stream) {
-  if (int rc = checkCollectText(dfa, data, len, n_matches)) return rc;
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  if (int rc = checkRawText(dfa, n_matches, "null n_matches buffer", data, len, nullptr, nullptr))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // ONE allocation for the call, carved up by launchCollectText
-  void *scratch = nullptr;
-  HIP_TRY(scratchFor(s, size_t(collectTextScratchBytes(len)), &scratch), "hipMalloc scratch");
-  const LaunchCfg cfg = cfgOf(dfa);
-  const char *name = "";
-  const hipError_t e = launchCollectText(dfa->im->dev, data, len, delim, cap, n_lines, n_matches,
-                                         line, begin, result, start, end, scratch, cfg, s, &name);
-  tlsKernel = name;
-  if (e != hipSuccess) return failHip(e, "kernel launch");
-  return REDGPU_OK;
+  return rawTextDev(dfa, s, collectTextScratchBytes(len),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchCollectText(dfa->im->dev, data, len, delim, cap, n_lines, n_matches, line, begin,
+                             result, start, end, scratch, cfg, s, name);
+  });
 }
 
 // host-buffer form: one upload of the text, then the two counts and the filled prefixes back
 int redgpu_collect_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                         uint64_t cap, uint64_t *n_lines, uint64_t *n_matches, uint64_t *line,
                         uint64_t *begin, int32_t *result, uint64_t *start, uint64_t *end) {
-  if (int rc = checkCollectText(dfa, data, len, n_matches)) return rc;
+  if (int rc = checkRawText(dfa, n_matches, "null n_matches buffer", data, len, nullptr, nullptr))
+    return rc;
   if (cap > len) cap = len;  // a match has a byte of its own: no more records than bytes
   HostCall call(dfa, len);
   uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
   uint64_t *dN = call.buf<uint64_t>(kSlAux0, 2, "counts");
-  uint64_t *dLine = line && cap ? call.buf<uint64_t>(kSlOff, cap, "line") : nullptr;
-  uint64_t *dBegin = begin && cap ? call.buf<uint64_t>(kSlAux1, cap, "begin") : nullptr;
-  int32_t *dRes = result && cap ? call.buf<int32_t>(kSlRes, cap, "result") : nullptr;
-  uint64_t *dStart = start && cap ? call.buf<uint64_t>(kSlStart, cap, "start") : nullptr;
-  uint64_t *dEnd = end && cap ? call.buf<uint64_t>(kSlEnd, cap, "end") : nullptr;
+  const RecordCols host{line, begin, nullptr, result, start, end};
+  const RecordCols d = host.onDevice(call, cap);
   call.upload(dData, data, len, "data");
   call.run([&] {
-    return redgpu_collect_text_dev(dfa, dData, len, delim, cap, dN, dN + 1, dLine, dBegin, dRes,
-                                   dStart, dEnd, call.stream());
+    return redgpu_collect_text_dev(dfa, dData, len, delim, cap, dN, dN + 1, d.line, d.begin,
+                                   d.result, d.start, d.end, call.stream());
   });
   uint64_t counts[2] = {0, 0};
   call.download(counts, dN, 2, "counts");
   if (int rc = call.wait()) return rc;
   if (n_lines) *n_lines = counts[0];
   *n_matches = counts[1];
-  const uint64_t got = counts[1] < cap ? counts[1] : cap;
-  if (got) {
-    if (dLine) call.download(line, dLine, got, "line");
-    if (dBegin) call.download(begin, dBegin, got, "begin");
-    if (dRes) call.download(result, dRes, got, "result");
-    if (dStart) call.download(start, dStart, got, "start");
-    if (dEnd) call.download(end, dEnd, got, "end");
-  }
+  host.download(call, d, counts[1] < cap ? counts[1] : cap);
   return call.wait();
 }
 
-// the arguments of both tally_text forms: what can be refused without a device first
+// the arguments of both tally_text forms
 static int checkTallyText(const redgpu_dfa *dfa, int what, int style, const uint8_t *data,
                           uint64_t len, uint64_t nBins, const uint64_t *bins) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (!bins) return fail(REDGPU_EAPI, "null bins buffer");
-  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  if (what != REDGPU_TALLY_LINES && what != REDGPU_TALLY_MATCHES)
-    return fail(REDGPU_EAPI, "what is neither REDGPU_TALLY_LINES nor REDGPU_TALLY_MATCHES");
-  if (what == REDGPU_TALLY_LINES)
-    if (int rc = checkStyle(style)) return rc;
-  if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
-  if (nBins > (1ull << 31)) return fail(REDGPU_ELIMIT, "n_bins too large");
-  return checkHandle(dfa);
+  const bool lines = what == REDGPU_TALLY_LINES;
+  return checkRawText(dfa, bins, "null bins buffer", data, len,
+                      lines || what == REDGPU_TALLY_MATCHES
+                          ? nullptr
+                          : "what is neither REDGPU_TALLY_LINES nor REDGPU_TALLY_MATCHES",
+                      lines ? &style : nullptr, nBins);
 }
 
 // raw text -> how many lines / matches report each result (k_tally_text.h): everything on
@@ -1326,23 +1333,15 @@ int redgpu_tally_text_dev(const redgpu_dfa *dfa, int what, int style, int do_lea
                           int accumulate, uint64_t *n_lines, uint64_t *n_items, uint64_t *bins,
                           void *stream) {
   if (int rc = checkTallyText(dfa, what, style, data, len, n_bins, bins)) return rc;
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // ONE allocation for the call, carved up by launchTallyText
-  void *scratch = nullptr;
-  HIP_TRY(scratchFor(s, size_t(tallyTextScratchBytes(len)), &scratch), "hipMalloc scratch");
-  const LaunchCfg cfg = cfgOf(dfa);
   // REDGPU_TALLY_PLAIN=1: an atomic per item, no ballot and no peel (measurements)
   const char *env = getenv("REDGPU_TALLY_PLAIN");
   const int plain = env && env[0] == '1';
-  const char *name = "";
-  const hipError_t e = launchTallyText(dfa->im->dev, what, style, do_leader ? 1 : 0, data, len,
-                                       delim, n_bins, accumulate ? 1 : 0, plain, n_lines, n_items,
-                                       bins, scratch, cfg, s, &name);
-  tlsKernel = name;
-  if (e != hipSuccess) return failHip(e, "kernel launch");
-  return REDGPU_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return rawTextDev(dfa, s, tallyTextScratchBytes(len),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchTallyText(dfa->im->dev, what, style, do_leader ? 1 : 0, data, len, delim, n_bins,
+                           accumulate ? 1 : 0, plain, n_lines, n_items, bins, scratch, cfg, s, name);
+  });
 }
 
 // host-buffer form: one upload of the text, device bins of the call's own, then the two counts
@@ -1390,16 +1389,11 @@ uint32_t redgpu_tally_lds_bins(const redgpu_dfa *dfa) {
   return tallyLdsBins(img.tableKind, (img.primaryBytes + 15u) & ~15u, img.nStates);
 }
 
-// the arguments of both replace_text forms: what can be refused without a device first
+// the arguments of both replace_text forms
 static int checkReplaceText(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
                             const uint8_t *repl, uint64_t replLen, const uint64_t *outLen) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (!outLen) return fail(REDGPU_EAPI, "null out_len buffer");
-  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  if (replLen && !repl) return fail(REDGPU_EAPI, "null replacement");
-  if (int rc = checkStyle(style)) return rc;
-  if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
-  return checkHandle(dfa);
+  return checkRawText(dfa, outLen, "null out_len buffer", data, len,
+                      replLen && !repl ? "null replacement" : nullptr, &style);
 }
 
 // raw text -> every line rewritten, the text put back together (k_replace_text.h): everything on
@@ -1410,20 +1404,12 @@ static int replaceTextDev(const redgpu_dfa *dfa, int style, int doLeader, int on
                           uint64_t *nReplaced, uint64_t *outLen, uint8_t *out, uint64_t outCap,
                           int phases, hipStream_t s) {
   if (int rc = checkReplaceText(dfa, style, data, len, repl, replLen, outLen)) return rc;
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  // ONE allocation for the call, carved up by launchReplaceText
-  void *scratch = nullptr;
-  HIP_TRY(scratchFor(s, size_t(replaceTextScratchBytes(len)), &scratch), "hipMalloc scratch");
-  const LaunchCfg cfg = cfgOf(dfa);
-  const char *name = "";
-  const hipError_t e = launchReplaceText(dfa->im->dev, style, doLeader ? 1 : 0, onlyChanged ? 1 : 0,
-                                         data, len, delim, repl, replLen, maxCount, nLines,
-                                         nReplaced, outLen, out, outCap, phases, scratch, cfg, s,
-                                         &name);
-  tlsKernel = name;
-  if (e != hipSuccess) return failHip(e, "kernel launch");
-  return REDGPU_OK;
+  return rawTextDev(dfa, s, replaceTextScratchBytes(len),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchReplaceText(dfa->im->dev, style, doLeader ? 1 : 0, onlyChanged ? 1 : 0, data, len,
+                             delim, repl, replLen, maxCount, nLines, nReplaced, outLen, out, outCap,
+                             phases, scratch, cfg, s, name);
+  });
 }
 
 int redgpu_replace_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int only_changed,
