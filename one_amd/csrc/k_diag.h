@@ -29,62 +29,62 @@ k_diag_read(const uint4 *__restrict__ p, uint64_t n16, uint32_t *sink) {
 }
 
 // The memory side of the streaming walk over 64-byte lines with nothing else: what HBM gives
-// k_stream_multi's requests and stores when no table is staged and no step is taken - 64 B read +
-// 20 B written per line.  It requests and stores exactly as the walk does (k_stream_multi.h): two
-// 512-thread workgroups per CU, lines c * 512 + tid of a 1024-line tile, each lane 4 x 16 bytes
-// back to back of each of its two lines, two register sets with the NEXT tile's 8 loads issued
-// before this tile's stores (gfx9's vmcnt is one in-order counter: a loop that stores and only
-// then requests waits for its store acknowledgements with every tile), the loop rotated as the
-// walk's, per line an int32 and two uint64 stored non-temporally.  bench.py reports the figure as
+// k_stream_multi_r1's requests and stores when no table is staged and no step is taken - 64 B read
+// + 20 B written per line.  It requests and stores exactly as the walk does (k_stream_multi.h): two
+// workgroups of THREADS per CU, lines c * THREADS + tid of a tile of 2 * THREADS lines, ONE register
+// set of 4 x 16 bytes per line; a tile's line is consumed, the line of the workgroup's next tile is
+// requested into its place (4 x 16 bytes back to back per line), then per line an int32 and two
+// uint64 are stored non-temporally (gfx9's vmcnt is one in-order counter: the wait in front of a
+// tile is a counted one, the stores still out), the first tile peeled as the walk's.  Nothing is
+// requested ahead: the other waves cover the round trip.  bench.py reports the figure as
 // lines64_memory_roof_GBps.  Measured, it is what the walk's schedule gets without the walk and
-// NOT an upper bound of the shape: the unpipelined loop this replaced (one workgroup per CU;
-// loads, wait, stores) gave 4.2 TB/s where this gives 3.9, and the walk itself passes it
-// (profiles/outcome_store_ab.txt).
-__global__ void __launch_bounds__(512)
+// NOT an upper bound of the shape (profiles/outcome_store_ab.txt).
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS)
 k_diag_lines(const uint8_t *__restrict__ data, uint64_t nLines, int32_t *res, uint64_t *st,
              uint64_t *en, uint32_t *sink) {
   typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-  const uint64_t tiles = nLines / 1024;
+  constexpr uint64_t LPT = 2 * uint64_t(THREADS);
+  const uint64_t tiles = nLines / LPT;
   const uint64_t G = gridDim.x;
   if (blockIdx.x >= tiles) return;
   const uint64_t Q = (tiles - blockIdx.x + G - 1) / G;  // tiles this workgroup takes
-  // load cursor: one tile ahead; on the last tile it stays there (unconditional requests)
-  uint64_t ldT = blockIdx.x, ldQ = 0, t = blockIdx.x;
+  // the cursor: the tile being requested; on the last tile it stays there (unconditional requests)
+  uint64_t ldT = blockIdx.x, ldQ = 0;
   v4 acc = {0, 0, 0, 0};
-  v4 A[2][4], B[2][4];
-  auto issue = [&](v4 (&blk)[2][4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const uint64_t ln = ldT * 1024 + uint64_t(c) * 512 + threadIdx.x;
-        blk[c][k] = reinterpret_cast<const v4 *>(data + ln * 64)[k];
-      }
-    if (ldQ + 1 < Q) { ++ldQ; ldT += G; }
-  };
-  auto walk = [&](const v4 (&blk)[2][4]) {
+  v4 X[4][2];
+  auto request = [&](int k) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      const uint64_t ln = t * 1024 + uint64_t(c) * 512 + threadIdx.x;
-      const v4 x = blk[c][0] ^ blk[c][1] ^ blk[c][2] ^ blk[c][3];
-      acc ^= x;
-      __builtin_nontemporal_store(int32_t(x.x), res + ln);
-      __builtin_nontemporal_store(uint64_t(x.z), en + ln);
-      __builtin_nontemporal_store(uint64_t(x.y), st + ln);
+      const uint64_t ln = ldT * LPT + uint64_t(c) * THREADS + threadIdx.x;
+      X[k][c] = reinterpret_cast<const v4 *>(data + ln * 64)[k];
     }
-    t += G;
   };
-  issue(A);
-  issue(B);
-  walk(A);
-  issue(A);
-  for (uint64_t q = 1; q < Q; q += 2) {
-    walk(B);
-    if (q + 1 >= Q) break;
-    issue(B);
-    walk(A);
-    issue(A);
-  }
+  auto walk = [&]() {
+    const uint64_t t = ldT;  // the tile under the cursor is the tile to consume
+    v4 x[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) x[c] = k ? x[c] ^ X[k][c] : X[k][c];
+    }
+    if (ldQ + 1 < Q) { ++ldQ; ldT += G; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) request(k);
+    __builtin_amdgcn_sched_barrier(0);  // the requests stay in front of the stores
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const uint64_t ln = t * LPT + uint64_t(c) * THREADS + threadIdx.x;
+      acc ^= x[c];
+      __builtin_nontemporal_store(int32_t(x[c].x), res + ln);
+      __builtin_nontemporal_store(uint64_t(x[c].z), en + ln);
+      __builtin_nontemporal_store(uint64_t(x[c].y), st + ln);
+    }
+  };
+#pragma unroll
+  for (int k = 0; k < 4; ++k) request(k);
+  walk();
+  for (uint64_t q = 1; q < Q; ++q) walk();
   if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x9e3779b9u) atomicAdd(sink, 1u);
 }
 

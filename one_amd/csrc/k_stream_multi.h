@@ -15,6 +15,8 @@
 // tile t belongs to batch k iff tileStart[k] <= t < tileStart[k + 1], and a cursor moves to the
 // next batch by comparing against the bound it keeps in an SGPR (the descriptors are read from
 // the kernel argument segment, scalar loads, once per batch and workgroup).
+// 64-byte lines run k_stream_multi_r1 below: one register block per line, 2048-line tiles, twice
+// the waves per CU.
 #pragma once
 
 constexpr int kMultiMax = 32;  // batches per launch (descriptors ride in the kernel arguments)
@@ -45,23 +47,19 @@ __device__ __forceinline__ uint4 ntLoad16(const uint8_t *p) {
 // not read by this launch; with two workgroups per CU the 20-batch configs[1] launch took 319 us
 // against 345-349 us for either measure alone and for neither, r3 lab); bit 0: non-temporal
 // input loads too (lab only: slower, 465 against 421 us).  REDGPU_MULTI_NT picks another value.
-// R1: 64-byte LINES - every block ends a line (the launcher's promise), so R is the constant 1
-// and the non-temporal stores stand alone in the code.  With R read from the descriptor the
-// choice "non-temporal if R == 1, plain otherwise" is an if / else around two copies of the same
-// stores: the compiler merges the copies and the merged stores lose the hint (in the ISA of that
-// form not one store carries nt) - which is how configs[1] ran with plain stores.
+// (64-byte lines have a kernel of their own, k_stream_multi_r1 below; here R is read from the
+// descriptor, and the choice "non-temporal if R == 1, plain otherwise" is an if / else around two
+// copies of the same stores that the compiler merges: in this kernel's ISA no store carries nt.)
 // LEAN: the deferred-bookkeeping step of k_stream_lean.h (long lines; the two remembered pieces of
 // a line are re-walked exactly when the line ends).
 // GR: groups of two chains per lane (2 = four lines per lane; LEAN only, k_stream_lean.h).
-template <int MODE, int HALVES, int THREADS, int NT = 2, bool LEAN = false, int GR = 1,
-          bool R1 = false>
+template <int MODE, int HALVES, int THREADS, int NT = 2, bool LEAN = false, int GR = 1>
 __global__ void __launch_bounds__(THREADS)
 k_stream_multi(DevDfa d, MultiIo m) {
   static_assert(MODE == kSmLastStartEnd || MODE == kSmLastEnd || MODE == kSmFullStart ||
                 MODE == kSmFull, "the plain output modes only");
   static_assert(!LEAN || MODE != kSmFull, "styFull without start has no bookkeeping to defer");
   static_assert(GR == 1 || LEAN, "more than two chains per lane: the lean step only");
-  static_assert(!R1 || (HALVES == 1 && !LEAN && GR == 1), "R1: the plain 64-byte walk only");
   constexpr uint32_t BLK = 64 * HALVES;
   constexpr int CH = kStreamChains * GR;
   constexpr bool kAcc = MODE == kSmLastStartEnd || MODE == kSmLastEnd;
@@ -73,7 +71,7 @@ k_stream_multi(DevDfa d, MultiIo m) {
 
   const uint32_t init = d.init, firstAccept = d.firstAccept;
   const uint32_t lineLen = m.lineLen;
-  const uint32_t R = R1 ? 1u : lineLen / BLK;  // blocks per line
+  const uint32_t R = lineLen / BLK;  // blocks per line
   const uint32_t nTiles = m.tileStart[m.nb];
   const uint32_t G = gridDim.x;
   if (blockIdx.x >= nTiles) return;
@@ -385,6 +383,195 @@ k_stream_multi(DevDfa d, MultiIo m) {
   }
 }
 
+// =========================================================================================
+// 64-byte LINES: the resident form.  A block is a whole line, so R is the constant 1, every block
+// ends in a line's six stores (non-temporal: written once, not read by this launch; with R read
+// from the descriptor the compiler merges the plain and the non-temporal copy of the stores and
+// the hint is lost) and the walk keeps ONE register block per line instead of two: when the 64
+// steps of a tile are taken the lane requests its next tile's line - four 16-byte loads back to
+// back, the first misses, the rest hit the cache line - into the registers the walk just left, in
+// front of the tile's stores, and starts on it as soon as it is there.  Nothing is requested a
+// block ahead; what covers the round trip is the other waves: 32 input VGPRs instead of 64 let
+// kResidentThreads threads of two workgroups - 32 waves, 64 dependent chains - stay resident on a
+// CU where the ping-pong form held 16.  One line per chain in flight per lane,
+// never more.  Per tile the vm operations are eight loads and six stores; the wait in front of a
+// tile's first piece is the counted vmcnt(6): the stores may still be out.  The first tile is
+// peeled so that both ways into the loop head end in the same fourteen operations (k_stream.h).
+// (Requesting piece q again right after ITS 16 steps keeps the block-ahead distance with the same
+// registers and was measured first: a line's four pieces are then requested microseconds apart,
+// its cache line is fetched from HBM more than once - FETCH_SIZE 1.66 x - and the walk lost 11 %,
+// profiles/stream_resident_ab.txt.)
+//
+// Addresses: a tile's lines are contiguous, so loads and stores take the tile's base (SGPRs) plus
+// the lane's line index within the tile, clamped ONCE per tile to the tile's last line
+// (ldLast = min(LPT, n - first) - 1 >= 0, because tile t of a batch exists only if first < n).
+// Every requested byte therefore lies in [data + first * 64, data + (first + ldLast + 1) * 64),
+// inside the batch's n * 64 bytes, for every lane, every piece and every repeat past the end of
+// the work (the cursor then stays on the workgroup's last tile).  Surplus lanes walk the batch's
+// last line again and store ITS Outcome into ITS slots - the same values the owning lane stores -
+// so there is no sink select and nothing is written outside [0, n) of any plane.
+// =========================================================================================
+constexpr int kResidentThreads = 1024;
+
+template <int MODE, int THREADS, int NT = 2>
+__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(THREADS / 128)))
+k_stream_multi_r1(DevDfa d, MultiIo m) {
+  static_assert(MODE == kSmLastStartEnd || MODE == kSmLastEnd || MODE == kSmFullStart ||
+                MODE == kSmFull, "the plain output modes only");
+  constexpr int CH = kStreamChains;
+  constexpr bool kAcc = MODE == kSmLastStartEnd || MODE == kSmLastEnd;
+  constexpr bool kStart = MODE == kSmLastStartEnd || MODE == kSmFullStart;
+  constexpr uint32_t LPT = uint32_t(THREADS) * CH;  // lines per tile
+  __shared__ __align__(16) uint8_t lds[kStreamTabBytes + 1024];  // table at LDS offset 0
+  uint8_t *tab = lds;
+  int32_t *ldsRes = reinterpret_cast<int32_t *>(lds + kStreamTabBytes);
+
+  const uint32_t init = d.init, firstAccept = d.firstAccept;
+  const uint32_t nTiles = m.tileStart[m.nb];
+  const uint32_t G = gridDim.x;
+  if (blockIdx.x >= nTiles) return;
+  const uint32_t Q = (nTiles - blockIdx.x + G - 1) / G;  // tiles this workgroup walks
+
+  // ---- the cursor: the tile being REQUESTED.  It moves once per tile, after the tile's last step
+  // and before the reload, and a tile's walk begins with the cursor on that very tile (it was
+  // moved there one tile earlier), so the walk copies what it needs from it.  On the
+  // workgroup's last tile it stays: requests past the end of the work re-read that tile
+  // (unconditional requests keep the compiler's in-order vmcnt counts exact, k_stream.h).  The
+  // batch's descriptor is re-read - scalar loads from the kernel argument segment - only when the
+  // cursor crosses into the next batch.
+  uint32_t ldTile = blockIdx.x, ldK = 0, ldQ = 0;
+  uint32_t ldLo = 0, ldHi = m.tileStart[1];
+  MultiPtrs ldB = m.b[0];
+  uint64_t ldFirst = 0;  // the tile's first line within its batch
+  uint32_t ldLast = 0;   // index within the tile of the last line that exists
+  auto setLoadTile = [&]() {
+    while (ldTile >= ldHi) {
+      ++ldK;
+      ldLo = ldHi;
+      ldHi = m.tileStart[ldK + 1];
+      ldB = m.b[ldK];
+    }
+    ldFirst = uint64_t(ldTile - ldLo) * LPT;
+    const uint64_t left = ldB.n - ldFirst;  // >= 1
+    ldLast = left < LPT ? uint32_t(left) - 1u : LPT - 1u;
+  };
+  uint4 X[4][CH];  // one line per chain, [piece][chain]
+  auto request = [&](int k) {
+    const uint8_t *base = ldB.data + ldFirst * 64u + 16u * uint32_t(k);
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const uint32_t l = uint32_t(c) * THREADS + threadIdx.x;
+      const uint32_t off = (l < ldLast ? l : ldLast) * 64u;
+      X[k][c] = (NT & 1) ? ntLoad16(base + off) : *reinterpret_cast<const uint4 *>(base + off);
+    }
+  };
+
+  // table requests first, the first tile's right behind them, the LDS stores and the barrier
+  // after (k_stream.h)
+  const uint4 *tsrc = reinterpret_cast<const uint4 *>(d.table);
+  const uint32_t n16 = d.tableBytes / 16;
+  constexpr uint32_t kStagePieces = (kStreamTabBytes / 16 + THREADS - 1) / THREADS;
+  uint4 tv[kStagePieces];
+#pragma unroll
+  for (uint32_t k = 0; k < kStagePieces; ++k) {
+    const uint32_t i = k * THREADS + threadIdx.x;
+    tv[k] = i < n16 ? tsrc[i] : make_uint4(0, 0, 0, 0);
+  }
+  const int32_t myRes = threadIdx.x < d.nStates ? d.result[threadIdx.x] : 0;
+  setLoadTile();
+#pragma unroll
+  for (int k = 0; k < 4; ++k) request(k);
+  {
+    uint4 *dst = reinterpret_cast<uint4 *>(tab);
+#pragma unroll
+    for (uint32_t k = 0; k < kStagePieces; ++k) {
+      const uint32_t i = k * THREADS + threadIdx.x;
+      if (i < kStreamTabBytes / 16) dst[i] = tv[k];
+    }
+    if (threadIdx.x < 256) ldsRes[threadIdx.x] = myRes;
+  }
+  asm volatile("" : : "v"(tab) : "memory");  // the byte steps read the table from asm only
+  __syncthreads();
+
+  auto walkTile = [&]() {
+    // the tile under the cursor is the tile to walk: its output slots
+    const uint32_t wkLast = ldLast;
+    int32_t *const oRes = ldB.result + ldFirst;
+    uint64_t *const oEnd = ldB.end ? ldB.end + ldFirst : nullptr;
+    uint64_t *const oStart = ldB.start ? ldB.start + ldFirst : nullptr;
+    uint32_t s[CH];
+    uint64_t mA[CH], mB[CH];
+    StreamBook b[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      s[c] = init; mA[c] = ~0ull; mB[c] = ~0ull;
+      b[c].acc = 0; b[c].end = 0; b[c].start = 0;
+    }
+    streamWalk16<MODE, 0>(X[0], s, b, mA, mB, firstAccept, init);
+    streamWalk16<MODE, 1>(X[1], s, b, mA, mB, firstAccept, init);
+    streamWalk16<MODE, 2>(X[2], s, b, mA, mB, firstAccept, init);
+    streamWalk16<MODE, 3>(X[3], s, b, mA, mB, firstAccept, init);
+    // the registers are free: the next tile's line, whole, in front of this tile's stores
+    if (ldQ + 1 < Q) {
+      ++ldQ;
+      ldTile += G;
+      setLoadTile();
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) request(k);
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      int32_t rr;
+      uint32_t en, sv = 0;
+      if (kAcc) {
+        uint32_t acc = b[c].acc;
+        en = b[c].end;
+        if (s[c] >= firstAccept) { acc = s[c]; en = 64; }
+        if (en <= m.ignoreAcceptUpTo) { en = 0; acc = 0; }  // k_stream.h
+        rr = ldsRes[acc & 0xffu];
+        rr = en ? rr : 0;
+      } else {
+        rr = ldsRes[s[c] & 0xffu];
+        rr = s[c] >= firstAccept ? rr : 0;
+        en = 64;
+      }
+      if (kStart) {
+        sv = b[c].start ? b[c].start - 1 : 0;
+        const bool wasInit63 = (mA[c] >> (threadIdx.x & 63)) & 1;
+        if (wasInit63 && s[c] != init) sv = 63;
+      }
+      // surplus lanes walked the tile's last line: they store its Outcome into its slots
+      const uint32_t l = uint32_t(c) * THREADS + threadIdx.x;
+      const uint32_t ln = l < wkLast ? l : wkLast;
+      int32_t *pr = oRes + ln;
+      uint64_t *pe = oEnd ? oEnd + ln : reinterpret_cast<uint64_t *>(d.sink);
+      uint64_t *ps = oStart ? oStart + ln : reinterpret_cast<uint64_t *>(d.sink);
+      if (NT & 2) {
+        __builtin_nontemporal_store(rr, pr);
+        __builtin_nontemporal_store(rr ? uint64_t(en) : uint64_t(0), pe);
+        if (kStart) __builtin_nontemporal_store(rr ? uint64_t(sv) : uint64_t(0), ps);
+      } else {
+        *pr = rr;
+        *pe = rr ? uint64_t(en) : 0;
+        if (kStart) *ps = rr ? uint64_t(sv) : 0;
+      }
+    }
+  };
+
+  walkTile();
+  for (uint32_t q = 1; q < Q; ++q) walkTile();
+}
+
+// the caller's MultiIo counts tiles of kStreamThreads * kStreamChains lines: the same batches in
+// tiles of `lpt` lines
+inline MultiIo retiled(const MultiIo &m, uint64_t lpt) {
+  MultiIo r = m;
+  for (uint32_t k = 0; k < m.nb; ++k)
+    r.tileStart[k + 1] = r.tileStart[k] + uint32_t((m.b[k].n + lpt - 1) / lpt);
+  for (uint32_t k = m.nb; k < uint32_t(kMultiMax); ++k) r.tileStart[k + 1] = r.tileStart[m.nb];
+  return r;
+}
+
 // tuning lab: REDGPU_MULTI_NT (see k_stream_multi; match<styLast> with start only),
 // REDGPU_MULTI_WGS = workgroups per CU for 64-byte blocks (default 2: 16 waves per CU over two
 // table copies - a single 64 MiB launch loses to it, 26.0 against 24.7 us, because both copies are
@@ -406,8 +593,12 @@ hipError_t launchStreamMultiN(const DevDfa &d, const MultiIo &m, const LaunchCfg
   const uint32_t blocks = tiles < want ? tiles : want;
   if constexpr (!LEAN) {
     if (m.lineLen == 64) {
-      hipLaunchKernelGGL((k_stream_multi<MODE, 1, kStreamThreads, NT, false, 1, true>), dim3(blocks),
-                         dim3(kStreamThreads), 0, stream, d, m);
+      // the resident form's own tiles; two workgroups per CU as above
+      const MultiIo mr = retiled(m, uint64_t(kResidentThreads) * kStreamChains);
+      const uint32_t rtiles = mr.tileStart[mr.nb];
+      hipLaunchKernelGGL((k_stream_multi_r1<MODE, kResidentThreads, NT>),
+                         dim3(rtiles < want ? rtiles : want), dim3(kResidentThreads), 0, stream, d,
+                         mr);
       return hipGetLastError();
     }
   }
@@ -425,11 +616,7 @@ hipError_t launchStreamMultiN(const DevDfa &d, const MultiIo &m, const LaunchCfg
 template <int MODE>
 hipError_t launchStreamLean4(const DevDfa &d, const MultiIo &m, const LaunchCfg &cfg,
                              hipStream_t stream) {
-  MultiIo m4 = m;
-  const uint64_t lpt = uint64_t(kStreamThreads) * kStreamChains * 2;
-  for (uint32_t k = 0; k < m.nb; ++k)
-    m4.tileStart[k + 1] = m4.tileStart[k] + uint32_t((m.b[k].n + lpt - 1) / lpt);
-  for (uint32_t k = m.nb; k < uint32_t(kMultiMax); ++k) m4.tileStart[k + 1] = m4.tileStart[m.nb];
+  const MultiIo m4 = retiled(m, uint64_t(kStreamThreads) * kStreamChains * 2);
   const uint32_t tiles = m4.tileStart[m4.nb];
   const uint32_t blocks = tiles < uint32_t(cfg.numCUs) ? tiles : uint32_t(cfg.numCUs);
   hipLaunchKernelGGL((k_stream_multi<MODE, 1, kStreamThreads, 2, true, 2>), dim3(blocks),

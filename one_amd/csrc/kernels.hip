@@ -381,6 +381,8 @@ hipError_t launchStreamBatches(const DevDfa &d, const Batch *bs, uint32_t nb, in
   m.lineLen = uint32_t(bs[0].stride);
   m.ignoreAcceptUpTo = 0;
   m.tileStart[0] = 0;
+  // tiles of 1024 lines: the unit of the decision below and of every form but the 64-byte one,
+  // which recounts tileStart for its own tiles (launchStreamMultiN)
   const uint64_t lpt = uint64_t(kStreamThreads) * kStreamChains;
   for (uint32_t k = 0; k < nb && m.nb < uint32_t(kMultiMax); ++k) {
     const Batch &b = bs[k];
@@ -848,16 +850,17 @@ hipError_t launchDiagL2(const uint16_t *table, uint32_t rounds, uint32_t *sink, 
 hipError_t launchDiagLines(const uint8_t *data, uint64_t nLines, uint32_t lineBytes, int32_t *res,
                            uint64_t *st, uint64_t *en, uint32_t *sink, int numCUs,
                            hipStream_t stream) {
-  if (nLines < 1024) return hipSuccess;
   if (lineBytes != 64) {
+    if (nLines < 1024) return hipSuccess;
     hipLaunchKernelGGL(k_diag_long, dim3(uint32_t(numCUs)), dim3(512), 0, stream, data, nLines,
                        lineBytes, sink);
     return hipGetLastError();
   }
   // two workgroups per CU when the tiles allow, as launchStreamMultiN
-  const uint64_t tiles = nLines / 1024, want = uint64_t(numCUs) * 2;
-  hipLaunchKernelGGL(k_diag_lines, dim3(uint32_t(tiles < want ? tiles : want)), dim3(512), 0,
-                     stream, data, nLines, res, st, en, sink);
+  const uint64_t tiles = nLines / (2 * uint64_t(kResidentThreads)), want = uint64_t(numCUs) * 2;
+  if (tiles == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_diag_lines<kResidentThreads>, dim3(uint32_t(tiles < want ? tiles : want)),
+                     dim3(kResidentThreads), 0, stream, data, nLines, res, st, en, sink);
   return hipGetLastError();
 }
 
