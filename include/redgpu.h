@@ -673,6 +673,55 @@ int redgpu_replace_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int
                             uint64_t *n_replaced, uint64_t *out_len, uint8_t *out, uint64_t out_cap,
                             void *stream);
 
+/* grep: raw text in, the selected lines out as a text, with grep's -A / -B / -C context - the line
+ * loop of tools/skim_red.cpp:36-46 over the lines lib/Util.cpp:109-130 cuts, printing the line
+ * where it prints the match.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter (the tail) are not a line and are never emitted.
+ *    This is the family's rule, not GNU grep's, which prints an unterminated last line.
+ *  - Line k is SELECTED iff (search<style,do_leader>(line k).result_ > 0) != (invert != 0):
+ *    exactly redgpu_grep_text's rule, verb and style normalisation.
+ *  - Only the first max_count selected lines count (grep -m): a later matching line is not
+ *    selected, though it can still be emitted as context of a counted one.
+ *  - Line i is EMITTED iff some counted selected line j has j - before <= i <= j + after.  before
+ *    and after are line counts and any value is legal, values above the number of lines too:
+ *    nothing overflows.  0, 0 is plain grep; grep -C n is before = after = n.
+ *  - The output is the emitted lines in text order, each followed by its delimiter, each ONCE:
+ *    overlapping contexts do not duplicate a line, and there is no group separator between runs
+ *    (grep --no-group-separator).  The output is a raw text every text verb accepts.
+ *  - *n_selected = min(selected, max_count); *n_emitted = lines emitted; *out_len = the length of
+ *    the whole output, whatever out_cap is; *n_lines = delimiters found.  n_lines, n_selected and
+ *    n_emitted may be NULL, each on its own; out_len is required.
+ *  - out == NULL or out_cap == 0 gives the sizes only.  Otherwise exactly the first
+ *    min(*out_len, out_cap) bytes of the output are written - the cut may fall inside a line - and
+ *    bytes of out from there on are NOT written (redgpu_replace_text's rule): out may be the middle
+ *    of a larger buffer.  out must not overlap data.
+ *  - REDGPU_EAPI for a NULL handle, a NULL out_len, a NULL data with len > 0 (the argument checks
+ *    run before the handle's device is looked at) and for a REDGPU_DEVICE_NONE handle;
+ *    REDGPU_EEXEC for a style that does not exist; REDGPU_ELIMIT for a text redgpu_split_lines
+ *    refuses.  In every error case nothing of the caller's is written.
+ *  - An empty text, or one without a delimiter: all four counts are 0 and nothing is written to
+ *    out (the _dev form writes the counts on the stream).
+ *  - A single line of megabytes is walked by one lane, and a run of emitted lines that ends in one
+ *    16 KiB chunk is copied by one wave however far back it begins: correct, and slow.
+ * redgpu_last_kernel() says "k_filter_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - nothing is read
+ * back, and no per-line array is needed from the caller or in scratch (the context is arithmetic
+ * on line numbers over the split's delimiter bitmap and the SELECTED bitmap, which the EMIT bitmap
+ * then overwrites; scratch is the two bitmaps and a few words per 16 KiB chunk: len / 4 + 68 bytes
+ * per chunk + 8 bytes per 1,024 chunks + 72, rounded up to 16, from the thread's pool).
+ * redgpu_filter_text: host buffers, as redgpu_replace_text - one upload of the text, a sizes pass,
+ * a device output sized from *out_len, and min(*out_len, out_cap) bytes downloaded. */
+int redgpu_filter_text(const redgpu_dfa *dfa, int style, int do_leader, int invert, uint64_t before,
+                       uint64_t after, uint64_t max_count, const uint8_t *data, uint64_t len,
+                       uint8_t delim, uint64_t *n_lines, uint64_t *n_selected, uint64_t *n_emitted,
+                       uint64_t *out_len, uint8_t *out, uint64_t out_cap);
+int redgpu_filter_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int invert,
+                           uint64_t before, uint64_t after, uint64_t max_count,
+                           const uint8_t *data, uint64_t len, uint8_t delim, uint64_t *n_lines,
+                           uint64_t *n_selected, uint64_t *n_emitted, uint64_t *out_len,
+                           uint8_t *out, uint64_t out_cap, void *stream);
+
 /* Measurement aid, no counterpart in the reference: one streaming read of `bytes` of device
  * memory (16-byte aligned) on the handle's device, asynchronous on `stream` - the read-bandwidth
  * calibration bench.py reports beside the roofline.  `sink` is a device uint32 the kernel may

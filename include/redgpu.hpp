@@ -310,6 +310,30 @@ inline size_t replaceText(const Executable &exec, Style style, bool doLeader,
   return size_t(made);
 }
 
+// grep (redgpu_filter_text): the lines of a text blob that search<style,doLeader> selects - the
+// others under invert, the first `most` of them - with `before` lines in front of and `after` lines
+// behind each (grep -B / -A), put together in `out`: every emitted line once, in text order, with
+// its delimiter, no group separator; the tail behind the last delimiter is never emitted.  Returns
+// the lines selected; *emitted = the lines in `out`.  `out` is sized from a first call that only sizes.
+inline size_t filterText(const Executable &exec, Style style, bool doLeader, std::string_view text,
+                         std::string &out, bool invert = false, size_t before = 0,
+                         size_t after = 0, size_t most = SIZE_MAX, char delim = '\n',
+                         size_t *emitted = nullptr) {
+  const Byte *p = reinterpret_cast<const Byte *>(text.data());
+  const uint64_t cnt = most > (uint64_t(1) << 62) ? uint64_t(1) << 62 : uint64_t(most);
+  uint64_t selected = 0, lines = 0, outLen = 0;
+  throwOnError(redgpu_filter_text(exec.handle(), style, doLeader, invert, before, after, cnt, p,
+                                  text.size(), Byte(delim), nullptr, &selected, &lines, &outLen,
+                                  nullptr, 0));
+  out.resize(size_t(outLen));
+  if (outLen)
+    throwOnError(redgpu_filter_text(exec.handle(), style, doLeader, invert, before, after, cnt, p,
+                                    text.size(), Byte(delim), nullptr, &selected, &lines, &outLen,
+                                    reinterpret_cast<Byte *>(out.data()), outLen));
+  if (emitted) *emitted = size_t(lines);
+  return size_t(selected);
+}
+
 // ---- several GPUs of one node: one image per device, contiguous shards, results in the caller's
 // arrays - the device form of tools/thr_red.cpp:84-91 (N workers over one shared Red).  devices
 // may name a device more than once (the shards then share it). ----------------------------------

@@ -183,6 +183,12 @@ def lib() -> C.CDLL:
                                            u64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         l.redgpu_collect_text.restype = C.c_int
         l.redgpu_collect_text.argtypes = [vp, vp, u64, C.c_uint8, u64, vp, vp, vp, vp, vp, vp, vp]
+        l.redgpu_filter_text.restype = C.c_int
+        l.redgpu_filter_text.argtypes = [vp, C.c_int, C.c_int, C.c_int, u64, u64, u64, vp, u64,
+                                         C.c_uint8, vp, vp, vp, vp, vp, u64]
+        l.redgpu_filter_text_dev.restype = C.c_int
+        l.redgpu_filter_text_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, u64, u64, u64, vp, u64,
+                                             C.c_uint8, vp, vp, vp, vp, vp, u64, vp]
         l.redgpu_replace_text.restype = C.c_int
         l.redgpu_replace_text.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, u64, C.c_uint8, vp, u64,
                                           u64, vp, vp, vp, vp, u64]

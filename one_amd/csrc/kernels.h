@@ -257,6 +257,21 @@ hipError_t launchReplaceText(const DevDfa &dfa, int style, int doLeader, int onl
                              void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                              const char **kernelName);
 
+// grep's output over a raw text (k_filter_text.h): the lines launchGrepText selects (the first
+// maxCount of them), `before` lines in front of and `after` lines behind each, every emitted line
+// once and in text order with its delimiter: *nSelected = min(selected, maxCount), *nEmitted = lines
+// emitted, *outLen = their bytes, the first min(*outLen, outCap) bytes in out and nothing behind them
+// (out, nLines, nSelected and nEmitted may be null).  phases: 1 = index, select, mark and size, 2 =
+// write out from what phase 1 left in scratch, 3 = both.  scratch: filterTextScratchBytes(len) bytes
+// of device memory, 16-byte aligned.  *kernelName = "k_filter_text".
+uint64_t filterTextScratchBytes(uint64_t len);
+hipError_t launchFilterText(const DevDfa &dfa, int style, int doLeader, int invert, uint64_t before,
+                            uint64_t after, uint64_t maxCount, const uint8_t *data, uint64_t len,
+                            uint8_t delim, uint64_t *nLines, uint64_t *nSelected,
+                            uint64_t *nEmitted, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                            int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                            const char **kernelName);
+
 // bench.py's read-bandwidth calibration: one streaming pass over `bytes` (16-byte aligned).
 hipError_t launchDiagRead(const void *data, uint64_t bytes, uint32_t *sink, int numCUs,
                           hipStream_t stream);

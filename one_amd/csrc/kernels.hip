@@ -48,6 +48,9 @@
 //                     the counts in a privatised LDS histogram flushed once per workgroup
 //   k_replace_text.h  k_rt_*: sed over a raw text - the same line driver, replaceCore per line, a
 //                     sizing pass, a scan, and a write pass whose waves copy the unchanged bytes
+//   k_filter_text.h   k_ft_*: grep's output with -A / -B context over a raw text - k_grep.h's select pass,
+//                     the context as arithmetic on line numbers over the two bitmaps, a scan, and a
+//                     write pass that only copies runs of emitted lines
 //   k_diag.h          bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
@@ -63,7 +66,7 @@
 // This file is compiled seven times in parallel (Makefile: -DREDGPU_TU=1/2/.../7): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
-// 3 = everything else and the dispatch, 4 = k_grep, 5 = k_collect_text, 6 = k_replace_text,
+// 3 = everything else and the dispatch, 4 = k_grep and k_filter_text (which runs k_grep's select), 5 = k_collect_text, 6 = k_replace_text,
 // 7 = k_tally_text.
 // REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
@@ -118,6 +121,7 @@ namespace {
 #include "k_collect_text.h"
 #include "k_tally_text.h"
 #include "k_replace_text.h"
+#include "k_filter_text.h"
 
 } // namespace
 
@@ -992,6 +996,100 @@ hipError_t launchGrepText(const DevDfa &d, int style, int doLeader, int invert, 
   REDGPU_KIND_SWITCH(GP_CALL)
 #undef GP_CALL
 #undef GP_ARGS
+}
+
+// grep's output over a raw text (k_filter_text.h): the line index (launchTextIndex), k_grep.h's
+// select pass, then the k_ft_* passes around k_gp_open's and k_misc.h's scans.  scratch:
+// filterTextScratchBytes(len) bytes, 16-byte aligned: the two bitmaps (len / 4), and 68 bytes per
+// chunk, 8 per 1,024 chunks and 72, rounded up to 16.
+struct FilterScratch {
+  uint64_t *bases, *open, *selBases, *prevSel, *nextRev, *emitBytes;  // [nChunks] each
+  uint64_t *outBases;                                                 // [nChunks + 1]
+  uint64_t *partials;                                                 // [nPart]
+  uint64_t *misc;  // [8]: lines, the scans' spare word, the selected total, 3 for absent counts, 2 spare
+  uint32_t *counts, *selCounts, *emitLines;  // [nChunks] each
+  uint16_t *masks, *selMasks;  // the delimiter bitmap, the SELECTED bitmap and then the EMIT one
+  uint64_t nPart, bytes;
+  FilterScratch(void *scratch, uint64_t nChunks) : nPart((nChunks + 1023) / 1024) {
+    Carve c{static_cast<uint8_t *>(scratch)};
+    bases = c.take<uint64_t>(nChunks);
+    open = c.take<uint64_t>(nChunks);
+    selBases = c.take<uint64_t>(nChunks);
+    prevSel = c.take<uint64_t>(nChunks);
+    nextRev = c.take<uint64_t>(nChunks);
+    emitBytes = c.take<uint64_t>(nChunks);
+    outBases = c.take<uint64_t>(nChunks + 1);
+    partials = c.take<uint64_t>(nPart);
+    misc = c.take<uint64_t>(8);
+    counts = c.take<uint32_t>(nChunks);
+    selCounts = c.take<uint32_t>(nChunks);
+    emitLines = c.take<uint32_t>(nChunks);
+    c.align(16);
+    masks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    selMasks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    bytes = c.at;
+  }
+};
+
+uint64_t filterTextScratchBytes(uint64_t len) {
+  return FilterScratch(nullptr, splitChunks(len)).bytes;
+}
+
+hipError_t launchFilterText(const DevDfa &d, int style, int doLeader, int invert, uint64_t before,
+                            uint64_t after, uint64_t maxCount, const uint8_t *data, uint64_t len,
+                            uint8_t delim, uint64_t *nLines, uint64_t *nSelected,
+                            uint64_t *nEmitted, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                            int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                            const char **kernelName) {
+  *kernelName = "k_filter_text";
+  const uint64_t nChunks = splitChunks(len);
+  const FilterScratch m(scratch, nChunks);
+  uint64_t *dummy = m.misc + 1, *total = m.misc + 2;
+  const GpBufs b{m.masks, m.selMasks, m.bases, m.open, m.selCounts, m.selBases, nChunks};
+  // the grid of the passes without a table: a wave per chunk, four to a workgroup
+  uint64_t small = (nChunks + 3) / 4;
+  if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
+  if (phases & 1) {
+    hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                   m.selMasks, m.misc, cfg.numCUs, stream);
+    if (e != hipSuccess) return e;
+    const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
+    int verb = kSearch;
+    normalizeVerbStyle(d, cfg, lead != 0, verb, style);
+    // k_gp_select, the scan of selCounts and k_gp_total; no records
+    const GpOut none{};
+#define FT_ARGS d, data, b, style, lead, invert, none, false, total, maxCount,                     \
+                nSelected ? nSelected : m.misc + 3, m.selBases, dummy, cfg, stream
+#define FT_CALL(K) \
+  (verb == kSearch ? launchGrepK<K, kSearch>(FT_ARGS) : launchGrepK<K, kMatch>(FT_ARGS))
+    e = [&]() -> hipError_t { REDGPU_KIND_SWITCH(FT_CALL) }();
+#undef FT_CALL
+#undef FT_ARGS
+    if (e != hipSuccess) return e;
+    if (nChunks) {
+      hipLaunchKernelGGL(k_ft_edges, dim3(uint32_t(small)), dim3(256), 0, stream, b, maxCount,
+                         m.prevSel, m.nextRev);
+      hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, m.prevSel, nChunks);
+      hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, m.nextRev, nChunks);
+      hipLaunchKernelGGL(k_ft_mark, dim3(uint32_t(small)), dim3(256), 0, stream, b, maxCount, before,
+                         after, m.prevSel, m.nextRev, m.emitBytes, m.emitLines);
+      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream,
+                         m.emitBytes, nChunks, m.partials);
+      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
+      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.emitBytes,
+                         nChunks, m.partials, m.outBases);
+    }
+    hipLaunchKernelGGL(k_ft_totals, dim3(1), dim3(1024), 0, stream, m.emitLines, nChunks,
+                       nChunks ? m.outBases + nChunks : nullptr, outLen,
+                       nEmitted ? nEmitted : m.misc + 4);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if ((phases & 2) && out && outCap && nChunks) {
+    hipLaunchKernelGGL(k_ft_write, dim3(uint32_t(small)), dim3(256), 0, stream, data, b,
+                       m.emitBytes, m.outBases, out, outCap);
+  }
+  return hipGetLastError();
 }
 #endif  // REDGPU_TU_GREP
 

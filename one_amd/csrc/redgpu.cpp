@@ -1458,6 +1458,69 @@ int redgpu_replace_text(const redgpu_dfa *dfa, int style, int do_leader, int onl
   return call.wait();
 }
 
+// raw text -> the selected lines and their context, as a text (k_filter_text.h): everything on
+// `stream`, nothing read back; phases as launchFilterText's
+static int filterTextDev(const redgpu_dfa *dfa, int style, int doLeader, int invert,
+                         uint64_t before, uint64_t after, uint64_t maxCount, const uint8_t *data,
+                         uint64_t len, uint8_t delim, uint64_t *nLines, uint64_t *nSelected,
+                         uint64_t *nEmitted, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                         int phases, hipStream_t s) {
+  if (int rc = checkRawText(dfa, outLen, "null out_len buffer", data, len, nullptr, &style))
+    return rc;
+  return rawTextDev(dfa, s, filterTextScratchBytes(len),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchFilterText(dfa->im->dev, style, doLeader ? 1 : 0, invert ? 1 : 0, before, after,
+                            maxCount, data, len, delim, nLines, nSelected, nEmitted, outLen, out,
+                            outCap, phases, scratch, cfg, s, name);
+  });
+}
+
+int redgpu_filter_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int invert,
+                           uint64_t before, uint64_t after, uint64_t max_count,
+                           const uint8_t *data, uint64_t len, uint8_t delim, uint64_t *n_lines,
+                           uint64_t *n_selected, uint64_t *n_emitted, uint64_t *out_len,
+                           uint8_t *out, uint64_t out_cap, void *stream) {
+  return filterTextDev(dfa, style, do_leader, invert, before, after, max_count, data, len, delim,
+                       n_lines, n_selected, n_emitted, out_len, out, out_cap, 3,
+                       static_cast<hipStream_t>(stream));
+}
+
+// host-buffer form, as redgpu_replace_text: the text goes up once; phase 1 leaves the sizes, the
+// bitmaps and the chunks' output bases in the stream's scratch, the device output is sized from
+// *out_len, phase 2 copies the runs, and min(*out_len, out_cap) bytes come back
+int redgpu_filter_text(const redgpu_dfa *dfa, int style, int do_leader, int invert, uint64_t before,
+                       uint64_t after, uint64_t max_count, const uint8_t *data, uint64_t len,
+                       uint8_t delim, uint64_t *n_lines, uint64_t *n_selected, uint64_t *n_emitted,
+                       uint64_t *out_len, uint8_t *out, uint64_t out_cap) {
+  if (int rc = checkRawText(dfa, out_len, "null out_len buffer", data, len, nullptr, &style))
+    return rc;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 4, "sizes");
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return filterTextDev(dfa, style, do_leader, invert, before, after, max_count, dData, len, delim,
+                         dSizes, dSizes + 1, dSizes + 2, dSizes + 3, nullptr, 0, 1, call.stream());
+  });
+  uint64_t sizes[4] = {0, 0, 0, 0};
+  call.download(sizes, dSizes, 4, "sizes");
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = sizes[0];
+  if (n_selected) *n_selected = sizes[1];
+  if (n_emitted) *n_emitted = sizes[2];
+  *out_len = sizes[3];
+  const uint64_t put = sizes[3] < out_cap ? sizes[3] : out_cap;
+  if (!out || !put) return REDGPU_OK;
+  // (the streams are drained: growing the slot waits for nothing)
+  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
+  call.run([&] {
+    return filterTextDev(dfa, style, do_leader, invert, before, after, max_count, dData, len, delim,
+                         dSizes, dSizes + 1, dSizes + 2, dSizes + 3, dOut, put, 2, call.stream());
+  });
+  call.download(out, dOut, put, "out");
+  return call.wait();
+}
+
 int redgpu_split_lines(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                        uint64_t *offsets, uint64_t cap, uint64_t *n_lines) {
   if (int rc = checkHandle(dfa)) return rc;

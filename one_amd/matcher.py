@@ -1215,6 +1215,56 @@ def replace_text(exe, data, repl, style=styLast, do_leader=True, max_count=1 << 
     return int(nl.value), int(nr.value), buf[:int(olen.value)].tobytes()
 
 
+def filter_text(exe, data, style=styInstant, do_leader=True, *, invert=False, before=0, after=0,
+                max_count=1 << 62, delim=b"\n", out=None, out_cap=None):
+    """redgpu_filter_text[_dev]: grep - the delimiter-terminated lines of a raw text buffer that
+    search<style,doLeader> selects (grep_text's rule; invert=True is grep -v), the first max_count
+    of them (grep -m), with `before` lines in front of and `after` lines behind each (grep -B /
+    -A), put together as a text: every emitted line once, in text order, with its delimiter, no
+    group separator.  The tail behind the last delimiter is not a line and is never emitted.
+    Host input -> (n_lines, n_selected, n_emitted, bytes).
+    A CUDA uint8 tensor needs out (a contiguous uint8 CUDA tensor to write into) or out_cap (one
+    of that size is made; 0 gives the sizes only) -> (n_lines, n_selected, n_emitted, out_len,
+    out): the counts as 1-element int64 tensors, asynchronously on the current stream and without
+    any read-back; out_len may exceed the room, bytes of out from min(out_len, room) on are
+    untouched.  The output is a raw text that every text verb accepts."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    style, lead, inv = int(style), 1 if do_leader else 0, 1 if invert else 0
+    before, after, max_count = int(before), int(after), int(max_count)
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = data.device
+        if out is None and out_cap is None:
+            raise RedExceptApi("device filter_text needs out or out_cap (room for the output)")
+        if out is None:
+            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
+        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
+              not out.is_contiguous() or out.device != dev):
+            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
+        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        cnt = torch.empty(4, dtype=torch.int64, device=dev)
+        _check(l.redgpu_filter_text_dev(
+            exe._h, style, lead, inv, before, after, max_count,
+            data.data_ptr() if data.numel() else None, data.numel(), d, cnt.data_ptr(),
+            cnt.data_ptr() + 8, cnt.data_ptr() + 16, cnt.data_ptr() + 24,
+            out.data_ptr() if room else None, room, torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], cnt[2:3], cnt[3:4], out
+    if out is not None or out_cap is not None:
+        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    a = _host_u8(data)
+    nl, ns, ne, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    # the output is no longer than the text
+    cap = int(a.size)
+    buf = np.zeros(max(cap, 1), dtype=np.uint8)
+    _check(l.redgpu_filter_text(
+        exe._h, style, lead, inv, before, after, max_count, a.ctypes.data if a.size else None,
+        a.size, d, C.byref(nl), C.byref(ns), C.byref(ne), C.byref(olen), buf.ctypes.data, cap))
+    return int(nl.value), int(ns.value), int(ne.value), buf[:int(olen.value)].tobytes()
+
+
 class StatefulMatcher:
     """Mirror of zezax::red::StatefulMatcher (include/Matcher.h:770-792): `advance(byte)` and
     `result()`; `advance_bytes` feeds a whole chunk in one kernel launch.  The executable must
