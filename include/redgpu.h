@@ -722,6 +722,58 @@ int redgpu_filter_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int 
                            uint64_t *n_selected, uint64_t *n_emitted, uint64_t *out_len,
                            uint8_t *out, uint64_t out_cap, void *stream);
 
+/* grep -o as a text: raw text in, every match of every line out as bytes, one per output line -
+ * Red::collect (lib/Red.cpp:103-116) inside the line loop of tools/skim_red.cpp:36-46, over the lines
+ * lib/Util.cpp:109-130 cuts, printing the match; redgpu_collect_text's text-valued form.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter are not a line and contribute nothing.
+ *  - The PIECES of line k are the spans replace<styLast,false>(line k, ., all) substitutes
+ *    (include/Matcher.h:643-706), in order.  Piece j is line[a_j, e_j): e_j is the end of
+ *    Red::collect's j-th Outcome on that line (redgpu_collect_text's end[] minus the line's begin),
+ *    a_j the position at which the successful search<styLast,false> attempt began - the first
+ *    position at or behind e_{j-1} from which the DFA accepts.  a_j <= start_j always (a loose-start
+ *    DFA reports as start where it left its initial state, which lies behind a_j and can lie behind
+ *    e_j: text[start:end] is NOT the match there), and a_j < e_j: a piece is never empty and never
+ *    holds the delimiter.  The chain is Red::collect's and replaceCore's - the same one: the next
+ *    attempt begins at e_j.  No style or leader argument, as in redgpu_collect_text.
+ *  - Only the first max_per_line pieces of a line are emitted: 1 << 62 emits all of them, 1 the
+ *    first match of every line, 0 nothing (*n_matches = 0, *out_len = 0).
+ *  - The output is every emitted piece followed by delim, in line order, then match order: a raw
+ *    text every text verb accepts (extract -> tally / grep / extract with another DFA stays on the
+ *    device).
+ *  - *n_matches = pieces emitted - with an unbounded max_per_line redgpu_collect_text's n_matches,
+ *    and output line j is the bytes of its record j; *out_len = the length of the whole output,
+ *    whatever out_cap is: the sum of the piece lengths plus *n_matches; *n_lines = delimiters found.
+ *    n_lines and n_matches may be NULL, each on its own; out_len is required.
+ *  - out == NULL or out_cap == 0 gives the sizes only, and no line is walked a second time.
+ *    Otherwise exactly the first min(*out_len, out_cap) bytes of the output are written - the cut
+ *    may fall inside a piece or on a separator - and bytes of out from there on are NOT written
+ *    (redgpu_filter_text's rule): out may be the middle of a larger buffer.  out must not overlap
+ *    data.
+ *  - REDGPU_EAPI for a NULL handle, a NULL out_len, a NULL data with len > 0 (the argument checks
+ *    run before the handle's device is looked at) and for a REDGPU_DEVICE_NONE handle;
+ *    REDGPU_ELIMIT for a text redgpu_split_lines refuses.  In every error case nothing of the
+ *    caller's is written.
+ *  - An empty text, or one without a delimiter: all three counts are 0 and nothing is written to
+ *    out (the _dev form writes the counts on the stream).
+ *  - A single line of megabytes is walked by one lane, which also writes its pieces: correct, and
+ *    slow.
+ * redgpu_last_kernel() says "k_extract_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - nothing is read
+ * back, and no per-line or per-match array is needed from the caller or in scratch (the lines are
+ * driven from the split's delimiter bitmap, a lane's place in the output comes from a scan over
+ * per-chunk sums and a prefix inside the wave; scratch is the two bitmaps and a few words per
+ * 16 KiB chunk, what redgpu_replace_text_dev takes: len / 4 + 44 bytes per chunk + 8 bytes per
+ * 1,024 chunks + 72, rounded up to 16, from the thread's pool).
+ * redgpu_extract_text: host buffers, as redgpu_filter_text - one upload of the text, a sizes pass,
+ * a device output sized from *out_len, and min(*out_len, out_cap) bytes downloaded. */
+int redgpu_extract_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                        uint64_t max_per_line, uint64_t *n_lines, uint64_t *n_matches,
+                        uint64_t *out_len, uint8_t *out, uint64_t out_cap);
+int redgpu_extract_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                            uint64_t max_per_line, uint64_t *n_lines, uint64_t *n_matches,
+                            uint64_t *out_len, uint8_t *out, uint64_t out_cap, void *stream);
+
 /* Measurement aid, no counterpart in the reference: one streaming read of `bytes` of device
  * memory (16-byte aligned) on the handle's device, asynchronous on `stream` - the read-bandwidth
  * calibration bench.py reports beside the roofline.  `sink` is a device uint32 the kernel may

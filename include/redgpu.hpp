@@ -334,6 +334,28 @@ inline size_t filterText(const Executable &exec, Style style, bool doLeader, std
   return size_t(selected);
 }
 
+// grep -o as a text (redgpu_extract_text): every match of every line of a text blob put in `out`,
+// one per line - the bytes replace<styLast,false> would substitute, each followed by the delimiter,
+// in text order; at most maxPerLine of a line (1 = its first match).  Output line j is the bytes of
+// collectText's record j, from where the matching attempt began (at or before start_) to end_.
+// Returns the matches emitted; *lines = delimiters found.  `out` is sized from a first call that
+// only sizes.
+inline size_t extractText(const Executable &exec, std::string_view text, std::string &out,
+                          size_t maxPerLine = SIZE_MAX, char delim = '\n',
+                          size_t *lines = nullptr) {
+  const Byte *p = reinterpret_cast<const Byte *>(text.data());
+  const uint64_t most = maxPerLine > (uint64_t(1) << 62) ? uint64_t(1) << 62 : uint64_t(maxPerLine);
+  uint64_t found = 0, nLines = 0, outLen = 0;
+  throwOnError(redgpu_extract_text(exec.handle(), p, text.size(), Byte(delim), most, &nLines,
+                                   &found, &outLen, nullptr, 0));
+  out.resize(size_t(outLen));
+  if (outLen)
+    throwOnError(redgpu_extract_text(exec.handle(), p, text.size(), Byte(delim), most, &nLines,
+                                     &found, &outLen, reinterpret_cast<Byte *>(out.data()), outLen));
+  if (lines) *lines = size_t(nLines);
+  return size_t(found);
+}
+
 // ---- several GPUs of one node: one image per device, contiguous shards, results in the caller's
 // arrays - the device form of tools/thr_red.cpp:84-91 (N workers over one shared Red).  devices
 // may name a device more than once (the shards then share it). ----------------------------------

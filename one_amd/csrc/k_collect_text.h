@@ -29,9 +29,13 @@
 // repeated search<styLast,false> from the end of the previous match - k_lists.h:k_collect's loop
 // body, with the record handed to f(accepting state, start, end) instead of stored; f returns
 // whether the chain goes on.  Returns the matches found (those f saw).
+// An f that takes a fourth argument is also handed where the attempt that matched BEGAN: [at, end)
+// is the span replaceCore substitutes, and at <= start (a loose-start DFA leaves its initial state
+// later).  For an f of three arguments nothing of this exists: the code is what it was.
 template <class T, class F>
 __device__ __forceinline__ uint64_t collectLane(const T &tab, const LaneCtx &c, const uint8_t *p,
                                                 uint64_t n, F &&f) {
+  constexpr bool kWantsAt = std::is_invocable_v<F &, uint32_t, uint64_t, uint64_t, uint64_t>;
   const StartFilter flt{c.startWord[0], c.startCount[0] <= 4 ? c.startCount[0] : 0u,
                         c.start2Word[0], c.start2Count[0] <= 4 ? c.start2Count[0] : 0u, false};
   uint64_t found = 0, pos = 0;
@@ -43,6 +47,7 @@ __device__ __forceinline__ uint64_t collectLane(const T &tab, const LaneCtx &c, 
     bool got = false;
     uint32_t accS = 0;
     uint64_t mS = 0, mE = 0;
+    [[maybe_unused]] uint64_t mA = 0;
     walkBytesPeek(p, pos, n, flt, [] {}, [&](uint32_t byte, uint64_t i, uint32_t nextByte) -> bool {
       uint32_t st = tab.next(c.init, byte);
       bool any = false;
@@ -68,11 +73,14 @@ __device__ __forceinline__ uint64_t collectLane(const T &tab, const LaneCtx &c, 
       }
       if (!any) return !(c.suffixClosed && alive);  // L = SIGMA* L: no later start can match either
       got = true; accS = aS; mS = ms; mE = me;
+      if constexpr (kWantsAt) mA = i;
       return false;
     });
     if (!got) break;
     ++found;
-    if (!f(accS, mS, mE)) break;
+    if constexpr (kWantsAt) {
+      if (!f(accS, mS, mE, mA)) break;
+    } else if (!f(accS, mS, mE)) break;
     pos = mE;
   }
   return found;

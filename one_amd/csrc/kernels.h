@@ -272,6 +272,21 @@ hipError_t launchFilterText(const DevDfa &dfa, int style, int doLeader, int inve
                             int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                             const char **kernelName);
 
+// grep -o's output as a text (k_extract_text.h): the first maxPerLine pieces of every line of
+// launchSplitLines' rule - a piece is [where the matching attempt began, the match's end), the chain
+// launchCollectText's - each followed by delim, in text order: *nMatches = pieces emitted, *outLen =
+// their bytes with the delimiters, the first min(*outLen, outCap) bytes in out and nothing behind them
+// (out, nLines and nMatches may be null).  hand: pieces from this length on are copied by the whole
+// wave (0 = the default).  phases: 1 = index and size, 2 = write out from what phase 1 left in
+// scratch, 3 = both.  scratch: extractTextScratchBytes(len) bytes of device memory, 16-byte
+// aligned.  *kernelName = "k_extract_text".
+uint64_t extractTextScratchBytes(uint64_t len);
+hipError_t launchExtractText(const DevDfa &dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                             uint64_t maxPerLine, uint32_t hand, uint64_t *nLines,
+                             uint64_t *nMatches, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                             int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                             const char **kernelName);
+
 // bench.py's read-bandwidth calibration: one streaming pass over `bytes` (16-byte aligned).
 hipError_t launchDiagRead(const void *data, uint64_t bytes, uint32_t *sink, int numCUs,
                           hipStream_t stream);

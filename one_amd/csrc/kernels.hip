@@ -51,7 +51,10 @@
 //   k_filter_text.h   k_ft_*: grep's output with -A / -B context over a raw text - k_grep.h's select pass,
 //                     the context as arithmetic on line numbers over the two bitmaps, a scan, and a
 //                     write pass that only copies runs of emitted lines
-//   k_diag.h          bench.py's calibration kernels
+//   k_extract_text.h  k_xt_*: grep -o's output as a text - k_collect_text.h's chain per line, a sizing
+//                     pass, a scan, and a write pass whose lanes assemble their pieces in a 16-byte
+//                     register window
+//   k_diag.h         bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
 //   here              the dispatch: launchBatch / launchBatches and friends - which kernel runs what.
@@ -63,11 +66,11 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled seven times in parallel (Makefile: -DREDGPU_TU=1/2/.../7): the templates are
+// This file is compiled eight times in parallel (Makefile: -DREDGPU_TU=1/2/.../8): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
 // 3 = everything else and the dispatch, 4 = k_grep and k_filter_text (which runs k_grep's select), 5 = k_collect_text, 6 = k_replace_text,
-// 7 = k_tally_text.
+// 7 = k_tally_text, 8 = k_extract_text.
 // REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
@@ -79,6 +82,7 @@
 #define REDGPU_TU_COLLECT_TEXT (REDGPU_TU == 0 || REDGPU_TU == 5)
 #define REDGPU_TU_REPLACE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 6)
 #define REDGPU_TU_TALLY_TEXT (REDGPU_TU == 0 || REDGPU_TU == 7)
+#define REDGPU_TU_EXTRACT_TEXT (REDGPU_TU == 0 || REDGPU_TU == 8)
 
 // return CALL(KIND) for the table kind of the DevDfa `d` in scope: a launcher's instantiation per kind
 #define REDGPU_KIND_SWITCH(CALL)                                                          \
@@ -122,6 +126,7 @@ namespace {
 #include "k_tally_text.h"
 #include "k_replace_text.h"
 #include "k_filter_text.h"
+#include "k_extract_text.h"
 
 } // namespace
 
@@ -1199,10 +1204,11 @@ hipError_t launchTallyText(const DevDfa &d, int what, int style, int doLeader, c
 }
 #endif  // REDGPU_TU_TALLY_TEXT
 
-#if REDGPU_TU_REPLACE_TEXT
-// sed over a raw text (k_replace_text.h): the line index (launchTextIndex), then the k_rt_* passes
-// around k_misc.h's 64-bit scan.  scratch: replaceTextScratchBytes(len) bytes, 16-byte aligned:
-// the two bitmaps, and 44 bytes per chunk, 8 per 1,024 chunks and 72, rounded up to 16.
+#if REDGPU_TU_REPLACE_TEXT || REDGPU_TU_EXTRACT_TEXT
+// the scratch of sed and of grep -o's text, for a text of nChunks split chunks: what launchTextIndex
+// fills, the output bytes and the replacements (extract_text: the pieces) per chunk, the scan's
+// arrays, eight spare words, the two bitmaps - the two bitmaps, and 44 bytes per chunk, 8 per 1,024
+// chunks and 72, rounded up to 16
 struct ReplaceScratch {
   uint64_t *bases, *open, *outBytes, *replCounts;  // [nChunks] each
   uint64_t *outBases;                              // [nChunks + 1]
@@ -1227,7 +1233,11 @@ struct ReplaceScratch {
     bytes = c.at;
   }
 };
+#endif
 
+#if REDGPU_TU_REPLACE_TEXT
+// sed over a raw text (k_replace_text.h): the line index (launchTextIndex), then the k_rt_* passes
+// around k_misc.h's 64-bit scan.  scratch: replaceTextScratchBytes(len) bytes, 16-byte aligned.
 uint64_t replaceTextScratchBytes(uint64_t len) {
   return ReplaceScratch(nullptr, splitChunks(len)).bytes;
 }
@@ -1279,6 +1289,53 @@ hipError_t launchReplaceText(const DevDfa &d, int style, int doLeader, int onlyC
   return hipGetLastError();
 }
 #endif  // REDGPU_TU_REPLACE_TEXT
+
+#if REDGPU_TU_EXTRACT_TEXT
+// grep -o's output as a text (k_extract_text.h): the line index (launchTextIndex), then the k_xt_*
+// passes around k_misc.h's 64-bit scan.  scratch: extractTextScratchBytes(len) bytes, 16-byte
+// aligned - what sed takes (ReplaceScratch: replCounts holds the chunks' pieces).
+uint64_t extractTextScratchBytes(uint64_t len) {
+  return ReplaceScratch(nullptr, splitChunks(len)).bytes;
+}
+
+hipError_t launchExtractText(const DevDfa &d, const uint8_t *data, uint64_t len, uint8_t delim,
+                             uint64_t maxPerLine, uint32_t hand, uint64_t *nLines,
+                             uint64_t *nMatches, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                             int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                             const char **kernelName) {
+  *kernelName = "k_extract_text";
+  const uint64_t nChunks = splitChunks(len);
+  const ReplaceScratch m(scratch, nChunks);
+  const GpBufs b{m.masks, m.hitMasks, m.bases, m.open, nullptr, nullptr, nChunks};
+  const XtBufs x{m.outBytes, m.replCounts, m.outBases};
+  if (hand == 0) hand = kXtHand;
+#define XT_CALL(K) \
+  launchExtractTextK<K>(d, data, len, b, x, maxPerLine, delim, hand, size, out, outCap, cfg, stream)
+  auto pass = [&](bool size) { REDGPU_KIND_SWITCH(XT_CALL) };
+#undef XT_CALL
+  if (phases & 1) {
+    hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                   m.hitMasks, m.misc, cfg.numCUs, stream);
+    if (e != hipSuccess) return e;
+    if (nChunks) {
+      e = pass(true);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream,
+                         m.outBytes, nChunks, m.partials);
+      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
+      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.outBytes,
+                         nChunks, m.partials, m.outBases);
+    }
+    hipLaunchKernelGGL(k_xt_totals, dim3(1), dim3(1024), 0, stream, m.replCounts, nChunks,
+                       nChunks ? m.outBases + nChunks : nullptr, outLen,
+                       nMatches ? nMatches : m.misc + 2);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if ((phases & 2) && out && outCap && nChunks) return pass(false);
+  return hipGetLastError();
+}
+#endif  // REDGPU_TU_EXTRACT_TEXT
 
 #if REDGPU_TU_GENERIC
 hipError_t launchBatches(const DevDfa &d, const Batch *bs, uint32_t nb, int verb, int style,

@@ -1521,6 +1521,66 @@ int redgpu_filter_text(const redgpu_dfa *dfa, int style, int do_leader, int inve
   return call.wait();
 }
 
+// raw text -> every match of every line as bytes, one per output line (k_extract_text.h):
+// everything on `stream`, nothing read back; phases as launchExtractText's
+static int extractTextDev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                          uint64_t maxPerLine, uint64_t *nLines, uint64_t *nMatches,
+                          uint64_t *outLen, uint8_t *out, uint64_t outCap, int phases,
+                          hipStream_t s) {
+  if (int rc = checkRawText(dfa, outLen, "null out_len buffer", data, len, nullptr, nullptr))
+    return rc;
+  // REDGPU_XT_HAND=n: pieces of n bytes or more go to the whole wave (measurements, DESIGN 4.3k;
+  // unset or 0 = the kernel's default)
+  const char *env = getenv("REDGPU_XT_HAND");
+  const uint32_t hand = env ? uint32_t(strtoul(env, nullptr, 10)) : 0u;
+  return rawTextDev(dfa, s, extractTextScratchBytes(len),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchExtractText(dfa->im->dev, data, len, delim, maxPerLine, hand, nLines, nMatches,
+                             outLen, out, outCap, phases, scratch, cfg, s, name);
+  });
+}
+
+int redgpu_extract_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                            uint64_t max_per_line, uint64_t *n_lines, uint64_t *n_matches,
+                            uint64_t *out_len, uint8_t *out, uint64_t out_cap, void *stream) {
+  return extractTextDev(dfa, data, len, delim, max_per_line, n_lines, n_matches, out_len, out,
+                        out_cap, 3, static_cast<hipStream_t>(stream));
+}
+
+// host-buffer form, as redgpu_filter_text: the text goes up once; phase 1 leaves the sizes, the
+// bitmaps and the chunks' output bases in the stream's scratch, the device output is sized from
+// *out_len, phase 2 assembles the pieces, and min(*out_len, out_cap) bytes come back
+int redgpu_extract_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                        uint64_t max_per_line, uint64_t *n_lines, uint64_t *n_matches,
+                        uint64_t *out_len, uint8_t *out, uint64_t out_cap) {
+  if (int rc = checkRawText(dfa, out_len, "null out_len buffer", data, len, nullptr, nullptr))
+    return rc;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 3, "sizes");
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return extractTextDev(dfa, dData, len, delim, max_per_line, dSizes, dSizes + 1, dSizes + 2,
+                          nullptr, 0, 1, call.stream());
+  });
+  uint64_t sizes[3] = {0, 0, 0};
+  call.download(sizes, dSizes, 3, "sizes");
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = sizes[0];
+  if (n_matches) *n_matches = sizes[1];
+  *out_len = sizes[2];
+  const uint64_t put = sizes[2] < out_cap ? sizes[2] : out_cap;
+  if (!out || !put) return REDGPU_OK;
+  // (the streams are drained: growing the slot waits for nothing)
+  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
+  call.run([&] {
+    return extractTextDev(dfa, dData, len, delim, max_per_line, dSizes, dSizes + 1, dSizes + 2,
+                          dOut, put, 2, call.stream());
+  });
+  call.download(out, dOut, put, "out");
+  return call.wait();
+}
+
 int redgpu_split_lines(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                        uint64_t *offsets, uint64_t cap, uint64_t *n_lines) {
   if (int rc = checkHandle(dfa)) return rc;

@@ -1265,6 +1265,58 @@ def filter_text(exe, data, style=styInstant, do_leader=True, *, invert=False, be
     return int(nl.value), int(ns.value), int(ne.value), buf[:int(olen.value)].tobytes()
 
 
+def extract_text(exe, data, *, max_per_line=1 << 62, delim=b"\n", out=None, out_cap=None):
+    """redgpu_extract_text[_dev]: grep -o as a text - every match of every delimiter-terminated
+    line of a raw text buffer (Red::collect's chain, collect_text's records), as bytes: the span
+    replace<styLast,false> would substitute, from where the matching attempt began (at or before
+    the record's start) to the record's end, each followed by the delimiter, in text order.  Only
+    the first max_per_line matches of a line are emitted (1 = the first of every line, 0 = none).
+    Host input -> (n_lines, n_matches, bytes).
+    A CUDA uint8 tensor needs out (a contiguous uint8 CUDA tensor to write into) or out_cap (one
+    of that size is made; 0 gives the sizes only) -> (n_lines, n_matches, out_len, out): the
+    counts as 1-element int64 tensors, asynchronously on the current stream and without any
+    read-back; out_len may exceed the room, bytes of out from min(out_len, room) on are
+    untouched.  The output is a raw text that every text verb accepts."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    max_per_line = int(max_per_line)
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = data.device
+        if out is None and out_cap is None:
+            raise RedExceptApi("device extract_text needs out or out_cap (room for the output)")
+        if out is None:
+            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
+        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
+              not out.is_contiguous() or out.device != dev):
+            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
+        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        cnt = torch.empty(3, dtype=torch.int64, device=dev)
+        _check(l.redgpu_extract_text_dev(
+            exe._h, data.data_ptr() if data.numel() else None, data.numel(), d, max_per_line,
+            cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 16,
+            out.data_ptr() if room else None, room, torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], cnt[2:3], out
+    if out is not None or out_cap is not None:
+        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    a = _host_u8(data)
+    nl, nm, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    # first guess: output about as long as the input (it can reach twice that: one-byte pieces
+    # and their delimiters); once more with the exact size otherwise
+    cap = int(a.size + 64)
+    for _ in range(2):
+        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+        _check(l.redgpu_extract_text(
+            exe._h, a.ctypes.data if a.size else None, a.size, d, max_per_line, C.byref(nl),
+            C.byref(nm), C.byref(olen), buf.ctypes.data, cap))
+        if int(olen.value) <= cap:
+            break
+        cap = int(olen.value)
+    return int(nl.value), int(nm.value), buf[:int(olen.value)].tobytes()
+
+
 class StatefulMatcher:
     """Mirror of zezax::red::StatefulMatcher (include/Matcher.h:770-792): `advance(byte)` and
     `result()`; `advance_bytes` feeds a whole chunk in one kernel launch.  The executable must
