@@ -1428,12 +1428,8 @@ hipError_t launchBatch(const DevDfa &d, const Batch &b, int verb, int style, int
     if (handled || fe != hipSuccess) return fe;
   }
 
-  {
-    *kernelName = (verb == kScan || verb == kSearch) && scanMarkable(d, lead) &&
-                          !cfg.forceGeneric
-                      ? "k_scan_marked" : "k_generic";
-  }
-#define GE_CALL(K) launchGeneric<K>(d, b, verb, style, lead, cfg, stream)
+  // (launchGeneric names the kernel it launches: k_scan_marked or k_generic)
+#define GE_CALL(K) launchGeneric<K>(d, b, verb, style, lead, cfg, stream, kernelName)
   REDGPU_KIND_SWITCH(GE_CALL)
 #undef GE_CALL
 }

@@ -12,9 +12,11 @@ hipError_t setLds(K kernel, size_t bytes) {
 
 #include "k_chunk.h"
 
+// *kernelName = the kernel this launches: "k_scan_marked" or "k_generic" (decided here, where the
+// marks' LDS is sized, so the reported name cannot differ from the kernel that ran)
 template <int KIND>
 hipError_t launchGeneric(const DevDfa &d, const Batch &b, int verb, int style, int lead,
-                         const LaunchCfg &cfg, hipStream_t stream) {
+                         const LaunchCfg &cfg, hipStream_t stream, const char **kernelName) {
   constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
   constexpr int kThreads = kLds ? 1024 : 256;
   const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
@@ -49,6 +51,7 @@ hipError_t launchGeneric(const DevDfa &d, const Batch &b, int verb, int style, i
     const size_t markLds = 512 + ((ldsTableBytes<KIND>(d) + 15) & ~size_t(15)) + kMarkBytes +
                            size_t(kScanThreads) * (6 * 4 + 8) + 32 + 256;
     if (markLds <= 158 * 1024) {
+      *kernelName = "k_scan_marked";
       hipError_t e_ = verb == kScan ? setLds(k_scan_marked<KIND, kScanThreads, kScan>, markLds)
                                     : setLds(k_scan_marked<KIND, kScanThreads, kSearch>, markLds);
       if (e_ != hipSuccess) return e_;
@@ -67,6 +70,7 @@ hipError_t launchGeneric(const DevDfa &d, const Batch &b, int verb, int style, i
   }
   // whole-line walks over ragged lines profit from the length bucketing; walks that die in
   // their first bytes (early-death DFAs under check / match) do not care how long the line is
+  *kernelName = "k_generic";
   Batch pb = sb;
   if (b.offsets && !(d.earlyDeath && (verb == kCheck || verb == kMatch))) {
     hipError_t pe = prepareRagged(sb, cfg, stream, false, pb);
