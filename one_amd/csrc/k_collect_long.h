@@ -1,5 +1,5 @@
 // k_collect_long.h - Red::collect (lib/Red.cpp:103-116) over ONE long text, across the chip
-// (included by kernels.hip inside its namespace, after k_lists.h).
+// (included by kernels.hip inside its namespace, after k_long.h).
 //
 // collect is a chain: p0 = 0, m_k = the first position >= p_k whose anchored attempt
 // (searchCore's inner loop, include/Matcher.h:557-640, <styLast, false>) matches, p_{k+1} = the
@@ -17,7 +17,7 @@
 //                kClRounds rounds at most, each a no-op once one queued nothing;
 //   k_cl_check / k_cl_serial  the first chunk still open, and one lane that walks on from it
 //                in order, unbounded (the chains that never resynchronise: "aa" on a run of a);
-//   fold         k_cl_scan1 / k_cl_scan2, an exclusive scan of the per-chunk counts (the total
+//   fold         k_long.h's scan kernels, an exclusive scan of the per-chunk counts (the total
 //                is the call's count), and k_cl_scatter, a wave per chunk, up to `cap` records.
 // Speculative walks are bounded: a chunk walks at most `budget` bytes of attempts past their
 // first byte (an attempt that never dies would otherwise make every chunk walk to the end of
@@ -27,7 +27,7 @@
 // byte.  (A record's start is the attempt's last "left the initial state", Matcher.h:582-587:
 // two attempts can report the same one, so chains are compared by attempt position.)
 // The same chain serves replaceCore over one text (k_replace_long.h): every kernel here takes a
-// MODE - kClCollect is the above, kClReplace swaps the attempt for replaceCore's (ClAttempt: style
+// MODE - kClCollect is the above, kClReplace swaps the attempt for replaceCore's (LongAttempt: style
 // and leader test) and keeps lean slots (attempt position + end, 12 bytes; res and rst unused).
 #pragma once
 
@@ -61,86 +61,26 @@ struct ClBufs {
 
 // MODE of the chain kernels: whose attempt runs at a position, and what a record slot keeps
 constexpr int kClCollect = 0;  // k_collect's attempt (searchCore <styLast, false>); result, at, start, end
-constexpr int kClReplace = 1;  // replaceCore's (k_replace_long.h): ClAttempt's style and leader; at, end
+constexpr int kClReplace = 1;  // replaceCore's (k_replace_long.h): LongAttempt's style and leader; at, end
 
-struct ClAttempt {
-  int style = kStyLast;
-  int lead = 0;
-};
-
-// The chain over the attempt positions [q, hi) of p[0, n).  emit(result, at, start, end) per match,
-// false = stop here (the return value is then meaningless).  Returns the exit, or kClOpen when the
-// attempts walked more than `budget` bytes past their first one.  The attempt is k_collect's, or
-// (kClReplace) replaceCore's under a.style with the leader test: Instant stops at the first
-// accept, First and Tangent at the first non-accept behind one (First also where the result
-// changes), Full forgets its accept at every non-accept; result and start are then 0.
+// The chain over the attempt positions [q, hi) of p[0, n): k_long.h's longChain from where the
+// match before ended.  emit(result, at, start, end) per match, false = stop here (the return value
+// is then meaningless).  Returns the exit, or kClOpen when the attempts walked more than `budget`
+// bytes past their first one.  The attempt is k_collect's, or (kClReplace) replaceCore's under
+// a.style with the leader test; result and start are then 0 and the attempt position.
 template <int MODE = kClCollect, class T, class E>
 __device__ __forceinline__ uint64_t clChain(const T &tab, const LaneCtx &c, const StartFilter &flt,
                                             const uint8_t *p, uint64_t n, uint64_t q, uint64_t hi,
-                                            uint64_t budget, E &&emit, const ClAttempt a = ClAttempt{}) {
+                                            uint64_t budget, E &&emit, const LongAttempt a = LongAttempt{}) {
   uint64_t pos = q;
   while (pos < hi) {
-    int how = 0;  // 1 = a match, 2 = suffix-closed stop, 3 = out of budget
-    uint32_t accS = 0;
-    uint64_t mA = 0, mS = 0, mE = 0;
-    walkBytesPeek(p, pos, hi, flt, [] {}, [&](uint32_t byte, uint64_t i, uint32_t nextByte) -> bool {
-      uint32_t st = tab.next(c.init, byte);
-      bool any = false;
-      uint64_t ms = i, me = i;
-      uint32_t aS = 0;
-      if (st >= c.firstAccept) { aS = st; me = i + 1; any = true; }
-      else if (st < c.nPureDead) return true;
-      else if (nextByte != kNoPeek && tab.next(st, nextByte) < c.nPureDead) return true;
-      int32_t prev = 0;  // (kClReplace, styFirst) the result of the accepts so far
-      if constexpr (MODE == kClReplace) {
-        if (a.lead && !lookingAt(c, p, i, n)) return true;
-        if (any && a.style == kStyFirst) prev = c.res[st];
-      }
-      const uint64_t lim = n - i - 1 > budget ? i + 1 + budget : n;
-      uint64_t at = i + 1;
-      auto stepOne = [&](uint32_t b2, uint64_t q2) -> bool {
-        const uint32_t was = st;
-        st = tab.next(st, b2);
-        at = q2 + 1;
-        const bool acc = st >= c.firstAccept;
-        if constexpr (MODE == kClReplace) {
-          if (acc) {
-            if (a.style == kStyFirst) {
-              const int32_t r = c.res[st];
-              if (prev && r != prev) return false;
-              prev = r;
-            }
-            aS = st; me = q2 + 1; any = true;
-            return a.style != kStyInstant;
-          }
-          if (a.style == kStyFull) any = false;
-          else if (any && (a.style == kStyFirst || a.style == kStyTangent)) return false;
-          return st >= c.nPureDead;
-        } else {
-          if (was == c.init && st != was) ms = q2;
-          if (acc) { aS = st; me = q2 + 1; any = true; }
-          return acc || st >= c.nPureDead;
-        }
-      };
-      uint64_t q2 = i + 1;
-      bool alive = !(MODE == kClReplace && any && a.style == kStyInstant);
-      for (uint32_t k = 0; k < 6 && q2 < lim && alive; ++k, ++q2) alive = stepOne(uint32_t(p[q2]), q2);
-      if (alive)
-        walkBytes(p, q2, lim, [&](uint32_t b2, uint64_t q3) -> bool { return alive = stepOne(b2, q3); });
-      budget -= at - i - 1;
-      if (alive && lim < n) { how = 3; return false; }
-      if (!any) {
-        if (c.suffixClosed && alive && !(MODE == kClReplace && a.lead)) { how = 2; return false; }  // L = SIGMA* L
-        return true;
-      }
-      how = 1; accS = aS; mA = i; mS = ms; mE = me;
-      return false;
-    });
-    if (how == 0) return hi;
-    if (how == 2) return n;
-    if (how == 3) return kClOpen;
-    if (!emit(MODE == kClReplace ? 0 : c.res[accS], mA, mS, mE)) return 0;
-    pos = mE;
+    const LongHit h = longChain<MODE == kClCollect, MODE == kClCollect>(tab, c, flt, p, n, pos, hi,
+                                                                        budget, a);
+    if (h.how == 0) return hi;
+    if (h.how == 2) return n;
+    if (h.how == 3) return kClOpen;
+    if (!emit(MODE == kClReplace ? 0 : c.res[h.acc], h.at, h.ms, h.me)) return 0;
+    pos = h.me;
   }
   return pos;
 }
@@ -151,9 +91,9 @@ __device__ __forceinline__ uint64_t clChain(const T &tab, const LaneCtx &c, cons
 template <int MODE = kClCollect, class T>
 __device__ void clRewalk(const T &tab, const LaneCtx &c, const StartFilter &flt, const uint8_t *p,
                          uint64_t n, const ClBufs &b, uint64_t j, uint64_t q, uint64_t budget,
-                         const ClAttempt a = ClAttempt{}) {
-  const uint64_t lo = j * b.chunk;
-  const uint64_t hi = lo + b.chunk < n ? lo + b.chunk : n;
+                         const LongAttempt a = LongAttempt{}) {
+  const LongSpan sp = longSpan(j, b.chunk, n);
+  const uint64_t lo = sp.lo, hi = sp.hi;
   const uint64_t base = j * b.slots;
   const uint32_t cnt0 = b.cnt[j];
   const uint64_t oldExit = b.exit[j];
@@ -213,19 +153,6 @@ __device__ void clRewalk(const T &tab, const LaneCtx &c, const StartFilter &flt,
   }, a);
 }
 
-template <int KIND>
-__device__ __forceinline__ LaneCtx clCtx(const DevDfa &d, uint8_t *lds) {
-  LaneCtx c{lds, lds + 256, resOf<KIND>(d, lds), d.init, d.leaderNext, d.nPureDead, d.firstAccept,
-            d.leaderLen};
-  c.suffixClosed = d.suffixClosed;
-  return c;
-}
-
-__device__ __forceinline__ StartFilter clFilter(const DevDfa &d) {
-  return StartFilter{d.startFreeWord, d.startFreeCount <= 4 ? d.startFreeCount : 0u,
-                     d.start2FreeWord, d.start2FreeCount <= 4 ? d.start2FreeCount : 0u, false};
-}
-
 __global__ void __launch_bounds__(64) k_cl_init(ClBufs b) {
   if (threadIdx.x < uint32_t(kClRounds)) b.ctl[threadIdx.x] = 0;
   if (threadIdx.x == uint32_t(kClRounds)) b.ctl[kClRounds] = uint32_t(b.m);
@@ -234,15 +161,15 @@ __global__ void __launch_bounds__(64) k_cl_init(ClBufs b) {
 // every chunk from its guessed entry (chunk 0 from 0, exactly)
 template <int KIND, int kThreads, int MODE = kClCollect>
 __global__ void __launch_bounds__(kThreads)
-k_cl_walk(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, uint64_t budget, ClAttempt a) {
+k_cl_walk(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, uint64_t budget, LongAttempt a) {
   extern __shared__ __align__(16) uint8_t lds[];
   const Tab<KIND> tab = stageTab<KIND, kThreads>(d, lds);
-  const LaneCtx c = clCtx<KIND>(d, lds);
-  const StartFilter flt = clFilter(d);
+  const LaneCtx c = longCtx<KIND>(d, lds);
+  const StartFilter flt = longFilter(d);
   const uint64_t step = uint64_t(gridDim.x) * kThreads;
   for (uint64_t j = uint64_t(blockIdx.x) * kThreads + threadIdx.x; j < b.m; j += step) {
-    const uint64_t lo = j * b.chunk;
-    const uint64_t hi = lo + b.chunk < n ? lo + b.chunk : n;
+    const LongSpan sp = longSpan(j, b.chunk, n);
+    const uint64_t lo = sp.lo, hi = sp.hi;
     uint64_t q = 0;
     if (j) {
       q = clChain<MODE>(tab, c, flt, p, n, lo > kClWarm ? lo - kClWarm : 0, lo, budget,
@@ -282,12 +209,12 @@ __global__ void __launch_bounds__(256) k_cl_resolve(ClBufs b, int round) {
 template <int KIND, int kThreads, int MODE = kClCollect>
 __global__ void __launch_bounds__(kThreads)
 k_cl_rewalk(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, int round, uint64_t budget,
-            ClAttempt a) {
+            LongAttempt a) {
   extern __shared__ __align__(16) uint8_t lds[];
   if (b.ctl[round] == 0) return;  // uniform: nothing queued this round
   const Tab<KIND> tab = stageTab<KIND, kThreads>(d, lds);
-  const LaneCtx c = clCtx<KIND>(d, lds);
-  const StartFilter flt = clFilter(d);
+  const LaneCtx c = longCtx<KIND>(d, lds);
+  const StartFilter flt = longFilter(d);
   const uint32_t cnt = b.ctl[round];
   const uint64_t step = uint64_t(gridDim.x) * kThreads;
   for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < cnt; i += step) {
@@ -310,12 +237,12 @@ __global__ void __launch_bounds__(256) k_cl_check(ClBufs b) {
 // one lane, in order, from the first open chunk: every exit it reads is final
 template <int KIND, int MODE = kClCollect>
 __global__ void __launch_bounds__(64)
-k_cl_serial(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, ClAttempt a) {
+k_cl_serial(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, LongAttempt a) {
   extern __shared__ __align__(16) uint8_t lds[];
   if (b.ctl[kClRounds] >= b.m) return;  // uniform: everything is final
   const Tab<KIND> tab = stageTab<KIND, 64>(d, lds);
-  const LaneCtx c = clCtx<KIND>(d, lds);
-  const StartFilter flt = clFilter(d);
+  const LaneCtx c = longCtx<KIND>(d, lds);
+  const StartFilter flt = longFilter(d);
   if (threadIdx.x) return;
   for (uint64_t j = b.ctl[kClRounds]; j < b.m; ++j) {
     const uint64_t want = j ? b.exit[j - 1] : 0;
@@ -323,45 +250,6 @@ k_cl_serial(DevDfa d, const uint8_t *p, uint64_t n, ClBufs b, ClAttempt a) {
     b.ent[j] = want;
     clRewalk<MODE>(tab, c, flt, p, n, b, j, want, kClOpen, a);
   }
-}
-
-// fold 1: block-exclusive scan of the counts (1024 chunks per block), block totals behind
-__global__ void __launch_bounds__(1024) k_cl_scan1(ClBufs b) {
-  __shared__ uint64_t s[1024];
-  const uint64_t j = uint64_t(blockIdx.x) * 1024 + threadIdx.x;
-  const uint64_t v = j < b.m ? b.cnt[j] : 0;
-  s[threadIdx.x] = v;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024; o <<= 1) {
-    const uint64_t add = threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-    __syncthreads();
-    s[threadIdx.x] += add;
-    __syncthreads();
-  }
-  if (j < b.m) b.off[j] = s[threadIdx.x] - v;
-  if (threadIdx.x == 1023) b.blockOff[blockIdx.x] = s[1023];
-}
-
-// fold 2: one workgroup, exclusive scan of the block totals in place; *count = the sum
-__global__ void __launch_bounds__(1024) k_cl_scan2(ClBufs b, uint64_t nb, uint64_t *count) {
-  __shared__ uint64_t s[1024];
-  uint64_t carry = 0;
-  for (uint64_t t0 = 0; t0 < nb; t0 += 1024) {
-    const uint64_t i = t0 + threadIdx.x;
-    const uint64_t v = i < nb ? b.blockOff[i] : 0;
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024; o <<= 1) {
-      const uint64_t add = threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-      __syncthreads();
-      s[threadIdx.x] += add;
-      __syncthreads();
-    }
-    if (i < nb) b.blockOff[i] = carry + s[threadIdx.x] - v;
-    carry += s[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *count = carry;
 }
 
 // fold 3: a wave per chunk copies its records to their place in the caller's arrays (< cap)
@@ -391,36 +279,32 @@ __global__ void __launch_bounds__(64) k_cl_closed(const int32_t *result, uint64_
 // the chain of every chunk, final: walk, rounds, check + serial finish, and the scan of the counts
 template <int KIND, int MODE>
 hipError_t launchClChain(const DevDfa &d, const uint8_t *p, uint64_t n, const ClBufs &b,
-                         const ClAttempt a, uint64_t *count, const LaunchCfg &cfg,
+                         const LongAttempt a, uint64_t *count, const LaunchCfg &cfg,
                          hipStream_t stream) {
-  constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
-  constexpr int kThreads = kLds ? 1024 : 256;
-  const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
-  hipError_t e = setLds(k_cl_walk<KIND, kThreads, MODE>, ldsBytes);
-  if (e == hipSuccess) e = setLds(k_cl_rewalk<KIND, kThreads, MODE>, ldsBytes);
-  if (e == hipSuccess) e = setLds(k_cl_serial<KIND, MODE>, ldsBytes);
+  constexpr int kThreads = kStagedThreads<KIND>;
+  const LongPlan g = longPlan<KIND>(d, b.m, b.chunk, cfg);
+  hipError_t e = setLds(k_cl_walk<KIND, kThreads, MODE>, g.ldsBytes);
+  if (e == hipSuccess) e = setLds(k_cl_rewalk<KIND, kThreads, MODE>, g.ldsBytes);
+  if (e == hipSuccess) e = setLds(k_cl_serial<KIND, MODE>, g.ldsBytes);
   if (e != hipSuccess) return e;
-  const uint64_t perCu = kLds ? (ldsBytes <= 80 * 1024 ? 2 : 1) : 8;
-  uint64_t blocks = (b.m + kThreads - 1) / kThreads;
-  if (blocks > uint64_t(cfg.numCUs) * perCu) blocks = uint64_t(cfg.numCUs) * perCu;
-  if (blocks == 0) blocks = 1;
-  uint64_t small = (b.m + 255) / 256;
-  if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
-  // (speculative attempts: 16 bytes per chunk byte past their first, and 1 KiB)
-  const uint64_t budget = uint64_t(b.chunk) * 16 + 1024;
   hipLaunchKernelGGL(k_cl_init, dim3(1), dim3(64), 0, stream, b);
-  hipLaunchKernelGGL((k_cl_walk<KIND, kThreads, MODE>), dim3(uint32_t(blocks)), dim3(kThreads),
-                     ldsBytes, stream, d, p, n, b, budget, a);
+  hipLaunchKernelGGL((k_cl_walk<KIND, kThreads, MODE>), dim3(g.blocks), dim3(kThreads), g.ldsBytes,
+                     stream, d, p, n, b, g.budget, a);
   for (int round = 0; round < kClRounds; ++round) {
-    hipLaunchKernelGGL(k_cl_resolve, dim3(uint32_t(small)), dim3(256), 0, stream, b, round);
-    hipLaunchKernelGGL((k_cl_rewalk<KIND, kThreads, MODE>), dim3(uint32_t(blocks)), dim3(kThreads),
-                       ldsBytes, stream, d, p, n, b, round, budget, a);
+    hipLaunchKernelGGL(k_cl_resolve, dim3(g.small), dim3(256), 0, stream, b, round);
+    hipLaunchKernelGGL((k_cl_rewalk<KIND, kThreads, MODE>), dim3(g.blocks), dim3(kThreads),
+                       g.ldsBytes, stream, d, p, n, b, round, g.budget, a);
   }
-  hipLaunchKernelGGL(k_cl_check, dim3(uint32_t(small)), dim3(256), 0, stream, b);
-  hipLaunchKernelGGL((k_cl_serial<KIND, MODE>), dim3(1), dim3(64), ldsBytes, stream, d, p, n, b, a);
+  hipLaunchKernelGGL(k_cl_check, dim3(g.small), dim3(256), 0, stream, b);
+  hipLaunchKernelGGL((k_cl_serial<KIND, MODE>), dim3(1), dim3(64), g.ldsBytes, stream, d, p, n, b, a);
+  // fold: the exclusive scan of the per-chunk counts; the total is the call's count
   const uint64_t nb = (b.m + 1023) / 1024;
-  hipLaunchKernelGGL(k_cl_scan1, dim3(uint32_t(nb)), dim3(1024), 0, stream, b);
-  hipLaunchKernelGGL(k_cl_scan2, dim3(1), dim3(1024), 0, stream, b, nb, count);
+  uint64_t *const none = nullptr;
+  hipLaunchKernelGGL((k_long_scan1<false, uint32_t>), dim3(uint32_t(nb)), dim3(1024), 0, stream, b.m,
+                     static_cast<const uint32_t *>(b.cnt), b.off, none, b.blockOff, none,
+                     static_cast<const uint32_t *>(nullptr));
+  hipLaunchKernelGGL(k_long_scan2<false>, dim3(1), dim3(1024), 0, stream, b.blockOff, none, nb,
+                     static_cast<const uint32_t *>(nullptr), count);
   return hipGetLastError();
 }
 
@@ -428,7 +312,7 @@ template <int KIND>
 hipError_t launchCollectLongK(const DevDfa &d, const uint8_t *p, uint64_t n, const ClBufs &b,
                               uint64_t cap, uint64_t *count, int32_t *result, uint64_t *start,
                               uint64_t *end, const LaunchCfg &cfg, hipStream_t stream) {
-  const hipError_t e = launchClChain<KIND, kClCollect>(d, p, n, b, ClAttempt{}, count, cfg, stream);
+  const hipError_t e = launchClChain<KIND, kClCollect>(d, p, n, b, LongAttempt{}, count, cfg, stream);
   if (e != hipSuccess) return e;
   if (cap) {
     uint64_t sb = (b.m + 3) / 4;

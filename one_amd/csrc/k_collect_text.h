@@ -175,8 +175,8 @@ hipError_t launchCollectTextK(const DevDfa &d, const uint8_t *data, const GpBufs
   // LDS placements: it holds two chunk views and the prefix beside the chain, and at 1024 threads
   // (128 VGPRs) it spills 22-27 of them (92-112 bytes of private memory per lane), where k_ct_count
   // and k_gp_select spill none - so it runs 512 threads (158 VGPRs, no spill)
-  constexpr int kThreads = kTextThreads<KIND>;
-  constexpr int kWriteThreads = kTextLds<KIND> ? 512 : 256;
+  constexpr int kThreads = kStagedThreads<KIND>;
+  constexpr int kWriteThreads = kStagedLds<KIND> ? 512 : 256;
   const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
   hipError_t e = setLds(k_ct_count<KIND, kThreads>, ldsBytes);
   if (e == hipSuccess) e = setLds(k_ct_write<KIND, kWriteThreads>, ldsBytes);

@@ -174,6 +174,40 @@ __device__ __forceinline__ Tab<KIND> stageTab(const DevDfa &d, uint8_t *lds) {
   return tab;
 }
 
+// The launch geometry of a pass that stages the table per workgroup (stageTab): 1024 threads where
+// the table is in LDS, else 256; at most one wave of resident workgroups.
+template <int KIND>
+constexpr bool kStagedLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
+template <int KIND>
+constexpr int kStagedThreads = kStagedLds<KIND> ? 1024 : 256;
+
+// resident workgroups per CU for a workgroup of ldsBytes
+template <int KIND>
+__host__ inline uint64_t stagedPerCu(size_t ldsBytes) {
+  return kStagedLds<KIND> ? (ldsBytes <= 80 * 1024 ? 2 : 1) : 8;
+}
+
+// A cursor over a verb's scratch: take<T>(n) hands out the next n T, align(a) rounds the cursor up
+// to a power of two.  Over a null base nothing is handed out and `at` ends as the size, so a
+// verb's layout is written once, for its size function and its launcher.  The base is 16-byte
+// aligned: a bitmap is taken at a multiple of 16 (gpLoadBits loads uint4), a u64 array at one of 8.
+struct Carve {
+  uint8_t *base;
+  uint64_t at = 0;
+  template <class T> T *take(uint64_t n) {
+    T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
+    at += n * sizeof(T);
+    return p;
+  }
+  void align(uint64_t a) { at = (at + a - 1) & ~(a - 1); }
+  // ... and the cursor rounded up to 16 bytes behind it
+  template <class T> T *take16(uint64_t n) {
+    T *p = take<T>(n);
+    align(16);
+    return p;
+  }
+};
+
 struct LaneCtx {
   const uint8_t *eq;      // LDS: byte -> class
   const uint8_t *leader;  // LDS: class-space leader

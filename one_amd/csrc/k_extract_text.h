@@ -289,8 +289,8 @@ hipError_t launchExtractTextK(const DevDfa &d, const uint8_t *data, uint64_t len
   // threads and resident workgroups by k_text.h's rule (textBlocks): the sizing pass as k_ct_count,
   // the write pass - two chunk views, the prefix and the window beside the chain - at 512 threads
   // under the LDS placements so that it does not spill (profiles/extract_text_resources.md)
-  constexpr int kThreads = kTextThreads<KIND>;
-  constexpr int kWriteThreads = kTextLds<KIND> ? 512 : 256;
+  constexpr int kThreads = kStagedThreads<KIND>;
+  constexpr int kWriteThreads = kStagedLds<KIND> ? 512 : 256;
   const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
   hipError_t e = setLds(k_xt_size<KIND, kThreads>, ldsBytes);
   if (e == hipSuccess) e = setLds(k_xt_write<KIND, kWriteThreads>, ldsBytes);

@@ -106,7 +106,7 @@ hipError_t launchGrepK(const DevDfa &d, const uint8_t *data, const GpBufs &b, in
                        int invert, const GpOut &out, bool write, uint64_t *total,
                        uint64_t maxCount, uint64_t *nSelected, uint64_t *selBases,
                        uint64_t *dummy, const LaunchCfg &cfg, hipStream_t stream) {
-  constexpr int kThreads = kTextThreads<KIND>;
+  constexpr int kThreads = kStagedThreads<KIND>;
   const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
   hipError_t e = setLds(k_gp_select<KIND, kThreads, VERB>, ldsBytes);
   if (e == hipSuccess) e = setLds(k_gp_write<KIND, kThreads, VERB>, ldsBytes);

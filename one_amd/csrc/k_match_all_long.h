@@ -23,7 +23,7 @@
 //   k_ml_check / k_ml_serial  the first chunk still inconsistent, and one lane that goes on from
 //                it in text order, unbounded, skipping chunks whose entry already matches (the
 //                DFAs whose guesses never converge);
-//   fold         k_ml_scan1 / k_ml_scan2: the exclusive sum of the counts (the total is the call's
+//   fold         k_long.h's scan kernels: the exclusive sum of the counts (the total is the call's
 //                count) and the exclusive prefix max of the escapes, over all chunks;
 //   k_ml_emit    the chunks that open a record below `cap` walk once more from their resolved
 //                entry and write their records in place; a record whose run goes on past its
@@ -86,9 +86,8 @@ __device__ __forceinline__ MlChunk mlCount(const T &tab, const LaneCtx &c, const
 template <class T>
 __device__ __forceinline__ void mlStore(const T &tab, const LaneCtx &c, const uint8_t *p, uint64_t n,
                                         const MlBufs &b, uint64_t j, uint32_t q) {
-  const uint64_t lo = j * b.chunk;
-  const uint64_t hi = lo + b.chunk < n ? lo + b.chunk : n;
-  const MlChunk k = mlCount(tab, c, p, lo, hi, q, j == 0);
+  const LongSpan sp = longSpan(j, b.chunk, n);
+  const MlChunk k = mlCount(tab, c, p, sp.lo, sp.hi, q, j == 0);
   b.exit[j] = k.exit;
   b.cnt[j] = k.cnt;
   b.head[j] = k.head;
@@ -115,7 +114,7 @@ k_ml_walk(DevDfa d, const uint8_t *p, uint64_t n, MlBufs b) {
   extern __shared__ __align__(16) uint8_t lds[];
   if (!b.ctl[kMlGo]) return;  // uniform: the leader test failed
   const Tab<KIND> tab = stageTab<KIND, kThreads>(d, lds);
-  const LaneCtx c = clCtx<KIND>(d, lds);
+  const LaneCtx c = longCtx<KIND>(d, lds);
   const uint64_t step = uint64_t(gridDim.x) * kThreads;
   for (uint64_t j = uint64_t(blockIdx.x) * kThreads + threadIdx.x; j < b.m; j += step) {
     const uint64_t lo = j * b.chunk;
@@ -148,7 +147,7 @@ k_ml_rewalk(DevDfa d, const uint8_t *p, uint64_t n, MlBufs b, int round) {
   extern __shared__ __align__(16) uint8_t lds[];
   if (!b.ctl[kMlGo] || b.ctl[round] == 0) return;  // uniform: nothing queued this round
   const Tab<KIND> tab = stageTab<KIND, kThreads>(d, lds);
-  const LaneCtx c = clCtx<KIND>(d, lds);
+  const LaneCtx c = longCtx<KIND>(d, lds);
   const uint32_t queued = b.ctl[round];
   const uint64_t step = uint64_t(gridDim.x) * kThreads;
   for (uint64_t i = uint64_t(blockIdx.x) * kThreads + threadIdx.x; i < queued; i += step) {
@@ -171,7 +170,7 @@ __global__ void __launch_bounds__(64) k_ml_serial(DevDfa d, const uint8_t *p, ui
   extern __shared__ __align__(16) uint8_t lds[];
   if (!b.ctl[kMlGo] || b.ctl[kMlOpen] >= b.m) return;  // uniform: everything is final
   const Tab<KIND> tab = stageTab<KIND, 64>(d, lds);
-  const LaneCtx c = clCtx<KIND>(d, lds);
+  const LaneCtx c = longCtx<KIND>(d, lds);
   if (threadIdx.x) return;
   uint32_t walked = 0;
   for (uint64_t j = b.ctl[kMlOpen]; j < b.m; ++j) {
@@ -182,68 +181,6 @@ __global__ void __launch_bounds__(64) k_ml_serial(DevDfa d, const uint8_t *p, ui
     ++walked;
   }
   b.ctl[kMlSerial] = walked;
-}
-
-// fold 1: per 1024 chunks the exclusive sum of the counts and the exclusive max of the escapes
-// (in place), block totals behind
-__global__ void __launch_bounds__(1024) k_ml_scan1(MlBufs b) {
-  __shared__ uint64_t s[1024], x[1024];
-  if (!b.ctl[kMlGo]) return;
-  const uint64_t j = uint64_t(blockIdx.x) * 1024 + threadIdx.x;
-  const uint64_t v = j < b.m ? b.cnt[j] : 0;
-  s[threadIdx.x] = v;
-  x[threadIdx.x] = j < b.m ? b.esc[j] : 0;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024; o <<= 1) {
-    const uint64_t add = threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-    const uint64_t mx = threadIdx.x >= o ? x[threadIdx.x - o] : 0;
-    __syncthreads();
-    s[threadIdx.x] += add;
-    if (mx > x[threadIdx.x]) x[threadIdx.x] = mx;
-    __syncthreads();
-  }
-  if (j < b.m) {
-    b.off[j] = s[threadIdx.x] - v;
-    b.esc[j] = threadIdx.x ? x[threadIdx.x - 1] : 0;
-  }
-  if (threadIdx.x == 1023) {
-    b.blockOff[blockIdx.x] = s[1023];
-    b.blockEsc[blockIdx.x] = x[1023];
-  }
-}
-
-// fold 2: one workgroup, the same two exclusive scans over the block totals in place; *count
-__global__ void __launch_bounds__(1024) k_ml_scan2(MlBufs b, uint64_t nb, uint64_t *count) {
-  __shared__ uint64_t s[1024], x[1024];
-  if (!b.ctl[kMlGo]) {
-    if (threadIdx.x == 0) *count = 0;
-    return;
-  }
-  uint64_t carry = 0, carryMax = 0;
-  for (uint64_t t0 = 0; t0 < nb; t0 += 1024) {
-    const uint64_t i = t0 + threadIdx.x;
-    const uint64_t v = i < nb ? b.blockOff[i] : 0;
-    s[threadIdx.x] = v;
-    x[threadIdx.x] = i < nb ? b.blockEsc[i] : 0;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024; o <<= 1) {
-      const uint64_t add = threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-      const uint64_t mx = threadIdx.x >= o ? x[threadIdx.x - o] : 0;
-      __syncthreads();
-      s[threadIdx.x] += add;
-      if (mx > x[threadIdx.x]) x[threadIdx.x] = mx;
-      __syncthreads();
-    }
-    if (i < nb) {
-      const uint64_t before = threadIdx.x ? x[threadIdx.x - 1] : 0;
-      b.blockOff[i] = carry + s[threadIdx.x] - v;
-      b.blockEsc[i] = before > carryMax ? before : carryMax;
-    }
-    carry += s[1023];
-    if (x[1023] > carryMax) carryMax = x[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *count = carry;
 }
 
 // the records, in place.  Chunk j closes the run that was open on its entry (end[off - 1]) when
@@ -257,13 +194,13 @@ k_ml_emit(DevDfa d, const uint8_t *p, uint64_t n, MlBufs b, uint64_t cap, int32_
   extern __shared__ __align__(16) uint8_t lds[];
   if (!b.ctl[kMlGo]) return;
   const Tab<KIND> tab = stageTab<KIND, kThreads>(d, lds);
-  const LaneCtx c = clCtx<KIND>(d, lds);
+  const LaneCtx c = longCtx<KIND>(d, lds);
   const uint64_t step = uint64_t(gridDim.x) * kThreads;
   for (uint64_t j = uint64_t(blockIdx.x) * kThreads + threadIdx.x; j < b.m; j += step) {
     const uint64_t off = b.blockOff[j / 1024] + b.off[j];
     if (off > cap) continue;  // (record off - 1 is not kept either)
-    const uint64_t lo = j * b.chunk;
-    const uint64_t hi = lo + b.chunk < n ? lo + b.chunk : n;
+    const LongSpan sp = longSpan(j, b.chunk, n);
+    const uint64_t lo = sp.lo, hi = sp.hi;
     const bool last = j + 1 == b.m;
     const uint32_t q = b.ent[j];
     const int32_t rq = j ? c.resultOf(q) : 0;
@@ -309,35 +246,33 @@ hipError_t launchMatchAllLongK(const DevDfa &d, const uint8_t *p, uint64_t n, co
                                int lead, uint64_t cap, uint64_t *count, int32_t *result,
                                uint64_t *start, uint64_t *end, const LaunchCfg &cfg,
                                hipStream_t stream) {
-  constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
-  constexpr int kThreads = kLds ? 1024 : 256;
-  const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
-  hipError_t e = setLds(k_ml_walk<KIND, kThreads>, ldsBytes);
-  if (e == hipSuccess) e = setLds(k_ml_rewalk<KIND, kThreads>, ldsBytes);
-  if (e == hipSuccess) e = setLds(k_ml_serial<KIND>, ldsBytes);
-  if (e == hipSuccess) e = setLds(k_ml_emit<KIND, kThreads>, ldsBytes);
+  constexpr int kThreads = kStagedThreads<KIND>;
+  const LongPlan g = longPlan<KIND>(d, b.m, b.chunk, cfg);
+  hipError_t e = setLds(k_ml_walk<KIND, kThreads>, g.ldsBytes);
+  if (e == hipSuccess) e = setLds(k_ml_rewalk<KIND, kThreads>, g.ldsBytes);
+  if (e == hipSuccess) e = setLds(k_ml_serial<KIND>, g.ldsBytes);
+  if (e == hipSuccess) e = setLds(k_ml_emit<KIND, kThreads>, g.ldsBytes);
   if (e != hipSuccess) return e;
-  const uint64_t perCu = kLds ? (ldsBytes <= 80 * 1024 ? 2 : 1) : 8;
-  uint64_t blocks = (b.m + kThreads - 1) / kThreads;
-  if (blocks > uint64_t(cfg.numCUs) * perCu) blocks = uint64_t(cfg.numCUs) * perCu;
-  if (blocks == 0) blocks = 1;
-  uint64_t small = (b.m + 255) / 256;
-  if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
   hipLaunchKernelGGL(k_ml_init, dim3(1), dim3(64), 0, stream, d, p, n, b, lead);
-  hipLaunchKernelGGL((k_ml_walk<KIND, kThreads>), dim3(uint32_t(blocks)), dim3(kThreads), ldsBytes,
-                     stream, d, p, n, b);
+  hipLaunchKernelGGL((k_ml_walk<KIND, kThreads>), dim3(g.blocks), dim3(kThreads), g.ldsBytes, stream,
+                     d, p, n, b);
   for (int round = 0; round < kMlRounds; ++round) {
-    hipLaunchKernelGGL(k_ml_resolve, dim3(uint32_t(small)), dim3(256), 0, stream, b, round);
-    hipLaunchKernelGGL((k_ml_rewalk<KIND, kThreads>), dim3(uint32_t(blocks)), dim3(kThreads),
-                       ldsBytes, stream, d, p, n, b, round);
+    hipLaunchKernelGGL(k_ml_resolve, dim3(g.small), dim3(256), 0, stream, b, round);
+    hipLaunchKernelGGL((k_ml_rewalk<KIND, kThreads>), dim3(g.blocks), dim3(kThreads), g.ldsBytes,
+                       stream, d, p, n, b, round);
   }
-  hipLaunchKernelGGL(k_ml_check, dim3(uint32_t(small)), dim3(256), 0, stream, b);
-  hipLaunchKernelGGL((k_ml_serial<KIND>), dim3(1), dim3(64), ldsBytes, stream, d, p, n, b);
+  hipLaunchKernelGGL(k_ml_check, dim3(g.small), dim3(256), 0, stream, b);
+  hipLaunchKernelGGL((k_ml_serial<KIND>), dim3(1), dim3(64), g.ldsBytes, stream, d, p, n, b);
+  // fold: the exclusive sum of the counts and the exclusive max of the escapes, in place, shut
+  // (*count = 0) when the leader test failed
   const uint64_t nb = (b.m + 1023) / 1024;
-  hipLaunchKernelGGL(k_ml_scan1, dim3(uint32_t(nb)), dim3(1024), 0, stream, b);
-  hipLaunchKernelGGL(k_ml_scan2, dim3(1), dim3(1024), 0, stream, b, nb, count);
+  const uint32_t *go = b.ctl + kMlGo;
+  hipLaunchKernelGGL((k_long_scan1<true, uint32_t>), dim3(uint32_t(nb)), dim3(1024), 0, stream, b.m,
+                     static_cast<const uint32_t *>(b.cnt), b.off, b.esc, b.blockOff, b.blockEsc, go);
+  hipLaunchKernelGGL(k_long_scan2<true>, dim3(1), dim3(1024), 0, stream, b.blockOff, b.blockEsc, nb,
+                     go, count);
   if (cap)
-    hipLaunchKernelGGL((k_ml_emit<KIND, kThreads>), dim3(uint32_t(blocks)), dim3(kThreads), ldsBytes,
+    hipLaunchKernelGGL((k_ml_emit<KIND, kThreads>), dim3(g.blocks), dim3(kThreads), g.ldsBytes,
                        stream, d, p, n, b, cap, result, start, end);
   return hipGetLastError();
 }

@@ -4,13 +4,15 @@
 // replaceCore is collect's chain with another attempt: at position `in` one anchored attempt under
 // the call's style (and the leader test); on success the bytes [in, found + 1) become the
 // replacement and the chain goes on at found + 1, otherwise one byte is copied and it goes on at
-// in + 1.  The chain is k_collect_long.h's, instantiated kClReplace (lean slots: attempt position
-// u32 + end u64 = 12 bytes per text byte).  What is new here is the assembly, a pure function of
-// the final records, numbered k = 0, 1, ... by the scan of the chunk counts; only k < max count:
+// in + 1.  The chain is k_collect_long.h's, instantiated kClReplace (LongAttempt: style and leader;
+// lean slots: attempt position u32 + end u64 = 12 bytes per text byte).  What is new here is the
+// assembly, a pure function of the final records, numbered k = 0, 1, ... by the scan of the chunk
+// counts; only k < max count:
 //   k_rl_sum     a wave per chunk: the bytes its counted records remove (end - at), and the end
 //                of its last one;
-//   k_rl_scan1/2 exclusive scan of (sum, max) over the chunks: in front of chunk j, `rem` bytes
-//                were removed and the text is covered up to `cov`; *count and *out_len;
+//   scans        (k_long.h's k_long_scan1, k_rl_scan2) exclusive scan of (sum, max) over the
+//                chunks: in front of chunk j, `rem` bytes were removed and the text is covered up
+//                to `cov`; *count and *out_len;
 //   k_rl_copy    driven by TILES OF THE INPUT (kRlTile bytes, 16 per lane), not by the chunk that
 //                owns a record: a kept byte x lands at x - (removed before x) + repl_len *
 //                (records before x), replacement k at the landing place of its attempt position.
@@ -60,69 +62,18 @@ __global__ void __launch_bounds__(256) k_rl_sum(ClBufs b, RlBufs r, uint64_t max
   }
 }
 
-// block-exclusive (sum, max) of 1024 chunks, block totals behind
-__global__ void __launch_bounds__(1024) k_rl_scan1(ClBufs b, RlBufs r) {
-  __shared__ uint64_t s[1024], x[1024];
-  const uint64_t j = uint64_t(blockIdx.x) * 1024 + threadIdx.x;
-  const uint64_t v = j < b.m ? r.rem[j] : 0;
-  const uint64_t w = j < b.m ? r.cov[j] : 0;
-  s[threadIdx.x] = v;
-  x[threadIdx.x] = w;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024; o <<= 1) {
-    const uint64_t add = threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-    const uint64_t mx = threadIdx.x >= o ? x[threadIdx.x - o] : 0;
-    __syncthreads();
-    s[threadIdx.x] += add;
-    if (mx > x[threadIdx.x]) x[threadIdx.x] = mx;
-    __syncthreads();
-  }
-  if (j < b.m) {
-    r.rem[j] = s[threadIdx.x] - v;
-    r.cov[j] = threadIdx.x ? x[threadIdx.x - 1] : 0;
-  }
-  if (threadIdx.x == 1023) {
-    r.blockRem[blockIdx.x] = s[1023];
-    r.blockCov[blockIdx.x] = x[1023];
-  }
-}
-
-// one workgroup: exclusive (sum, max) of the block totals in place; *count = min(found, max),
-// *outLen = n - removed + replLen * *count
+// one workgroup: exclusive (sum, max) of the block totals in place (k_long.h); *count =
+// min(found, max), *outLen = n - removed + replLen * *count
 __global__ void __launch_bounds__(1024)
 k_rl_scan2(RlBufs r, uint64_t nb, uint64_t n, uint64_t replLen, uint64_t max, uint64_t *count,
            uint64_t *outLen) {
   __shared__ uint64_t s[1024], x[1024];
-  uint64_t carry = 0, carryMax = 0;
-  for (uint64_t t0 = 0; t0 < nb; t0 += 1024) {
-    const uint64_t i = t0 + threadIdx.x;
-    const uint64_t v = i < nb ? r.blockRem[i] : 0;
-    const uint64_t w = i < nb ? r.blockCov[i] : 0;
-    s[threadIdx.x] = v;
-    x[threadIdx.x] = w;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024; o <<= 1) {
-      const uint64_t add = threadIdx.x >= o ? s[threadIdx.x - o] : 0;
-      const uint64_t mx = threadIdx.x >= o ? x[threadIdx.x - o] : 0;
-      __syncthreads();
-      s[threadIdx.x] += add;
-      if (mx > x[threadIdx.x]) x[threadIdx.x] = mx;
-      __syncthreads();
-    }
-    if (i < nb) {
-      r.blockRem[i] = carry + s[threadIdx.x] - v;
-      const uint64_t before = threadIdx.x ? x[threadIdx.x - 1] : 0;
-      r.blockCov[i] = before > carryMax ? before : carryMax;
-    }
-    carry += s[1023];
-    if (x[1023] > carryMax) carryMax = x[1023];
-    __syncthreads();
-  }
+  const uint64_t removed = longScanTotals<true>(s, x, r.blockRem, r.blockCov, nb);
   if (threadIdx.x == 0) {
     const uint64_t found = *count;
     const uint64_t done = found < max ? found : max;
     *count = done;
-    *outLen = n - carry + replLen * done;
+    *outLen = n - removed + replLen * done;
   }
 }
 
@@ -339,7 +290,9 @@ inline hipError_t launchRlAssemble(const uint8_t *p, uint64_t n, const ClBufs &b
     uint64_t sb = (b.m + 3) / 4;
     if (sb > uint64_t(cfg.numCUs) * 16) sb = uint64_t(cfg.numCUs) * 16;
     hipLaunchKernelGGL(k_rl_sum, dim3(uint32_t(sb)), dim3(256), 0, stream, b, r, max);
-    hipLaunchKernelGGL(k_rl_scan1, dim3(uint32_t(nb)), dim3(1024), 0, stream, b, r);
+    hipLaunchKernelGGL((k_long_scan1<true, uint64_t>), dim3(uint32_t(nb)), dim3(1024), 0, stream, b.m,
+                       static_cast<const uint64_t *>(r.rem), r.rem, r.cov, r.blockRem, r.blockCov,
+                       static_cast<const uint32_t *>(nullptr));
     hipLaunchKernelGGL(k_rl_scan2, dim3(1), dim3(1024), 0, stream, r, nb, n, replLen, max, count,
                        outLen);
   }

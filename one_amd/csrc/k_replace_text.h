@@ -246,8 +246,8 @@ hipError_t launchReplaceTextK(const DevDfa &d, const uint8_t *data, const GpBufs
   // threads and resident workgroups by k_text.h's rule (textBlocks): the count pass as k_ct_count,
   // the write pass - two chunk views, the prefix and the stretch beside replaceCore - at 512
   // threads under the LDS placements so that it does not spill (DESIGN 4.3h has the report)
-  constexpr int kThreads = kTextThreads<KIND>;
-  constexpr int kWriteThreads = kTextLds<KIND> ? 512 : 256;
+  constexpr int kThreads = kStagedThreads<KIND>;
+  constexpr int kWriteThreads = kStagedLds<KIND> ? 512 : 256;
   const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
   hipError_t e = setLds(k_rt_count<KIND, kThreads>, ldsBytes);
   if (e == hipSuccess) e = setLds(k_rt_write<KIND, kWriteThreads>, ldsBytes);

@@ -2,11 +2,12 @@
 // (included by kernels.hip inside its namespace, after k_replace_long.h).
 //
 // searchCore returns the Outcome of the LOWEST position whose anchored attempt succeeds - the
-// attempt being its inner loop under the call's style, with the leader test (lookingAt) in front
-// when asked for.  An attempt's Outcome depends on its position alone, so there is nothing to
-// guess and nothing to walk again (k_collect_long.h's entries and rounds): the text is cut into
-// chunks of C bytes, chunk j owns the attempt positions [j * C, (j + 1) * C), tries them in
-// increasing order and stops at its first success.  All queued on the caller's stream:
+// attempt (k_long.h: longChain) being its inner loop under the call's style, with the leader test
+// (lookingAt) in front when asked for.  An attempt's Outcome depends on its position alone, so
+// there is nothing to guess and nothing to walk again (k_collect_long.h's entries and rounds):
+// the text is cut into chunks of C bytes, chunk j owns the attempt positions [j * C, (j + 1) *
+// C), tries them in increasing order and stops at its first success.  All queued on the caller's
+// stream:
 //   k_sl_init    best = stop = first open chunk = "none", every chunk "untouched";
 //   k_sl_walk    persistent waves; wave w of W takes the tickets w, w + W, w + 2 W, ... - a ticket
 //                is 64 consecutive chunks, a chunk per lane - so at any time the chip works on
@@ -21,13 +22,14 @@
 //                failed attempt that read to the end of the text alive ends every later position
 //                (what k_collect_long.h's chain calls exit n).
 //                Attempts are bounded: a chunk walks at most `budget` bytes past the first bytes
-//                of its attempts (16 x C + 1 KiB, k_cl_walk's) - "x", then y without end, on
-//                every lane at once would otherwise pin the chip - and a chunk that runs out
-//                leaves the position it had reached;
+//                of its attempts (16 x C + 1 KiB, k_long.h's longPlan) - "x", then y without
+//                end, on every lane at once would otherwise pin the chip - and a chunk that runs
+//                out leaves the position it had reached;
 //   k_sl_check / k_sl_serial   the first chunk with an undecided position below best and stop,
 //                and ONE lane that finishes from it in order, unbounded: every chunk below it is
 //                decided, a decided chunk with a match ends the search, so does a success of its
-//                own (k_cl_check / k_cl_serial's pattern).  The bound costs time, never the Outcome;
+//                own (k_collect_long.h's check and serial finish, over k_long.h's longChain).
+//                The bound costs time, never the Outcome;
 //   k_sl_finish  result, start and end from best and the winner's slot, or 0 / 0 / 0.
 // Per chunk: one state word (u32: 0 = untouched, else 1 + the first undecided position relative to
 // the chunk, C = all decided; bit 31 = that position is a match) and one record slot (i32 + 2 x
@@ -56,7 +58,7 @@ inline uint64_t searchLongChunk(uint64_t n, uint32_t chunkBytes, const LaunchCfg
 }
 
 struct SlBufs {
-  uint64_t *ctl;     // [0] best, [1] stop, [2] first open chunk, [3] an attempt ran (SlAttempt::mark)
+  uint64_t *ctl;     // [0] best, [1] stop, [2] first open chunk, [3] an attempt ran (mark)
   uint32_t *state;   // [m]
   int32_t *res;      // [m] the chunk's match: result,
   uint64_t *rst, *ren;  // start, end
@@ -64,95 +66,13 @@ struct SlBufs {
   uint32_t chunk;
 };
 
-struct SlAttempt {
-  int style = kStyLast;
-  int lead = 0;
-  // the leader test in front of a DFA whose initial state accepts: searchCore's result is that
-  // state's when NO position passes the test (Matcher.h:571,577-578), so the passes are noted
-  int mark = 0;
-};
-
-struct SlHit {
-  int how;        // 0 = every position failed, 1 = a match, 2 = suffix-closed stop, 3 = out of budget
-  uint64_t at;    // the attempt position (how != 0)
-  uint32_t acc;   // the accepting state the result is read from
-  uint64_t ms, me;
-};
-
 __device__ __forceinline__ uint64_t slLoad(const uint64_t *w) {
   return __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The attempts at the positions [q, hi) of p[0, n) in order, up to the first that does not fail.
-// An attempt is searchCore's inner loop: Instant stops at the first accept, First and Tangent at
-// the first non-accept behind one (First also where the result changes), Last at a pure dead end,
-// Full likewise and only counts an accept in its last state; start is the last "left the initial
-// state" (Matcher.h:588-593).  `left` = the bytes the attempts may still walk past their first.
-template <class T>
-__device__ __forceinline__ SlHit slChain(const T &tab, const LaneCtx &c, const StartFilter &flt,
-                                         const uint8_t *p, uint64_t n, uint64_t q, uint64_t hi,
-                                         uint64_t &left, const SlAttempt a, uint64_t *ran) {
-  SlHit h{0, hi, 0, 0, 0};
-  walkBytesPeek(p, q, hi, flt, [] {}, [&](uint32_t byte, uint64_t i, uint32_t nextByte) -> bool {
-    if (a.lead && c.eq[byte] != c.leader[0]) return true;  // lookingAt's first byte
-    if (a.mark) {
-      if (!lookingAt(c, p, i, n)) return true;
-      *ran = 1;
-    }
-    uint32_t st = tab.next(c.init, byte);
-    bool any = false;
-    uint64_t ms = i, me = i;
-    uint32_t aS = 0;
-    int32_t prev = 0;  // (styFirst) the result of the accepts so far
-    if (st >= c.firstAccept) {
-      aS = st; me = i + 1; any = true;
-      if (a.style == kStyFirst) prev = c.res[st];
-    }
-    else if (st < c.nPureDead) return true;
-    else if (nextByte != kNoPeek && tab.next(st, nextByte) < c.nPureDead) return true;
-    if (a.lead && !a.mark && !lookingAt(c, p, i, n)) return true;
-    const uint64_t lim = n - i - 1 > left ? i + 1 + left : n;
-    uint64_t at = i + 1;
-    auto stepOne = [&](uint32_t b2, uint64_t q2) -> bool {
-      const uint32_t was = st;
-      st = tab.next(st, b2);
-      at = q2 + 1;
-      if (was == c.init && st != was) ms = q2;
-      if (st >= c.firstAccept) {
-        if (a.style == kStyFirst) {
-          const int32_t r = c.res[st];
-          if (prev && r != prev) return false;
-          prev = r;
-        }
-        aS = st; me = q2 + 1; any = true;
-        return a.style != kStyInstant;
-      }
-      if (a.style == kStyFull) any = false;
-      else if (any && (a.style == kStyFirst || a.style == kStyTangent)) return false;
-      return st >= c.nPureDead;
-    };
-    uint64_t q2 = i + 1;
-    bool alive = !(any && a.style == kStyInstant);
-    for (uint32_t k = 0; k < 6 && q2 < lim && alive; ++k, ++q2) alive = stepOne(uint32_t(p[q2]), q2);
-    if (alive)
-      walkBytes(p, q2, lim, [&](uint32_t b2, uint64_t q3) -> bool { return alive = stepOne(b2, q3); });
-    left -= at - i - 1;
-    h.at = i;
-    if (alive && lim < n) { h.how = 3; return false; }
-    if (!any) {
-      if (c.suffixClosed && alive && !a.lead) { h.how = 2; return false; }  // L = SIGMA* L
-      return true;
-    }
-    h.how = 1; h.acc = aS; h.ms = ms; h.me = me;
-    return false;
-  });
-  if (h.how == 0) h.at = hi;
-  return h;
-}
-
-// with SlAttempt::mark every position that passes the leader test must be seen: no start filter
-__device__ __forceinline__ StartFilter slFilter(const DevDfa &d, const SlAttempt a) {
-  return a.mark ? StartFilter{0, 0, 0, 0, false} : clFilter(d);
+// with mark every position that passes the leader test must be seen: no start filter
+__device__ __forceinline__ StartFilter slFilter(const DevDfa &d, int mark) {
+  return mark ? StartFilter{0, 0, 0, 0, false} : longFilter(d);
 }
 
 __global__ void __launch_bounds__(256) k_sl_init(SlBufs b) {
@@ -165,11 +85,12 @@ __global__ void __launch_bounds__(256) k_sl_init(SlBufs b) {
 
 template <int KIND, int kThreads>
 __global__ void __launch_bounds__(kThreads)
-k_sl_walk(DevDfa d, const uint8_t *p, uint64_t n, SlBufs b, uint64_t budget, SlAttempt a) {
+k_sl_walk(DevDfa d, const uint8_t *p, uint64_t n, SlBufs b, uint64_t budget, LongAttempt a,
+          int mark) {
   extern __shared__ __align__(16) uint8_t lds[];
   const Tab<KIND> tab = stageTab<KIND, kThreads>(d, lds);
-  const LaneCtx c = clCtx<KIND>(d, lds);
-  const StartFilter flt = slFilter(d, a);
+  const LaneCtx c = longCtx<KIND>(d, lds);
+  const StartFilter flt = slFilter(d, mark);
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t waves = uint64_t(gridDim.x) * (kThreads / 64);
   uint64_t best = slLoad(b.ctl), stop = slLoad(b.ctl + 1);
@@ -179,15 +100,16 @@ k_sl_walk(DevDfa d, const uint8_t *p, uint64_t n, SlBufs b, uint64_t budget, SlA
     if (first > best || first >= stop) break;  // nothing from this ticket on can be the Outcome
     const uint64_t j = t * 64 + lane;
     if (j >= b.m) break;
-    const uint64_t lo = j * b.chunk;
-    const uint64_t hi = lo + b.chunk < n ? lo + b.chunk : n;
+    const LongSpan sp = longSpan(j, b.chunk, n);
+    const uint64_t lo = sp.lo, hi = sp.hi;
     uint64_t reach = lo, left = budget;
     bool hit = false;
     while (reach < hi && reach <= best && reach < stop) {
       // (asked for here, looked at behind the run)
       const uint64_t nowBest = slLoad(b.ctl), nowStop = slLoad(b.ctl + 1);
       const uint64_t sub = hi - reach > kSlPoll ? reach + kSlPoll : hi;
-      const SlHit h = slChain(tab, c, flt, p, n, reach, sub, left, a, b.ctl + 3);
+      const LongHit h = longChain<false, true>(tab, c, flt, p, n, reach, sub, left, a, mark,
+                                                 b.ctl + 3);
       best = nowBest;
       stop = nowStop;
       reach = h.at;
@@ -226,8 +148,7 @@ __global__ void __launch_bounds__(256) k_sl_check(SlBufs b, uint64_t n) {
   for (uint64_t j = uint64_t(blockIdx.x) * 256 + threadIdx.x; j < jEnd; j += step) {
     bool hit;
     const uint64_t reach = slReach(b, j, &hit);
-    const uint64_t hi = (j + 1) * b.chunk < n ? (j + 1) * b.chunk : n;
-    if (!hit && reach < hi && reach < lim)
+    if (!hit && reach < longSpan(j, b.chunk, n).hi && reach < lim)
       atomicMin(reinterpret_cast<unsigned long long *>(b.ctl + 2), static_cast<unsigned long long>(j));
   }
 }
@@ -236,12 +157,12 @@ __global__ void __launch_bounds__(256) k_sl_check(SlBufs b, uint64_t n) {
 // decided and has no match (the lane's wave steps over the decided chunks, 64 at a look)
 template <int KIND>
 __global__ void __launch_bounds__(64)
-k_sl_serial(DevDfa d, const uint8_t *p, uint64_t n, SlBufs b, SlAttempt a) {
+k_sl_serial(DevDfa d, const uint8_t *p, uint64_t n, SlBufs b, LongAttempt a, int mark) {
   extern __shared__ __align__(16) uint8_t lds[];
   if (b.ctl[2] >= b.m) return;  // uniform: everything below best and stop is decided
   const Tab<KIND> tab = stageTab<KIND, 64>(d, lds);
-  const LaneCtx c = clCtx<KIND>(d, lds);
-  const StartFilter flt = slFilter(d, a);
+  const LaneCtx c = longCtx<KIND>(d, lds);
+  const StartFilter flt = slFilter(d, mark);
   const uint64_t lim = b.ctl[0] < b.ctl[1] ? b.ctl[0] : b.ctl[1];
   uint64_t j = b.ctl[2];
   while (j < b.m && j * b.chunk < lim) {
@@ -251,7 +172,7 @@ k_sl_serial(DevDfa d, const uint8_t *p, uint64_t n, SlBufs b, SlAttempt a) {
     if (mine < b.m) {
       bool hit;
       const uint64_t reach = slReach(b, mine, &hit);
-      open = hit || reach < ((mine + 1) * b.chunk < n ? (mine + 1) * b.chunk : n);
+      open = hit || reach < longSpan(mine, b.chunk, n).hi;
     }
     const unsigned long long mask = __ballot(open);
     if (!mask) { j += 64; continue; }
@@ -262,9 +183,10 @@ k_sl_serial(DevDfa d, const uint8_t *p, uint64_t n, SlBufs b, SlAttempt a) {
       const uint64_t reach = slReach(b, j, &hit);
       // (a match here is best itself: no chunk below has one)
       if (!hit && reach < lim) {
-        const uint64_t hi = (j + 1) * b.chunk < n ? (j + 1) * b.chunk : n;
+        const uint64_t hi = longSpan(j, b.chunk, n).hi;
         uint64_t left = kClOpen;
-        const SlHit h = slChain(tab, c, flt, p, n, reach, hi, left, a, b.ctl + 3);
+        const LongHit h = longChain<false, true>(tab, c, flt, p, n, reach, hi, left, a, mark,
+                                                 b.ctl + 3);
         if (h.how == 1) {
           b.res[j] = c.res[h.acc];
           b.rst[j] = h.ms;
@@ -280,7 +202,7 @@ k_sl_serial(DevDfa d, const uint8_t *p, uint64_t n, SlBufs b, SlAttempt a) {
 }
 
 // the Outcome: the slot of best's chunk, or no match - 0 / 0 / 0, the result being the initial
-// state's when no attempt ran at all (SlAttempt::mark)
+// state's when no attempt ran at all (mark)
 __global__ void __launch_bounds__(64)
 k_sl_finish(SlBufs b, const int32_t *resTab, uint32_t init, int mark, int32_t *result,
             uint64_t *start, uint64_t *end) {
@@ -303,28 +225,20 @@ k_sl_finish(SlBufs b, const int32_t *resTab, uint32_t init, int mark, int32_t *r
 
 template <int KIND>
 hipError_t launchSearchLongK(const DevDfa &d, const uint8_t *p, uint64_t n, const SlBufs &b,
-                             const SlAttempt a, int32_t *result, uint64_t *start, uint64_t *end,
-                             const LaunchCfg &cfg, hipStream_t stream) {
-  constexpr bool kLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
-  constexpr int kThreads = kLds ? 1024 : 256;
-  const size_t ldsBytes = 512 + ldsTableBytes<KIND>(d);
-  hipError_t e = setLds(k_sl_walk<KIND, kThreads>, ldsBytes);
-  if (e == hipSuccess) e = setLds(k_sl_serial<KIND>, ldsBytes);
+                             const LongAttempt a, int mark, int32_t *result, uint64_t *start,
+                             uint64_t *end, const LaunchCfg &cfg, hipStream_t stream) {
+  constexpr int kThreads = kStagedThreads<KIND>;
+  const LongPlan g = longPlan<KIND>(d, b.m, b.chunk, cfg);
+  hipError_t e = setLds(k_sl_walk<KIND, kThreads>, g.ldsBytes);
+  if (e == hipSuccess) e = setLds(k_sl_serial<KIND>, g.ldsBytes);
   if (e != hipSuccess) return e;
-  const uint64_t perCu = kLds ? (ldsBytes <= 80 * 1024 ? 2 : 1) : 8;
-  uint64_t blocks = (b.m + kThreads - 1) / kThreads;
-  if (blocks > uint64_t(cfg.numCUs) * perCu) blocks = uint64_t(cfg.numCUs) * perCu;
-  if (blocks == 0) blocks = 1;
-  uint64_t small = (b.m + 255) / 256;
-  if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
-  // (bounded attempts: 16 bytes per chunk byte past their first, and 1 KiB - k_cl_walk's)
-  const uint64_t budget = uint64_t(b.chunk) * 16 + 1024;
-  hipLaunchKernelGGL(k_sl_init, dim3(uint32_t(small)), dim3(256), 0, stream, b);
-  hipLaunchKernelGGL((k_sl_walk<KIND, kThreads>), dim3(uint32_t(blocks)), dim3(kThreads), ldsBytes,
-                     stream, d, p, n, b, budget, a);
-  hipLaunchKernelGGL(k_sl_check, dim3(uint32_t(small)), dim3(256), 0, stream, b, n);
-  hipLaunchKernelGGL((k_sl_serial<KIND>), dim3(1), dim3(64), ldsBytes, stream, d, p, n, b, a);
-  hipLaunchKernelGGL(k_sl_finish, dim3(1), dim3(64), 0, stream, b, d.result, d.init, a.mark,
+  hipLaunchKernelGGL(k_sl_init, dim3(g.small), dim3(256), 0, stream, b);
+  hipLaunchKernelGGL((k_sl_walk<KIND, kThreads>), dim3(g.blocks), dim3(kThreads), g.ldsBytes, stream,
+                     d, p, n, b, g.budget, a, mark);
+  hipLaunchKernelGGL(k_sl_check, dim3(g.small), dim3(256), 0, stream, b, n);
+  hipLaunchKernelGGL((k_sl_serial<KIND>), dim3(1), dim3(64), g.ldsBytes, stream, d, p, n, b, a,
+                     mark);
+  hipLaunchKernelGGL(k_sl_finish, dim3(1), dim3(64), 0, stream, b, d.result, d.init, mark,
                      result, start, end);
   return hipGetLastError();
 }

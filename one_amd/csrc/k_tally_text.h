@@ -42,11 +42,11 @@ struct TallyOut {
   uint32_t ldsBins;            // L: the bins kept in LDS
 };
 
-// the resident workgroups k_text.h's rule (textPerCu) gives k_ct_count for this DFA, and the LDS a
-// workgroup may take without lowering them
+// the resident workgroups k_common.h's rule (stagedPerCu) gives k_ct_count for this DFA, and the
+// LDS a workgroup may take without lowering them
 template <int KIND>
 __host__ inline uint64_t tallyPerCu(const DevDfa &d) {
-  return textPerCu<KIND>(512 + ldsTableBytes<KIND>(d));
+  return stagedPerCu<KIND>(512 + ldsTableBytes<KIND>(d));
 }
 
 // where the counters begin, and what follows them: 16 bytes (the workgroup's item count)
@@ -196,7 +196,7 @@ hipError_t launchTallyK(const DevDfa &d, const uint8_t *data, const GpBufs &b, i
                         int plain, const TallyOut &o, const LaunchCfg &cfg, hipStream_t stream) {
   // threads and resident workgroups by k_text.h's rule (textBlocks) for k_ct_count's LDS; the
   // counters fit in what that rule leaves of the LDS (tallyLdsBinsK), so the rule holds here as well
-  constexpr int kThreads = kTextThreads<KIND>;
+  constexpr int kThreads = kStagedThreads<KIND>;
   const size_t ldsBytes = tallyLdsOff<KIND>(d) + ((size_t(o.ldsBins) * 4 + 15) & ~size_t(15)) + 16;
   const hipError_t e = setLds(k_tally_text<KIND, kThreads, MODE>, ldsBytes);
   if (e != hipSuccess) return e;

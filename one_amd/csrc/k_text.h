@@ -1,7 +1,7 @@
 // k_text.h - what the raw-text verbs share (k_grep.h, k_collect_text.h, k_tally_text.h,
 // k_replace_text.h): the views of the split's delimiter bitmap, the line index behind it (k_gp_last,
 // k_gp_open), the line walk (textLines), the hit-line lookup (TextHits), the lane context, and on
-// the host the launch geometry (textBlocks) and the scratch cursor (Carve)
+// the host the launch geometry (textBlocks; the scratch cursor, Carve, is k_common.h's)
 // (included by kernels.hip inside namespace redgpu { namespace { ... } }, in front of k_grep.h;
 // DESIGN 4.3f).
 //
@@ -293,39 +293,13 @@ struct TextHits {
   }
 };
 
-// The launch geometry of a pass that stages the table per workgroup and gives a wave to a chunk:
-// 1024 threads where the table is in LDS, else 256; at most one wave of resident workgroups.
-template <int KIND>
-constexpr bool kTextLds = Tab<KIND>::kInLds || KIND == REDGPU_TAB_HOT_ROWS;
-template <int KIND>
-constexpr int kTextThreads = kTextLds<KIND> ? 1024 : 256;
-
-// resident workgroups per CU for a workgroup of ldsBytes
-template <int KIND>
-__host__ inline uint64_t textPerCu(size_t ldsBytes) {
-  return kTextLds<KIND> ? (ldsBytes <= 80 * 1024 ? 2 : 1) : 8;
-}
-
+// The launch geometry of a pass that stages the table per workgroup and gives a wave to a chunk
+// (k_common.h: kStagedThreads, stagedPerCu): at most one wave of resident workgroups.
 template <int KIND>
 __host__ inline uint32_t textBlocks(uint64_t nChunks, size_t ldsBytes, int threads,
                                     const LaunchCfg &cfg) {
   const uint64_t waves = uint64_t(threads) / 64;
-  const uint64_t most = uint64_t(cfg.numCUs) * textPerCu<KIND>(ldsBytes);
+  const uint64_t most = uint64_t(cfg.numCUs) * stagedPerCu<KIND>(ldsBytes);
   const uint64_t blocks = (nChunks + waves - 1) / waves;
   return uint32_t(blocks > most ? most : blocks);
 }
-
-// A cursor over a verb's scratch: take<T>(n) hands out the next n T, align(a) rounds the cursor up
-// to a power of two.  Over a null base nothing is handed out and `at` ends as the size, so a
-// verb's layout is written once, for its size function and its launcher.  The base is 16-byte
-// aligned: a bitmap is taken at a multiple of 16 (gpLoadBits loads uint4), a u64 array at one of 8.
-struct Carve {
-  uint8_t *base;
-  uint64_t at = 0;
-  template <class T> T *take(uint64_t n) {
-    T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
-    at += n * sizeof(T);
-    return p;
-  }
-  void align(uint64_t a) { at = (at + a - 1) & ~(a - 1); }
-};

@@ -10,7 +10,8 @@
 //
 // Map of the kernel families, one header each, all included below inside the namespace
 // (DESIGN.md section 4 has the measurements):
-//   k_common.h        table accessors, table staging, lane context, the byte readers
+//   k_common.h        table accessors, table staging (and the geometry of a pass that stages), the
+//                     scratch cursor, lane context, the byte readers
 //   k_lanes.h         the lane functions: direct restatements of the reference's cores
 //   k_generic.h       k_generic<KIND, THREADS, VERB>: any verb / style / table, one line per lane
 //   k_early.h         k_early: match / check over early-death DFAs (probe, park, drain)
@@ -26,6 +27,8 @@
 //   k_ragged_long.h   k_ragged_outliers (the long lines of a batch: listed, walked first, huge ones as
 //                     pieces), k_ragged_pieces_fold (the pieces' records -> their lines' Outcomes)
 //   k_lists.h         k_collect, k_matchall, k_matchall_blocks (record lists per line)
+//   k_long.h          what the long-text verbs share: the anchored attempt (longChain), the 1024-wide
+//                     scan kernels (sum and prefix max), a chunk's span, the launch plan
 //   k_replace_long.h  k_rl_*: replaceCore over ONE long text: k_collect_long.h's chain under any
 //                     style, then the assembly (sums, scans, a tile-driven copy/insert)
 //   k_collect_long.h  k_cl_*: Red::collect over ONE long text, chunk-parallel (guessed entries,
@@ -39,7 +42,7 @@
 //   k_misc.h          k_advance, k_replace (+ scan), k_visits, k_walked
 //   k_split.h         line splitting on the device
 //   k_text.h          what the raw-text verbs share: the bitmap views, the line index (k_gp_last,
-//                     k_gp_open), the line walk, the hit-line lookup, launch geometry, scratch cursor
+//                     k_gp_open), the line walk, the hit-line lookup, launch geometry
 //   k_grep.h          k_gp_*: grep over a raw text - the split's delimiter bitmap drives the lines,
 //                     a wave per 16 KiB chunk selects, a scan orders, a second pass writes records
 //   k_collect_text.h  k_ct_*: grep -o over a raw text - k_grep.h's line driver, Red::collect per line,
@@ -111,6 +114,7 @@ namespace {
 #include "k_stream_multi.h"
 #include "k_ragged.h"
 #include "k_lists.h"
+#include "k_long.h"
 #include "k_collect_long.h"
 #include "k_replace_long.h"
 #include "k_search_long.h"
@@ -520,6 +524,71 @@ hipError_t launchCollect(const DevDfa &d, const Batch &b, uint64_t cap, uint64_t
 #undef CO_CALL
 }
 
+// The scratch of the long-text verbs, for b.m chunks (collect, replace: of b.slots record slots
+// each): every array rounded up to 16 bytes, 64 bytes of control words; returns the size, and over
+// a null base hands out nothing else.
+static uint64_t carveCollectLong(void *scratch, ClBufs &b) {
+  Carve c{static_cast<uint8_t *>(scratch)};
+  const uint64_t nb = (b.m + 1023) / 1024, recs = b.m * b.slots;
+  b.ent = c.take16<uint64_t>(b.m);
+  b.exit = c.take16<uint64_t>(b.m);
+  b.off = c.take16<uint64_t>(b.m);
+  b.blockOff = c.take16<uint64_t>(nb);
+  b.ren = c.take16<uint64_t>(recs);
+  b.rst = c.take16<uint64_t>(recs);
+  b.res = c.take16<int32_t>(recs);
+  b.rat = c.take16<uint32_t>(recs);
+  b.cnt = c.take16<uint32_t>(b.m);
+  b.work = c.take16<uint32_t>(b.m);
+  b.ctl = c.take16<uint32_t>(16);
+  return c.at;
+}
+
+static uint64_t carveReplaceLong(void *scratch, ClBufs &b, RlBufs &r) {
+  Carve c{static_cast<uint8_t *>(scratch)};
+  const uint64_t nb = (b.m + 1023) / 1024, recs = b.m * b.slots;
+  b.ent = c.take16<uint64_t>(b.m);
+  b.exit = c.take16<uint64_t>(b.m);
+  b.off = c.take16<uint64_t>(b.m);
+  r.rem = c.take16<uint64_t>(b.m);
+  r.cov = c.take16<uint64_t>(b.m);
+  b.blockOff = c.take16<uint64_t>(nb);
+  r.blockRem = c.take16<uint64_t>(nb);
+  r.blockCov = c.take16<uint64_t>(nb);
+  b.ren = c.take16<uint64_t>(recs);
+  b.rat = c.take16<uint32_t>(recs);
+  b.cnt = c.take16<uint32_t>(b.m);
+  b.work = c.take16<uint32_t>(b.m);
+  b.ctl = c.take16<uint32_t>(16);
+  return c.at;
+}
+
+static uint64_t carveSearchLong(void *scratch, SlBufs &b) {
+  Carve c{static_cast<uint8_t *>(scratch)};
+  b.ctl = c.take16<uint64_t>(8);
+  b.rst = c.take16<uint64_t>(b.m);
+  b.ren = c.take16<uint64_t>(b.m);
+  b.res = c.take16<int32_t>(b.m);
+  b.state = c.take16<uint32_t>(b.m);
+  return c.at;
+}
+
+static uint64_t carveMatchAllLong(void *scratch, MlBufs &b) {
+  Carve c{static_cast<uint8_t *>(scratch)};
+  const uint64_t nb = (b.m + 1023) / 1024;
+  b.esc = c.take16<uint64_t>(b.m);
+  b.off = c.take16<uint64_t>(b.m);
+  b.blockOff = c.take16<uint64_t>(nb);
+  b.blockEsc = c.take16<uint64_t>(nb);
+  b.ent = c.take16<uint32_t>(b.m);
+  b.exit = c.take16<uint32_t>(b.m);
+  b.cnt = c.take16<uint32_t>(b.m);
+  b.head = c.take16<uint32_t>(b.m);
+  b.work = c.take16<uint32_t>(b.m);
+  b.ctl = c.take16<uint32_t>(16);
+  return c.at;
+}
+
 // Red::collect over one text (k_collect_long.h): the chunked chain, the suffix-closed route or
 // the one-lane k_collect - the same records either way.
 hipError_t launchCollectLong(const DevDfa &d, const uint8_t *data, uint64_t n, uint32_t chunkBytes,
@@ -551,26 +620,10 @@ hipError_t launchCollectLong(const DevDfa &d, const uint8_t *data, uint64_t n, u
   b.m = (n + c - 1) / c;
   b.chunk = uint32_t(c);
   b.slots = c < n ? c : n;
-  const uint64_t nb = (b.m + 1023) / 1024;
-  auto up16 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
-  const uint64_t recs = b.m * b.slots;
-  const size_t bytes = up16(b.m * 8) * 3 + up16(nb * 8) + up16(recs * 8) * 2 + up16(recs * 4) * 2 +
-                       up16(b.m * 4) * 2 + 64;
   void *scratch = nullptr;
-  hipError_t e = raggedScratch(stream, bytes, &scratch);
+  hipError_t e = raggedScratch(stream, carveCollectLong(nullptr, b), &scratch);
   if (e != hipSuccess) return e;
-  uint8_t *q = static_cast<uint8_t *>(scratch);
-  b.ent = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  b.exit = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  b.off = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  b.blockOff = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
-  b.ren = reinterpret_cast<uint64_t *>(q); q += up16(recs * 8);
-  b.rst = reinterpret_cast<uint64_t *>(q); q += up16(recs * 8);
-  b.res = reinterpret_cast<int32_t *>(q); q += up16(recs * 4);
-  b.rat = reinterpret_cast<uint32_t *>(q); q += up16(recs * 4);
-  b.cnt = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
-  b.work = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
-  b.ctl = reinterpret_cast<uint32_t *>(q);
+  carveCollectLong(scratch, b);
 #define CL_CALL(K) launchCollectLongK<K>(d, data, n, b, cap, count, result, start, end, cfg, stream)
   REDGPU_KIND_SWITCH(CL_CALL)
 #undef CL_CALL
@@ -589,7 +642,7 @@ hipError_t launchReplaceLong(const DevDfa &d, int style, int doLeader, const uin
     if (phases & 1) hipLaunchKernelGGL(k_rl_empty, dim3(1), dim3(64), 0, stream, count, outLen);
     return hipGetLastError();
   }
-  const ClAttempt a{style, doLeader && d.leaderLen > 0 ? 1 : 0};
+  const LongAttempt a{style, doLeader && d.leaderLen > 0 ? 1 : 0};
   // one chunk (the chain in order, on one lane) for a short text, and where failing attempts
   // cannot end early: no pure dead state, under a style that walks on behind an accept
   const bool early = d.nPureDead > 0 || style == kStyInstant || style == kStyFirst ||
@@ -603,28 +656,10 @@ hipError_t launchReplaceLong(const DevDfa &d, int style, int doLeader, const uin
   b.m = (n + c - 1) / c;
   b.chunk = uint32_t(c < n ? c : n);
   b.slots = b.chunk;
-  const uint64_t nb = (b.m + 1023) / 1024;
-  auto up16 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
-  const uint64_t recs = b.m * b.slots;
-  const size_t bytes = up16(b.m * 8) * 5 + up16(nb * 8) * 3 + up16(recs * 8) + up16(recs * 4) +
-                       up16(b.m * 4) * 2 + 64;
   void *scratch = nullptr;
-  hipError_t e = raggedScratch(stream, bytes, &scratch);
+  hipError_t e = raggedScratch(stream, carveReplaceLong(nullptr, b, r), &scratch);
   if (e != hipSuccess) return e;
-  uint8_t *q = static_cast<uint8_t *>(scratch);
-  b.ent = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  b.exit = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  b.off = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  r.rem = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  r.cov = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  b.blockOff = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
-  r.blockRem = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
-  r.blockCov = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
-  b.ren = reinterpret_cast<uint64_t *>(q); q += up16(recs * 8);
-  b.rat = reinterpret_cast<uint32_t *>(q); q += up16(recs * 4);
-  b.cnt = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
-  b.work = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
-  b.ctl = reinterpret_cast<uint32_t *>(q);
+  carveReplaceLong(scratch, b, r);
   if (phases & 1) {
     e = [&]() -> hipError_t {
 #define RL_CALL(K) launchClChain<K, kClReplace>(d, data, n, b, a, count, cfg, stream)
@@ -661,19 +696,14 @@ hipError_t launchSearchLong(const DevDfa &d, int style, int doLeader, const uint
   SlBufs b{};
   b.m = (n + c - 1) / c;
   b.chunk = uint32_t(c);
-  auto up16 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
-  const size_t bytes = 64 + up16(b.m * 8) * 2 + up16(b.m * 4) * 2;
   void *scratch = nullptr;
-  hipError_t e = raggedScratch(stream, bytes, &scratch);
+  hipError_t e = raggedScratch(stream, carveSearchLong(nullptr, b), &scratch);
   if (e != hipSuccess) return e;
-  uint8_t *q = static_cast<uint8_t *>(scratch);
-  b.ctl = reinterpret_cast<uint64_t *>(q); q += 64;
-  b.rst = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  b.ren = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  b.res = reinterpret_cast<int32_t *>(q); q += up16(b.m * 4);
-  b.state = reinterpret_cast<uint32_t *>(q);
-  const SlAttempt a{style, lead, lead && d.init >= d.firstAccept ? 1 : 0};
-#define SL_CALL(K) launchSearchLongK<K>(d, data, n, b, a, result, start, end, cfg, stream)
+  carveSearchLong(scratch, b);
+  const LongAttempt a{style, lead};
+  // the leader test in front of an accepting initial state: its passes are noted (k_long.h)
+  const int mark = lead && d.init >= d.firstAccept ? 1 : 0;
+#define SL_CALL(K) launchSearchLongK<K>(d, data, n, b, a, mark, result, start, end, cfg, stream)
   REDGPU_KIND_SWITCH(SL_CALL)
 #undef SL_CALL
 }
@@ -710,23 +740,10 @@ hipError_t launchMatchAllLong(const DevDfa &d, int doLeader, const uint8_t *data
   MlBufs b{};
   b.m = (n + c - 1) / c;
   b.chunk = uint32_t(c);
-  const uint64_t nb = (b.m + 1023) / 1024;
-  auto up16 = [](uint64_t x) { return (x + 15) & ~uint64_t(15); };
-  const size_t bytes = up16(b.m * 8) * 2 + up16(nb * 8) * 2 + up16(b.m * 4) * 5 + 64;
   void *scratch = nullptr;
-  hipError_t e = raggedScratch(stream, bytes, &scratch);
+  hipError_t e = raggedScratch(stream, carveMatchAllLong(nullptr, b), &scratch);
   if (e != hipSuccess) return e;
-  uint8_t *q = static_cast<uint8_t *>(scratch);
-  b.esc = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  b.off = reinterpret_cast<uint64_t *>(q); q += up16(b.m * 8);
-  b.blockOff = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
-  b.blockEsc = reinterpret_cast<uint64_t *>(q); q += up16(nb * 8);
-  b.ent = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
-  b.exit = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
-  b.cnt = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
-  b.head = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
-  b.work = reinterpret_cast<uint32_t *>(q); q += up16(b.m * 4);
-  b.ctl = reinterpret_cast<uint32_t *>(q);
+  carveMatchAllLong(scratch, b);
   *ctl = b.ctl;
   const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
 #define ML_CALL(K) launchMatchAllLongK<K>(d, data, n, b, lead, cap, count, result, start, end, cfg, stream)

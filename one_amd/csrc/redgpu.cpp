@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -235,6 +236,72 @@ int rawTextDev(const redgpu_dfa *dfa, hipStream_t s, uint64_t scratchBytes, F &&
   tlsKernel = name;
   if (e != hipSuccess) return failHip(e, "kernel launch");
   return REDGPU_OK;
+}
+
+// The arguments of both forms of a long-text verb (collect_long, match_all_long, replace_long,
+// search_long): what can be refused without a device first, in this order - no handle, a bad style
+// (style null: the verb takes none), the verb's own refusals as listed, a text too large or cut
+// into too many chunks, and last whether the handle has a device image (so a device-less handle
+// still names a bad argument).
+struct Refusal {
+  bool bad;
+  const char *why;
+};
+
+static int checkLongText(const redgpu_dfa *dfa, const int *style,
+                         std::initializer_list<Refusal> refusals, uint64_t len,
+                         uint32_t chunkBytes) {
+  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
+  if (style)
+    if (int rc = checkStyle(*style)) return rc;
+  for (const Refusal &r : refusals)
+    if (r.bad) return fail(REDGPU_EAPI, r.why);
+  if (len >= (1ull << 40)) return fail(REDGPU_ELIMIT, "text too large");
+  if (chunkBytes && (len + chunkBytes - 1) / chunkBytes >= (1ull << 31))
+    return fail(REDGPU_ELIMIT, "too many chunks");
+  return checkHandle(dfa);
+}
+
+// The _dev form of a long-text verb behind its argument check: the device, the verb's launcher -
+// which launch(&name) calls, and which takes its scratch from the stream's - nothing read back
+template <class F>
+static int longTextDev(const redgpu_dfa *dfa, F &&launch) {
+  DeviceScope scope(dfa->im->device);
+  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
+  const char *name = "";
+  const hipError_t e = launch(&name);
+  tlsKernel = name;
+  if (e != hipSuccess) return failHip(e, "kernel launch");
+  return REDGPU_OK;
+}
+
+// The host form of the two verbs that return (count, result, start, end) up to cap: the whole
+// text goes up once, dev(data, count, result, start, end, stream) is the verb's _dev form over the
+// staged buffers, the count and the records that were kept come back
+template <class F>
+static int longRecordsHost(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint64_t cap,
+                           uint64_t *count, int32_t *result, uint64_t *start, uint64_t *end,
+                           F &&dev) {
+  if (cap > (~0ull / 16)) return fail(REDGPU_ELIMIT, "cap too large");
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dCnt = call.buf<uint64_t>(kSlAux0, 1, "count");
+  int32_t *dRes = call.buf<int32_t>(kSlRes, cap + 1, "result");
+  uint64_t *dStart = start ? call.buf<uint64_t>(kSlStart, cap + 1, "start") : nullptr;
+  uint64_t *dEnd = end ? call.buf<uint64_t>(kSlEnd, cap + 1, "end") : nullptr;
+  call.upload(dData, data, len, "data");
+  call.run([&] { return dev(dData, dCnt, cap ? dRes : nullptr, dStart, dEnd, call.stream()); });
+  uint64_t found = 0;
+  call.download(&found, dCnt, 1, "count");
+  if (int rc = call.wait()) return rc;
+  *count = found;
+  const uint64_t got = found < cap ? found : cap;
+  if (got) {
+    call.download(result, dRes, got, "result");
+    if (start) call.download(start, dStart, got, "start");
+    if (end) call.download(end, dEnd, got, "end");
+  }
+  return call.wait();
 }
 
 // The optional record columns of the grep_text / collect_text host forms: device buffers of cap
@@ -756,136 +823,66 @@ static int listHost(const redgpu_dfa *dfa, int listVerb, const uint8_t *data,
   return call.wait();
 }
 
-// Red::collect over one text, chunk-parallel (k_collect_long.h)
-static int collectLongDev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
-                          uint32_t chunkBytes, uint64_t cap, uint64_t *count, int32_t *result,
-                          uint64_t *start, uint64_t *end, hipStream_t stream) {
-  if (int rc = checkHandle(dfa)) return rc;
-  if (!count) return fail(REDGPU_EAPI, "null count buffer");
-  if (cap && !result) return fail(REDGPU_EAPI, "null result buffer");
-  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  if (len >= (1ull << 40)) return fail(REDGPU_ELIMIT, "text too large");
-  if (chunkBytes && (len + chunkBytes - 1) / chunkBytes >= (1ull << 31))
-    return fail(REDGPU_ELIMIT, "too many chunks");
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  const LaunchCfg cfg{dfa->numCUs, (dfa->flags & REDGPU_F_FORCE_GENERIC) ? 1 : 0};
-  const char *name = "";
-  const hipError_t e = launchCollectLong(dfa->im->dev, data, len, chunkBytes, cap, count, result,
-                                         start, end, cfg, stream, &name);
-  tlsKernel = name;
-  if (e != hipSuccess) return failHip(e, "kernel launch");
-  return REDGPU_OK;
+static int checkRecordsLong(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
+                            uint32_t chunkBytes, uint64_t cap, const uint64_t *count,
+                            const int32_t *result) {
+  return checkLongText(dfa, nullptr,
+                       {{!count, "null count buffer"},
+                        {cap && !result, "null result buffer"},
+                        {len && !data, "null data buffer"}},
+                       len, chunkBytes);
 }
 
+// Red::collect over one text, chunk-parallel (k_collect_long.h)
 int redgpu_collect_long_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
                             uint32_t chunk_bytes, uint64_t cap, uint64_t *count, int32_t *result,
                             uint64_t *start, uint64_t *end, void *stream) {
-  return collectLongDev(dfa, data, len, chunk_bytes, cap, count, result, start, end,
-                        static_cast<hipStream_t>(stream));
+  if (int rc = checkRecordsLong(dfa, data, len, chunk_bytes, cap, count, result)) return rc;
+  return longTextDev(dfa, [&](const char **name) {
+    const LaunchCfg cfg{dfa->numCUs, (dfa->flags & REDGPU_F_FORCE_GENERIC) ? 1 : 0};
+    return launchCollectLong(dfa->im->dev, data, len, chunk_bytes, cap, count, result, start, end,
+                             cfg, static_cast<hipStream_t>(stream), name);
+  });
 }
 
-// the whole text goes up once (the chain crosses all of it), the records come back
 int redgpu_collect_long(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
                         uint32_t chunk_bytes, uint64_t cap, uint64_t *count, int32_t *result,
                         uint64_t *start, uint64_t *end) {
-  if (int rc = checkHandle(dfa)) return rc;
-  if (!count) return fail(REDGPU_EAPI, "null count buffer");
-  if (cap && !result) return fail(REDGPU_EAPI, "null result buffer");
-  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  if (cap > (~0ull / 16)) return fail(REDGPU_ELIMIT, "cap too large");
-  HostCall call(dfa, len);
-  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
-  uint64_t *dCnt = call.buf<uint64_t>(kSlAux0, 1, "count");
-  int32_t *dRes = call.buf<int32_t>(kSlRes, cap + 1, "result");
-  uint64_t *dStart = start ? call.buf<uint64_t>(kSlStart, cap + 1, "start") : nullptr;
-  uint64_t *dEnd = end ? call.buf<uint64_t>(kSlEnd, cap + 1, "end") : nullptr;
-  call.upload(dData, data, len, "data");
-  call.run([&] {
-    return collectLongDev(dfa, dData, len, chunk_bytes, cap, dCnt, cap ? dRes : nullptr, dStart,
-                          dEnd, call.stream());
-  });
-  uint64_t found = 0;
-  call.download(&found, dCnt, 1, "count");
-  if (int rc = call.wait()) return rc;
-  *count = found;
-  const uint64_t got = found < cap ? found : cap;
-  if (got) {
-    call.download(result, dRes, got, "result");
-    if (start) call.download(start, dStart, got, "start");
-    if (end) call.download(end, dEnd, got, "end");
-  }
-  return call.wait();
+  if (int rc = checkRecordsLong(dfa, data, len, chunk_bytes, cap, count, result)) return rc;
+  return longRecordsHost(dfa, data, len, cap, count, result, start, end,
+                         [&](const uint8_t *d, uint64_t *c, int32_t *r, uint64_t *s, uint64_t *e,
+                             hipStream_t st) {
+                           return redgpu_collect_long_dev(dfa, d, len, chunk_bytes, cap, c, r, s, e, st);
+                         });
 }
 
 // the control words of this thread's last chunked match_all_long call, and the stream it ran on
 static thread_local const uint32_t *tlsMlCtl = nullptr;
 static thread_local hipStream_t tlsMlStream = nullptr;
 
-static int matchAllLongArgs(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint64_t cap,
-                            const uint64_t *count, const int32_t *result) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (!count) return fail(REDGPU_EAPI, "null count buffer");
-  if (cap && !result) return fail(REDGPU_EAPI, "null result buffer");
-  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  return checkHandle(dfa);
-}
-
 // matchAll over one text, chunk-parallel (k_match_all_long.h)
-static int matchAllLongDev(const redgpu_dfa *dfa, int doLeader, const uint8_t *data, uint64_t len,
-                           uint32_t chunkBytes, uint64_t cap, uint64_t *count, int32_t *result,
-                           uint64_t *start, uint64_t *end, hipStream_t stream) {
-  if (int rc = matchAllLongArgs(dfa, data, len, cap, count, result)) return rc;
-  if (len >= (1ull << 40)) return fail(REDGPU_ELIMIT, "text too large");
-  if (chunkBytes && (len + chunkBytes - 1) / chunkBytes >= (1ull << 31))
-    return fail(REDGPU_ELIMIT, "too many chunks");
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  const LaunchCfg cfg{dfa->numCUs, (dfa->flags & REDGPU_F_FORCE_GENERIC) ? 1 : 0};
-  const char *name = "";
-  const hipError_t e = launchMatchAllLong(dfa->im->dev, doLeader ? 1 : 0, data, len, chunkBytes, cap,
-                                          count, result, start, end, cfg, stream, &name, &tlsMlCtl);
-  tlsMlStream = stream;
-  tlsKernel = name;
-  if (e != hipSuccess) return failHip(e, "kernel launch");
-  return REDGPU_OK;
-}
-
 int redgpu_match_all_long_dev(const redgpu_dfa *dfa, int do_leader, const uint8_t *data,
                               uint64_t len, uint32_t chunk_bytes, uint64_t cap, uint64_t *count,
                               int32_t *result, uint64_t *start, uint64_t *end, void *stream) {
-  return matchAllLongDev(dfa, do_leader, data, len, chunk_bytes, cap, count, result, start, end,
-                         static_cast<hipStream_t>(stream));
+  if (int rc = checkRecordsLong(dfa, data, len, chunk_bytes, cap, count, result)) return rc;
+  return longTextDev(dfa, [&](const char **name) {
+    const LaunchCfg cfg{dfa->numCUs, (dfa->flags & REDGPU_F_FORCE_GENERIC) ? 1 : 0};
+    tlsMlStream = static_cast<hipStream_t>(stream);
+    return launchMatchAllLong(dfa->im->dev, do_leader ? 1 : 0, data, len, chunk_bytes, cap, count,
+                              result, start, end, cfg, tlsMlStream, name, &tlsMlCtl);
+  });
 }
 
-// the whole text goes up once, the count and the records that were kept come back
 int redgpu_match_all_long(const redgpu_dfa *dfa, int do_leader, const uint8_t *data, uint64_t len,
                           uint32_t chunk_bytes, uint64_t cap, uint64_t *count, int32_t *result,
                           uint64_t *start, uint64_t *end) {
-  if (int rc = matchAllLongArgs(dfa, data, len, cap, count, result)) return rc;
-  if (cap > (~0ull / 16)) return fail(REDGPU_ELIMIT, "cap too large");
-  HostCall call(dfa, len);
-  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
-  uint64_t *dCnt = call.buf<uint64_t>(kSlAux0, 1, "count");
-  int32_t *dRes = call.buf<int32_t>(kSlRes, cap + 1, "result");
-  uint64_t *dStart = start ? call.buf<uint64_t>(kSlStart, cap + 1, "start") : nullptr;
-  uint64_t *dEnd = end ? call.buf<uint64_t>(kSlEnd, cap + 1, "end") : nullptr;
-  call.upload(dData, data, len, "data");
-  call.run([&] {
-    return matchAllLongDev(dfa, do_leader, dData, len, chunk_bytes, cap, dCnt,
-                           cap ? dRes : nullptr, dStart, dEnd, call.stream());
-  });
-  uint64_t found = 0;
-  call.download(&found, dCnt, 1, "count");
-  if (int rc = call.wait()) return rc;
-  *count = found;
-  const uint64_t got = found < cap ? found : cap;
-  if (got) {
-    call.download(result, dRes, got, "result");
-    if (start) call.download(start, dStart, got, "start");
-    if (end) call.download(end, dEnd, got, "end");
-  }
-  return call.wait();
+  if (int rc = checkRecordsLong(dfa, data, len, chunk_bytes, cap, count, result)) return rc;
+  return longRecordsHost(dfa, data, len, cap, count, result, start, end,
+                         [&](const uint8_t *d, uint64_t *c, int32_t *r, uint64_t *s, uint64_t *e,
+                             hipStream_t st) {
+                           return redgpu_match_all_long_dev(dfa, do_leader, d, len, chunk_bytes, cap, c,
+                                                            r, s, e, st);
+                         });
 }
 
 // how the calling thread's last redgpu_match_all_long_dev call resolved its chunks
@@ -966,21 +963,15 @@ int redgpu_replace_batch(const redgpu_dfa *dfa, int style, int do_leader, const 
   return call.wait();
 }
 
-// the arguments of both forms, in this order: the handle, the style, the buffers, the limits, and
-// last whether the handle has a device image (so a device-less handle still names a bad argument)
 static int checkReplaceLong(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
                             uint32_t chunkBytes, const uint8_t *repl, uint64_t replLen,
                             const uint64_t *count, const uint64_t *outLen) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (int rc = checkStyle(style)) return rc;
-  if (!count) return fail(REDGPU_EAPI, "null count buffer");
-  if (!outLen) return fail(REDGPU_EAPI, "null out_len buffer");
-  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  if (replLen && !repl) return fail(REDGPU_EAPI, "null replacement");
-  if (len >= (1ull << 40)) return fail(REDGPU_ELIMIT, "text too large");
-  if (chunkBytes && (len + chunkBytes - 1) / chunkBytes >= (1ull << 31))
-    return fail(REDGPU_ELIMIT, "too many chunks");
-  return checkHandle(dfa);
+  return checkLongText(dfa, &style,
+                       {{!count, "null count buffer"},
+                        {!outLen, "null out_len buffer"},
+                        {len && !data, "null data buffer"},
+                        {replLen && !repl, "null replacement"}},
+                       len, chunkBytes);
 }
 
 // replaceCore over one text, chunk-parallel (k_replace_long.h); phases as launchReplaceLong's
@@ -990,16 +981,11 @@ static int replaceLongDev(const redgpu_dfa *dfa, int style, int doLeader, const 
                           uint64_t outCap, int phases, hipStream_t stream) {
   if (int rc = checkReplaceLong(dfa, style, data, len, chunkBytes, repl, replLen, count, outLen))
     return rc;
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  const LaunchCfg cfg{dfa->numCUs, 0};
-  const char *name = "";
-  const hipError_t e = launchReplaceLong(dfa->im->dev, style, doLeader ? 1 : 0, data, len,
-                                         chunkBytes, repl, replLen, maxCount, count, outLen, out,
-                                         outCap, phases, cfg, stream, &name);
-  tlsKernel = name;
-  if (e != hipSuccess) return failHip(e, "kernel launch");
-  return REDGPU_OK;
+  return longTextDev(dfa, [&](const char **name) {
+    return launchReplaceLong(dfa->im->dev, style, doLeader ? 1 : 0, data, len, chunkBytes, repl,
+                             replLen, maxCount, count, outLen, out, outCap, phases,
+                             LaunchCfg{dfa->numCUs, 0}, stream, name);
+  });
 }
 
 int redgpu_replace_long_dev(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
@@ -1045,18 +1031,11 @@ int redgpu_replace_long(const redgpu_dfa *dfa, int style, int do_leader, const u
   return call.wait();
 }
 
-// the arguments of both forms, in checkReplaceLong's order: the handle, the style, the buffers,
-// the limits, and last whether the handle has a device image
 static int checkSearchLong(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
                            uint32_t chunkBytes, const int32_t *result) {
-  if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
-  if (int rc = checkStyle(style)) return rc;
-  if (!result) return fail(REDGPU_EAPI, "null result buffer");
-  if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
-  if (len >= (1ull << 40)) return fail(REDGPU_ELIMIT, "text too large");
-  if (chunkBytes && (len + chunkBytes - 1) / chunkBytes >= (1ull << 31))
-    return fail(REDGPU_ELIMIT, "too many chunks");
-  return checkHandle(dfa);
+  return checkLongText(dfa, &style,
+                       {{!result, "null result buffer"}, {len && !data, "null data buffer"}}, len,
+                       chunkBytes);
 }
 
 // searchCore over one text, chunk-parallel (k_search_long.h)
@@ -1064,16 +1043,10 @@ int redgpu_search_long_dev(const redgpu_dfa *dfa, int style, int do_leader, cons
                            uint64_t len, uint32_t chunk_bytes, int32_t *result, uint64_t *start,
                            uint64_t *end, void *stream) {
   if (int rc = checkSearchLong(dfa, style, data, len, chunk_bytes, result)) return rc;
-  DeviceScope scope(dfa->im->device);
-  if (scope.err != hipSuccess) return failHip(scope.err, "hipSetDevice");
-  const LaunchCfg cfg = cfgOf(dfa);
-  const char *name = "";
-  const hipError_t e = launchSearchLong(dfa->im->dev, style, do_leader ? 1 : 0, data, len,
-                                        chunk_bytes, result, start, end, cfg,
-                                        static_cast<hipStream_t>(stream), &name);
-  tlsKernel = name;
-  if (e != hipSuccess) return failHip(e, "kernel launch");
-  return REDGPU_OK;
+  return longTextDev(dfa, [&](const char **name) {
+    return launchSearchLong(dfa->im->dev, style, do_leader ? 1 : 0, data, len, chunk_bytes, result,
+                            start, end, cfgOf(dfa), static_cast<hipStream_t>(stream), name);
+  });
 }
 
 // the text goes up once, the three values of the Outcome come back

@@ -517,6 +517,55 @@ def collect(exe, text: bytes, cap: int = 64):
     return [(int(res[0, i]), int(st[0, i]), int(en[0, i])) for i in range(k)]
 
 
+def _device_text(text):
+    """a long-text verb's device input, checked -> (device, torch's current stream on it)"""
+    import torch
+    if not text.is_cuda or text.dtype != torch.uint8 or not text.is_contiguous():
+        raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+    return text.device, torch.cuda.current_stream(text.device)
+
+
+def _long_records(entry, head, text, cap, chunk_bytes):
+    """collect_long / match_all_long: redgpu_<entry>[_dev](*head, data, len, chunk_bytes, room,
+    count, result, start, end[, stream]) over a host or a device text; with cap=None once more
+    with room for every record when the first 4096 slots were not enough"""
+    if cap is not None and cap < 0:
+        raise RedExceptApi("cap must be >= 0")
+    room = 4096 if cap is None else cap
+    if _is_torch(text):
+        import torch
+        dev, stream = _device_text(text)
+        for _ in range(2):
+            cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+            res = torch.empty(max(room, 1), dtype=torch.int32, device=dev)
+            st = torch.empty(max(room, 1), dtype=torch.int64, device=dev)
+            en = torch.empty(max(room, 1), dtype=torch.int64, device=dev)
+            _check(getattr(_lib.lib(), "redgpu_%s_dev" % entry)(
+                *head, text.data_ptr() if text.numel() else None, text.numel(), int(chunk_bytes),
+                room, cnt.data_ptr(), res.data_ptr(), st.data_ptr(), en.data_ptr(),
+                stream.cuda_stream))
+            count = int(cnt.item())
+            if cap is not None or count <= room:
+                break
+            room = count
+    else:
+        a = _host_u8(text)
+        for _ in range(2):
+            cnt = C.c_uint64(0)
+            res = np.zeros(max(room, 1), dtype=np.int32)
+            st = np.zeros(max(room, 1), dtype=np.uint64)
+            en = np.zeros(max(room, 1), dtype=np.uint64)
+            _check(getattr(_lib.lib(), "redgpu_" + entry)(
+                *head, a.ctypes.data if a.size else None, a.size, int(chunk_bytes), room,
+                C.byref(cnt), res.ctypes.data, st.ctypes.data, en.ctypes.data))
+            count = int(cnt.value)
+            if cap is not None or count <= room:
+                break
+            room = count
+    k = min(count, room)
+    return count, res[:k], st[:k], en[:k]
+
+
 def collect_long(exe, text, cap=None, *, chunk_bytes=0):
     """Red::collect (lib/Red.cpp:103-116) over ONE long text, chunk-parallel on the GPU
     (redgpu_collect_long[_dev]) -> (count, result int32[k], start uint64[k], end uint64[k]) with
@@ -524,46 +573,7 @@ def collect_long(exe, text, cap=None, *, chunk_bytes=0):
     CUDA tensor (the _dev form on torch's current stream; the arrays come back as CUDA tensors and
     count as an int after a synchronisation of that stream).  cap=None: room for every match (a
     second call when the first 4096 slots were not enough).  chunk_bytes=0: automatic."""
-    if cap is not None and cap < 0:
-        raise RedExceptApi("cap must be >= 0")
-    if _is_torch(text):
-        import torch
-        if not text.is_cuda or text.dtype != torch.uint8 or not text.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = text.device
-        stream = torch.cuda.current_stream(dev)
-        room = 4096 if cap is None else cap
-        for _ in range(2):
-            cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-            res = torch.empty(max(room, 1), dtype=torch.int32, device=dev)
-            st = torch.empty(max(room, 1), dtype=torch.int64, device=dev)
-            en = torch.empty(max(room, 1), dtype=torch.int64, device=dev)
-            _check(_lib.lib().redgpu_collect_long_dev(
-                exe._h, text.data_ptr() if text.numel() else None, text.numel(), int(chunk_bytes),
-                room, cnt.data_ptr(), res.data_ptr(), st.data_ptr(), en.data_ptr(),
-                stream.cuda_stream))
-            count = int(cnt.item())
-            if cap is not None or count <= room:
-                break
-            room = count
-        k = min(count, room)
-        return count, res[:k], st[:k], en[:k]
-    a = _host_u8(text)
-    room = 4096 if cap is None else cap
-    for _ in range(2):
-        cnt = C.c_uint64(0)
-        res = np.zeros(max(room, 1), dtype=np.int32)
-        st = np.zeros(max(room, 1), dtype=np.uint64)
-        en = np.zeros(max(room, 1), dtype=np.uint64)
-        _check(_lib.lib().redgpu_collect_long(
-            exe._h, a.ctypes.data if a.size else None, a.size, int(chunk_bytes), room,
-            C.byref(cnt), res.ctypes.data, st.ctypes.data, en.ctypes.data))
-        count = int(cnt.value)
-        if cap is not None or count <= room:
-            break
-        room = count
-    k = min(count, room)
-    return count, res[:k], st[:k], en[:k]
+    return _long_records("collect_long", (exe._h,), text, cap, chunk_bytes)
 
 
 def match_all_long(exe, text, cap=None, do_leader=True, *, chunk_bytes=0):
@@ -572,47 +582,7 @@ def match_all_long(exe, text, cap=None, do_leader=True, *, chunk_bytes=0):
     int32[k], start uint64[k], end uint64[k]) with k = min(count, cap).  text, cap and chunk_bytes
     as in collect_long: bytes / numpy uint8, or a contiguous uint8 CUDA tensor on torch's current
     stream (the arrays then come back as CUDA tensors)."""
-    if cap is not None and cap < 0:
-        raise RedExceptApi("cap must be >= 0")
-    lead = 1 if do_leader else 0
-    if _is_torch(text):
-        import torch
-        if not text.is_cuda or text.dtype != torch.uint8 or not text.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = text.device
-        stream = torch.cuda.current_stream(dev)
-        room = 4096 if cap is None else cap
-        for _ in range(2):
-            cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-            res = torch.empty(max(room, 1), dtype=torch.int32, device=dev)
-            st = torch.empty(max(room, 1), dtype=torch.int64, device=dev)
-            en = torch.empty(max(room, 1), dtype=torch.int64, device=dev)
-            _check(_lib.lib().redgpu_match_all_long_dev(
-                exe._h, lead, text.data_ptr() if text.numel() else None, text.numel(),
-                int(chunk_bytes), room, cnt.data_ptr(), res.data_ptr(), st.data_ptr(),
-                en.data_ptr(), stream.cuda_stream))
-            count = int(cnt.item())
-            if cap is not None or count <= room:
-                break
-            room = count
-        k = min(count, room)
-        return count, res[:k], st[:k], en[:k]
-    a = _host_u8(text)
-    room = 4096 if cap is None else cap
-    for _ in range(2):
-        cnt = C.c_uint64(0)
-        res = np.zeros(max(room, 1), dtype=np.int32)
-        st = np.zeros(max(room, 1), dtype=np.uint64)
-        en = np.zeros(max(room, 1), dtype=np.uint64)
-        _check(_lib.lib().redgpu_match_all_long(
-            exe._h, lead, a.ctypes.data if a.size else None, a.size, int(chunk_bytes), room,
-            C.byref(cnt), res.ctypes.data, st.ctypes.data, en.ctypes.data))
-        count = int(cnt.value)
-        if cap is not None or count <= room:
-            break
-        room = count
-    k = min(count, room)
-    return count, res[:k], st[:k], en[:k]
+    return _long_records("match_all_long", (exe._h, 1 if do_leader else 0), text, cap, chunk_bytes)
 
 
 def match_all_batch(exe, data, cap, do_leader=True, *, offsets=None, stride=0, n=None,
@@ -800,10 +770,7 @@ def replace_long(exe, text, repl: bytes, style=styLast, do_leader=True, max_coun
     l = _lib.lib()
     if _is_torch(text):
         import torch
-        if not text.is_cuda or text.dtype != torch.uint8 or not text.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = text.device
-        stream = torch.cuda.current_stream(dev)
+        dev, stream = _device_text(text)
         drepl = torch.from_numpy(r.copy()).to(dev) if r.size else None
         sizes = torch.zeros(2, dtype=torch.int64, device=dev)
 
@@ -857,15 +824,13 @@ def search_long(exe, text, style=styLast, do_leader=True, *, chunk_bytes=0):
     l = _lib.lib()
     if _is_torch(text):
         import torch
-        if not text.is_cuda or text.dtype != torch.uint8 or not text.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = text.device
+        dev, stream = _device_text(text)
         res = torch.empty(1, dtype=torch.int32, device=dev)
         pos = torch.empty(2, dtype=torch.int64, device=dev)
         _check(l.redgpu_search_long_dev(
             exe._h, int(style), 1 if do_leader else 0, text.data_ptr() if text.numel() else None,
             text.numel(), int(chunk_bytes), res.data_ptr(), pos.data_ptr(), pos.data_ptr() + 8,
-            torch.cuda.current_stream(dev).cuda_stream))
+            stream.cuda_stream))
         return res, pos[0:1], pos[1:2]
     a = _host_u8(text)
     res, st, en = C.c_int32(0), C.c_uint64(0), C.c_uint64(0)

@@ -62,3 +62,42 @@ def expect_of(vec, verb, style_idx, lead):
     if verb in ("match", "search"):
         return res, vec[key + "_start"], vec[key + "_end"]
     return res, None, None
+
+
+# The long-text verbs scan their per-chunk values in blocks of 1024 chunks and the block totals in
+# rounds of 1024 blocks: more than 1024 * 1024 chunks put the second round's carry to work.
+SCAN_ROUND = 1024 * 1024
+_SCAN_TEXT = []
+
+
+def scan_round_text():
+    """(text, chunk_bytes, border): 16 * (2^20 + 1025) + 5 fill bytes 0x01 - 1,049,602 chunks of 16,
+    1,026 blocks - with "New York" every 4,096 bytes, plant k shifted by k % 16 so the plants
+    straddle chunk borders at every offset; border = the first byte of chunk 1024 * 1024"""
+    if not _SCAN_TEXT:
+        chunk = 16
+        n = chunk * (SCAN_ROUND + 1025) + 5
+        a = np.full(n, 0x01, dtype=np.uint8)
+        piece = np.frombuffer(b"New York", dtype=np.uint8)
+        for k, b in enumerate(range(4096, n, 4096), 1):
+            at = b + k % 16
+            if at + len(piece) <= n:
+                a[at:at + len(piece)] = piece
+        assert (n + chunk - 1) // chunk == 1049602 and (1049602 + 1023) // 1024 == 1026
+        _SCAN_TEXT.append((bytes(a), chunk, chunk * SCAN_ROUND))
+    return _SCAN_TEXT[0]
+
+
+def literal_dfa(word):
+    """anchored `word` as a blob: 0 = error (pure dead end), 1 = initial, 2.. = its prefixes, the
+    last accepts (every byte -> error)"""
+    from oracle.reda_writer import write_reda
+    equiv = np.zeros(256, dtype=np.uint8)
+    for k, ch in enumerate(sorted(set(word)), 1):
+        equiv[ch] = k
+    trans = np.zeros((len(word) + 2, int(equiv.max()) + 1), dtype=np.int64)
+    for k, ch in enumerate(word):
+        trans[1 + k, equiv[ch]] = 2 + k
+    result = np.zeros(len(word) + 2, dtype=np.int64)
+    result[-1] = 1
+    return write_reda(trans, result, equiv=equiv, initial=1)

@@ -13,7 +13,7 @@ import one_amd
 import oracle as O
 from one_amd import workloads as W
 from oracle.reda_writer import random_dfa, write_reda
-from golden_util import GOLD, load_dfa, unb64
+from golden_util import GOLD, literal_dfa, load_dfa, scan_round_text, unb64
 
 pytestmark = pytest.mark.gpu
 
@@ -151,6 +151,27 @@ def test_collect_long_chains_that_never_meet():
         assert _check(exe, blob, text, chunk) == ((1 << 20) - 1) // 2
         assert one_amd.last_kernel() == "k_collect_long"
     _check(exe, blob, b"a" * (1 << 20), 16)
+
+
+def test_collect_long_second_round_of_block_totals():
+    """1,049,602 chunks of 16 bytes are 1,026 blocks of 1024: the scan of the block totals carries
+    its sum into a second round, and records lie behind it.  The golden newyork DFA is suffix-closed
+    without a pure dead end - its collect of this text is ONE record, on the route
+    k_collect_long<closed>, whatever the chunk size - so the chunked route gets "New York" as an
+    anchored literal: a record per plant."""
+    text, chunk, border = scan_round_text()
+    blob = load_dfa("newyork")
+    assert _expect(blob, text)[1] == 1
+    blob = literal_dfa(b"New York")
+    exe = one_amd.Executable(blob)
+    assert exe.info["n_pure_dead"] >= 1
+    recs, k = _expect(blob, text)
+    assert k == len(recs) == len(text) // 4096
+    assert all(text[s:e] == b"New York" and r == 1 for r, s, e in recs)
+    assert sum(1 for _, s, _ in recs if s < border) >= 4000
+    assert sum(1 for _, s, _ in recs if s >= border) >= 4
+    assert _check(exe, blob, text, chunk, dev=True) == k
+    assert one_amd.last_kernel() == "k_collect_long"
 
 
 def test_collect_long_cap_smaller_than_count():

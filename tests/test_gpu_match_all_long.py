@@ -17,7 +17,7 @@ import one_amd
 import oracle as O
 from one_amd import workloads as W
 from oracle.reda_writer import random_dfa, write_reda
-from golden_util import GOLD, load_dfa, unb64
+from golden_util import GOLD, load_dfa, scan_round_text, unb64
 
 pytestmark = pytest.mark.gpu
 
@@ -460,3 +460,16 @@ def test_match_all_long_rounds_or_serial_lane():
     out = torch.zeros(8, dtype=torch.int32, device="cuda")
     assert _lib.lib().redgpu_diag_match_all_long_dev(
         exe._h, out.data_ptr(), torch.cuda.current_stream().cuda_stream) == _lib.EAPI
+
+
+# ---- 11. more than 1024 * 1024 chunks: the block totals' second round of 1024 --------------------
+def test_match_all_long_second_round_of_block_totals():
+    """1,049,602 chunks of 16 bytes are 1,026 blocks of 1024: the scan of the block totals carries
+    its sum and its max into a second round, and records open behind it."""
+    text, chunk, border = scan_round_text()
+    d = _dfa("newyork")
+    exe = one_amd.Executable(d.blob)
+    recs = d.expect(text, True)
+    assert sum(1 for _, s, _ in recs if s < border) >= 4000
+    assert sum(1 for _, s, _ in recs if s >= border) >= 4
+    assert _check(exe, d, text, chunk, True, dev=True, route="k_match_all_long") == len(recs)

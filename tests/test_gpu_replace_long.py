@@ -16,7 +16,7 @@ import oracle as O
 from one_amd import _lib
 from one_amd import workloads as W
 from oracle.reda_writer import random_dfa, write_reda
-from golden_util import GOLD, load_dfa, unb64
+from golden_util import GOLD, literal_dfa, load_dfa, scan_round_text, unb64
 
 pytestmark = pytest.mark.gpu
 
@@ -299,6 +299,32 @@ def test_replace_long_device_form_20_mib():
     cnt = _check(exe, blob, text, 0, dev=True)
     assert one_amd.last_kernel() == "k_replace_long"
     assert (n + 255) // 256 > 65536 and cnt > 0
+
+
+def test_replace_long_second_round_of_block_totals():
+    """1,049,602 chunks of 16 bytes are 1,026 blocks of 1024: the scans of the block totals carry
+    their sums and the covered-up-to max into a second round, and records lie behind it.  The
+    golden newyork DFA is suffix-closed without a pure dead end: under styLast its replace of this
+    text is ONE record, and under the styles that stop early every attempt outruns the chunks'
+    budget, so one lane walks the text (23 s on an MI355X) - the chunked route gets "New York" as
+    an anchored literal: a record per plant."""
+    text, chunk, border = scan_round_text()
+    assert _expect(load_dfa("newyork"), text, b"<#>", 4, 1, ALL, key="scan_round_golden")[0] == 1
+    blob = literal_dfa(b"New York")
+    exe = one_amd.Executable(blob)
+    assert exe.info["n_pure_dead"] >= 1
+    count, want = _expect(blob, text, b"<#>", 4, 1, ALL, key="scan_round")
+    assert count == len(text) // 4096 and len(want) == len(text) - 5 * count
+    # replacement k stands 5 k bytes in front of where record k began
+    at, starts = want.find(b"<#>"), []
+    while at >= 0:
+        starts.append(at + 5 * len(starts))
+        at = want.find(b"<#>", at + 3)
+    assert len(starts) == count and all(text[s:s + 8] == b"New York" for s in starts)
+    assert sum(1 for s in starts if s < border) >= 4000
+    assert sum(1 for s in starts if s >= border) >= 4
+    assert _check(exe, blob, text, chunk, key="scan_round", dev=True) == count
+    assert one_amd.last_kernel() == "k_replace_long"
 
 
 def test_replace_long_two_streams_and_threads():

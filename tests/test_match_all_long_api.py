@@ -74,3 +74,21 @@ def test_match_all_long_device_none_handle_refused():
     assert lib.redgpu_match_all_long(exe._h, 1, b"123", 3, 16, 4, C.byref(cnt), res, None,
                                      None) == _lib.EAPI
     assert "device" in lib.redgpu_last_error().decode()
+
+
+@pytest.mark.parametrize("form", ["host", "dev"])
+def test_match_all_long_limits_refused_before_the_device(form):
+    """as for the other long-text verbs: a text too large or cut into too many chunks is refused
+    as such in both forms, before the handle's device image is looked at"""
+    exe = one_amd.Executable(load_dfa("num3"), device="none")
+    lib = _lib.lib()
+    f = lib.redgpu_match_all_long if form == "host" else lib.redgpu_match_all_long_dev
+    extra = [] if form == "host" else [None]
+    cnt = C.c_uint64(0)
+    # (nothing is read: the refusals come from the lengths alone)
+    assert f(exe._h, 1, b"123", 1 << 40, 0, 0, C.byref(cnt), None, None, None,
+             *extra) == _lib.ELIMIT
+    assert "text too large" in lib.redgpu_last_error().decode()
+    assert f(exe._h, 1, b"123", 1 << 31, 1, 0, C.byref(cnt), None, None, None,
+             *extra) == _lib.ELIMIT
+    assert "too many chunks" in lib.redgpu_last_error().decode()
