@@ -774,6 +774,62 @@ int redgpu_extract_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t
                             uint64_t max_per_line, uint64_t *n_lines, uint64_t *n_matches,
                             uint64_t *out_len, uint8_t *out, uint64_t out_cap, void *stream);
 
+/* awk '{ print > file[class] }': raw text in, ALL its lines out as a text, grouped by the result
+ * search reports for each - the fourth thing a log pipeline does with a many-pattern DFA, beside
+ * selecting (grep_text, filter_text), rewriting (replace_text, extract_text) and counting
+ * (tally_text).  The output is the text stably partitioned by bucket, and where each bucket begins.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter (the tail) are not a line and are never emitted.
+ *  - A line's VALUE is search<style,do_leader>(line).result_, 0 when it does not match: exactly
+ *    redgpu_tally_text's REDGPU_TALLY_LINES item, with redgpu_grep_text's verb and style
+ *    normalisation.  Its BUCKET is r when (uint32_t)r < n_bins, else n_bins ("everything else"):
+ *    redgpu_tally_text's slot rule, n_bins + 1 buckets.  n_bins == 0 is legal: one bucket, the
+ *    output is the text without its tail.  n_bins > 255 is REDGPU_ELIMIT: a line's bucket is kept
+ *    in at most 8 bit-planes of the delimiter bitmap's layout.
+ *  - The output is bucket 0's lines, then bucket 1's, ..., then bucket n_bins': inside a bucket the
+ *    lines are in text order, each followed by its delimiter.  Every section is a raw text every
+ *    text verb accepts.
+ *  - drop_unmatched != 0: lines of value 0 are not emitted - they are still counted in
+ *    bin_lines[0].  (Under n_bins == 0 bucket 0 then still holds the lines that match.)
+ *  - bin_lines[n_bins + 1] = lines per bucket, dropped ones included: redgpu_tally_text's LINES bins,
+ *    bit for bit.  May be NULL.
+ *  - bin_offsets[n_bins + 2] = the byte offset in the output at which bucket b's section begins (an
+ *    exclusive prefix sum of the sections' lengths); bin_offsets[n_bins + 1] == *out_len.  Required.
+ *  - *out_len = the length of the whole output, whatever out_cap is (required); *n_lines =
+ *    delimiters found, *n_routed = lines emitted; both may be NULL, each on its own.
+ *  - out == NULL or out_cap == 0 gives the sizes only.  Otherwise exactly the first
+ *    min(*out_len, out_cap) bytes of the concatenated output are written - the cut may fall inside
+ *    a line or between two sections - and bytes of out from there on are NOT written
+ *    (redgpu_filter_text's rule): out may be the middle of a larger buffer.  out must not overlap
+ *    data.
+ *  - REDGPU_EAPI for a NULL handle, a NULL bin_offsets, a NULL out_len, a NULL data with len > 0
+ *    (the argument checks run before the handle's device is looked at) and for a
+ *    REDGPU_DEVICE_NONE handle; REDGPU_EEXEC for a style that does not exist; REDGPU_ELIMIT for a
+ *    text redgpu_split_lines refuses and for n_bins > 255.  In every error case nothing of the
+ *    caller's is written.
+ *  - An empty text, or one without a delimiter: all counts and offsets are 0 and nothing is
+ *    written to out (the _dev form writes them on the stream).
+ *  - A single line of megabytes is walked by one lane; a chunk whose lines alternate between many
+ *    buckets is copied as many short runs, each by a whole wave: correct, and slow.
+ * redgpu_last_kernel() says "k_route_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - nothing is read
+ * back, and no per-line array is needed from the caller or in scratch (a line's bucket lives in
+ * P bit-planes, P = the bit width of n_bins, 1 under n_bins == 0 with drop_unmatched; the sizes are
+ * per (bucket, 16 KiB chunk), C = n_bins + 1 buckets, 2 in that case; scratch is (1 + P) * len / 8
+ * for the bitmaps + (20 + 20 * C) bytes per chunk + 8 bytes per 1,024 (bucket, chunk) pairs + 72,
+ * rounded up to 16, from the thread's pool).
+ * redgpu_route_text: host buffers, as redgpu_filter_text - one upload of the text, a sizes pass,
+ * a device output sized from *out_len, and min(*out_len, out_cap) bytes downloaded. */
+int redgpu_route_text(const redgpu_dfa *dfa, int style, int do_leader, int drop_unmatched,
+                      const uint8_t *data, uint64_t len, uint8_t delim, uint64_t n_bins,
+                      uint64_t *n_lines, uint64_t *n_routed, uint64_t *bin_lines,
+                      uint64_t *bin_offsets, uint64_t *out_len, uint8_t *out, uint64_t out_cap);
+int redgpu_route_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int drop_unmatched,
+                          const uint8_t *data, uint64_t len, uint8_t delim, uint64_t n_bins,
+                          uint64_t *n_lines, uint64_t *n_routed, uint64_t *bin_lines,
+                          uint64_t *bin_offsets, uint64_t *out_len, uint8_t *out, uint64_t out_cap,
+                          void *stream);
+
 /* Measurement aid, no counterpart in the reference: one streaming read of `bytes` of device
  * memory (16-byte aligned) on the handle's device, asynchronous on `stream` - the read-bandwidth
  * calibration bench.py reports beside the roofline.  `sink` is a device uint32 the kernel may

@@ -334,6 +334,35 @@ inline size_t filterText(const Executable &exec, Style style, bool doLeader, std
   return size_t(selected);
 }
 
+// awk '{ print > file[class] }' (redgpu_route_text): every line of a text blob put in `out`, grouped
+// by the result search<style,doLeader> reports for it - bucket r for a result r < nBins, bucket
+// nBins for everything else (nBins <= 255), the lines of a bucket in text order with their
+// delimiters; lines that do not match are left out under dropUnmatched (and still counted).
+// binLines[b] = the lines of bucket b (nBins + 1 of them), binOffsets[b] = where its section begins
+// in `out` (nBins + 2: the last one is out.size()).  Returns the lines emitted; *lines = delimiters
+// found.  `out` is sized from a first call that only sizes.
+inline size_t routeText(const Executable &exec, Style style, bool doLeader, std::string_view text,
+                        size_t nBins, std::string &out, std::vector<uint64_t> &binLines,
+                        std::vector<uint64_t> &binOffsets, bool dropUnmatched = false,
+                        char delim = '\n', size_t *lines = nullptr) {
+  const Byte *p = reinterpret_cast<const Byte *>(text.data());
+  if (nBins > 255) throw RedExceptLimit("n_bins too large");
+  binLines.assign(nBins + 1, 0);
+  binOffsets.assign(nBins + 2, 0);
+  uint64_t found = 0, routed = 0, outLen = 0;
+  throwOnError(redgpu_route_text(exec.handle(), style, doLeader, dropUnmatched, p, text.size(),
+                                 Byte(delim), nBins, &found, &routed, binLines.data(),
+                                 binOffsets.data(), &outLen, nullptr, 0));
+  out.resize(size_t(outLen));
+  if (outLen)
+    throwOnError(redgpu_route_text(exec.handle(), style, doLeader, dropUnmatched, p, text.size(),
+                                   Byte(delim), nBins, &found, &routed, binLines.data(),
+                                   binOffsets.data(), &outLen,
+                                   reinterpret_cast<Byte *>(out.data()), outLen));
+  if (lines) *lines = size_t(found);
+  return size_t(routed);
+}
+
 // grep -o as a text (redgpu_extract_text): every match of every line of a text blob put in `out`,
 // one per line - the bytes replace<styLast,false> would substitute, each followed by the delimiter,
 // in text order; at most maxPerLine of a line (1 = its first match).  Output line j is the bytes of

@@ -263,6 +263,80 @@ k_ft_totals(const uint32_t *emitLines, uint64_t nChunks, const uint64_t *outTota
   }
 }
 
+// The runs of one chunk's emitted lines (e: this lane's EMIT bits, a subset of its delimiter bits)
+// copied to out from dstAt on, cut at cap - k_ft_write's body, and k_route_text.h's once per
+// bucket.  h: the chunk's views (h.s is not read).  Every lane calls; dstAt and cap are uniform.
+__device__ __forceinline__ void ftWriteRuns(const uint8_t *data, const TextHits &h, const GpBits &e,
+                                            uint64_t dstAt, uint8_t *out, uint64_t cap,
+                                            uint32_t lane) {
+  // is the delimiter below the lane's bits emitted (none: no), and the one above them
+  const uint32_t own = h.g.m.count();
+  uint32_t below = 0, above = 0xffffffffu;
+  if (own) {
+    uint32_t top = 0, bottom = 0;  // is the lane's highest / lowest delimiter emitted
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint64_t x = h.g.m.w[k], y = h.g.m.w[3 - k];
+      if (x) top = (e.w[k] >> (63 - __clzll(static_cast<long long>(x)))) & 1u;
+      if (y) bottom = (e.w[3 - k] >> (__ffsll(static_cast<long long>(y)) - 1)) & 1u;
+    }
+    below = (lane << 1 | top) + 1;
+    above = lane << 1 | bottom;
+  }
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(below, o), u = __shfl_down(above, o);
+    if (lane >= uint32_t(o) && v > below) below = v;
+    if (lane + uint32_t(o) < 64 && u < above) above = u;
+  }
+  below = __shfl_up(below, 1);
+  above = __shfl_down(above, 1);
+  bool on = lane != 0 && below != 0 && ((below - 1) & 1u);
+  bool onAbove = lane != 63 && above != 0xffffffffu && (above & 1u);
+  // the delimiters that begin a run of emitted lines, and those that end one
+  GpBits begins{{0, 0, 0, 0}}, ends{{0, 0, 0, 0}};
+  ftEachUp(h.g.m, [&](auto word, uint64_t bit) {
+    constexpr int k = decltype(word)::value;
+    const bool is = (e.w[k] & bit) != 0;
+    if (is && !on) begins.w[k] |= bit;
+    on = is;
+  });
+  ftEachDown(h.g.m, [&](auto word, uint64_t bit) {
+    constexpr int k = decltype(word)::value;
+    const bool is = (e.w[k] & bit) != 0;
+    if (is && !onAbove) ends.w[k] |= bit;
+    onAbove = is;
+  });
+  GpChunk first, last;
+  first.m = begins;
+  last.m = ends;
+  first.scan(lane);
+  last.scan(lane);  // (last.total == first.total: the runs)
+  for (uint32_t k0 = 0; k0 < first.total && dstAt < cap; k0 += 64) {
+    const uint32_t k = k0 + lane;
+    const bool have = k < first.total;
+    const uint32_t pick = have ? k : first.total - 1;
+    const uint32_t endPos = last.select(pick);
+    uint64_t beg, fin;
+    uint32_t index;  // (not needed here)
+    h.line(first.select(pick), beg, fin, index);  // the run's first line
+    const uint64_t mine = have ? h.base + endPos + 1 - beg : 0;
+    uint64_t incl = mine;
+    for (int sh = 1; sh < 64; sh <<= 1) {
+      const uint64_t v = __shfl_up(incl, sh);
+      if (lane >= uint32_t(sh)) incl += v;
+    }
+    const uint64_t dst = dstAt + (incl - mine);
+    dstAt += __shfl(incl, 63);
+    // the runs, one after the other, by the whole wave
+    uint64_t todo = __ballot(have);
+    while (todo) {
+      const int j = __ffsll(static_cast<long long>(todo)) - 1;
+      todo &= todo - 1;
+      rtCopyWave(out, __shfl(dst, j), data + __shfl(beg, j), __shfl(mine, j), cap, lane);
+    }
+  }
+}
+
 // b.selMasks = the EMIT bitmap
 __global__ void __launch_bounds__(256)
 k_ft_write(const uint8_t *data, GpBufs b, const uint64_t *emitBytes, const uint64_t *outBases,
@@ -270,75 +344,9 @@ k_ft_write(const uint8_t *data, GpBufs b, const uint64_t *emitBytes, const uint6
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t waves = uint64_t(gridDim.x) * 4;
   for (uint64_t ch = uint64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); ch < b.nChunks; ch += waves) {
-    uint64_t dstAt = outBases[ch];
+    const uint64_t dstAt = outBases[ch];
     if (dstAt >= cap || emitBytes[ch] == 0) continue;  // (uniform)
     const TextHits h(b, ch, lane);                     // (h.s: the EMIT bits)
-    // is the delimiter below the lane's bits emitted (none: no), and the one above them
-    const uint32_t own = h.g.m.count();
-    const GpBits e = h.s.m;
-    uint32_t below = 0, above = 0xffffffffu;
-    if (own) {
-      uint32_t top = 0, bottom = 0;  // is the lane's highest / lowest delimiter emitted
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint64_t x = h.g.m.w[k], y = h.g.m.w[3 - k];
-        if (x) top = (e.w[k] >> (63 - __clzll(static_cast<long long>(x)))) & 1u;
-        if (y) bottom = (e.w[3 - k] >> (__ffsll(static_cast<long long>(y)) - 1)) & 1u;
-      }
-      below = (lane << 1 | top) + 1;
-      above = lane << 1 | bottom;
-    }
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t v = __shfl_up(below, o), u = __shfl_down(above, o);
-      if (lane >= uint32_t(o) && v > below) below = v;
-      if (lane + uint32_t(o) < 64 && u < above) above = u;
-    }
-    below = __shfl_up(below, 1);
-    above = __shfl_down(above, 1);
-    bool on = lane != 0 && below != 0 && ((below - 1) & 1u);
-    bool onAbove = lane != 63 && above != 0xffffffffu && (above & 1u);
-    // the delimiters that begin a run of emitted lines, and those that end one
-    GpBits begins{{0, 0, 0, 0}}, ends{{0, 0, 0, 0}};
-    ftEachUp(h.g.m, [&](auto word, uint64_t bit) {
-      constexpr int k = decltype(word)::value;
-      const bool is = (e.w[k] & bit) != 0;
-      if (is && !on) begins.w[k] |= bit;
-      on = is;
-    });
-    ftEachDown(h.g.m, [&](auto word, uint64_t bit) {
-      constexpr int k = decltype(word)::value;
-      const bool is = (e.w[k] & bit) != 0;
-      if (is && !onAbove) ends.w[k] |= bit;
-      onAbove = is;
-    });
-    GpChunk first, last;
-    first.m = begins;
-    last.m = ends;
-    first.scan(lane);
-    last.scan(lane);  // (last.total == first.total: the runs)
-    for (uint32_t k0 = 0; k0 < first.total && dstAt < cap; k0 += 64) {
-      const uint32_t k = k0 + lane;
-      const bool have = k < first.total;
-      const uint32_t pick = have ? k : first.total - 1;
-      const uint32_t endPos = last.select(pick);
-      uint64_t beg, fin;
-      uint32_t index;  // (not needed here)
-      h.line(first.select(pick), beg, fin, index);  // the run's first line
-      const uint64_t mine = have ? h.base + endPos + 1 - beg : 0;
-      uint64_t incl = mine;
-      for (int sh = 1; sh < 64; sh <<= 1) {
-        const uint64_t v = __shfl_up(incl, sh);
-        if (lane >= uint32_t(sh)) incl += v;
-      }
-      const uint64_t dst = dstAt + (incl - mine);
-      dstAt += __shfl(incl, 63);
-      // the runs, one after the other, by the whole wave
-      uint64_t todo = __ballot(have);
-      while (todo) {
-        const int j = __ffsll(static_cast<long long>(todo)) - 1;
-        todo &= todo - 1;
-        rtCopyWave(out, __shfl(dst, j), data + __shfl(beg, j), __shfl(mine, j), cap, lane);
-      }
-    }
+    ftWriteRuns(data, h, h.s.m, dstAt, out, cap, lane);
   }
 }

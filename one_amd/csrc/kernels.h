@@ -287,6 +287,24 @@ hipError_t launchExtractText(const DevDfa &dfa, const uint8_t *data, uint64_t le
                              int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                              const char **kernelName);
 
+// a raw text's lines grouped by result (k_route_text.h): every line of launchSplitLines' rule goes to
+// bucket r (its launchTallyText LINES value, (uint32_t)r < nBins) or nBins; the output is bucket
+// 0's lines, then bucket 1's, ..., each in text order with its delimiter - lines of value 0 left
+// out under dropUnmatched.  binLines[nBins + 1] = lines per bucket (dropped ones included),
+// binOffsets[nBins + 2] = where each bucket's section begins and the total, *outLen = the total,
+// *nRouted = lines emitted, the first min(*outLen, outCap) bytes in out and nothing behind them
+// (out, nLines, nRouted and binLines may be null).  nBins <= 255.  phases: 1 = index, class, size
+// and scan, 2 = write out from what phase 1 left in scratch, 3 = both.  scratch:
+// routeTextScratchBytes(len, nBins, dropUnmatched) bytes of device memory, 16-byte aligned.
+// *kernelName = "k_route_text".
+uint64_t routeTextScratchBytes(uint64_t len, uint64_t nBins, int dropUnmatched);
+hipError_t launchRouteText(const DevDfa &dfa, int style, int doLeader, int dropUnmatched,
+                           const uint8_t *data, uint64_t len, uint8_t delim, uint64_t nBins,
+                           uint64_t *nLines, uint64_t *nRouted, uint64_t *binLines,
+                           uint64_t *binOffsets, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                           int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                           const char **kernelName);
+
 // bench.py's read-bandwidth calibration: one streaming pass over `bytes` (16-byte aligned).
 hipError_t launchDiagRead(const void *data, uint64_t bytes, uint32_t *sink, int numCUs,
                           hipStream_t stream);

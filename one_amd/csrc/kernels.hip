@@ -57,6 +57,9 @@
 //   k_extract_text.h  k_xt_*: grep -o's output as a text - k_collect_text.h's chain per line, a sizing
 //                     pass, a scan, and a write pass whose lanes assemble their pieces in a 16-byte
 //                     register window
+//   k_route_text.h    k_ro_*: a raw text's lines grouped by result - k_grep.h's walk leaves each line's
+//                     bucket in bit-planes, a sizing pass per (bucket, chunk), ONE scan, and
+//                     k_filter_text.h's run copy once per bucket present in a chunk
 //   k_diag.h         bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
@@ -69,11 +72,11 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled eight times in parallel (Makefile: -DREDGPU_TU=1/2/.../8): the templates are
+// This file is compiled nine times in parallel (Makefile: -DREDGPU_TU=1/2/.../9): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
 // 3 = everything else and the dispatch, 4 = k_grep and k_filter_text (which runs k_grep's select), 5 = k_collect_text, 6 = k_replace_text,
-// 7 = k_tally_text, 8 = k_extract_text.
+// 7 = k_tally_text, 8 = k_extract_text, 9 = k_route_text.
 // REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
@@ -86,6 +89,7 @@
 #define REDGPU_TU_REPLACE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 6)
 #define REDGPU_TU_TALLY_TEXT (REDGPU_TU == 0 || REDGPU_TU == 7)
 #define REDGPU_TU_EXTRACT_TEXT (REDGPU_TU == 0 || REDGPU_TU == 8)
+#define REDGPU_TU_ROUTE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 9)
 
 // return CALL(KIND) for the table kind of the DevDfa `d` in scope: a launcher's instantiation per kind
 #define REDGPU_KIND_SWITCH(CALL)                                                          \
@@ -131,6 +135,7 @@ namespace {
 #include "k_replace_text.h"
 #include "k_filter_text.h"
 #include "k_extract_text.h"
+#include "k_route_text.h"
 
 } // namespace
 
@@ -1353,6 +1358,107 @@ hipError_t launchExtractText(const DevDfa &d, const uint8_t *data, uint64_t len,
   return hipGetLastError();
 }
 #endif  // REDGPU_TU_EXTRACT_TEXT
+
+#if REDGPU_TU_ROUTE_TEXT
+// a raw text's lines grouped by result (k_route_text.h): the line index (launchTextIndex), then the
+// k_ro_* passes around k_misc.h's scan.  A line's code is its bucket, except under nBins == 0 with
+// dropUnmatched, where it is "the line matches" (k_route_text.h: zeroCode).  scratch:
+// routeTextScratchBytes(len, nBins, dropUnmatched) bytes, 16-byte aligned: 1 + P bitmaps (len / 8
+// each), 20 bytes per chunk, 20 per (code, chunk), 8 per 1,024 of those and 72, rounded up to 16.
+struct RouteScratch {
+  uint64_t *bases, *open;  // [nChunks] each
+  uint64_t *sizes;         // [nCodes * nChunks]
+  uint64_t *outBases;      // [nCodes * nChunks + 1]
+  uint64_t *partials;      // [nPart]
+  uint64_t *misc;          // [8]: lines, the scan's two spare words, 5 spare
+  uint32_t *counts;        // [nChunks]
+  uint32_t *lines;         // [nCodes * nChunks]
+  uint16_t *masks, *planes;  // the delimiter bitmap, the nPlanes planes of the lines' codes
+  uint32_t nCodes, nPlanes;
+  int zeroCode;
+  uint64_t nCells, nPart, bytes;
+  RouteScratch(void *scratch, uint64_t nChunks, uint64_t nBins, int dropUnmatched) {
+    zeroCode = nBins == 0 && dropUnmatched;
+    nCodes = zeroCode ? 2u : uint32_t(nBins) + 1;
+    nPlanes = 0;
+    while ((nCodes - 1) >> nPlanes) ++nPlanes;
+    nCells = uint64_t(nCodes) * nChunks;
+    nPart = (nCells + 1023) / 1024;
+    Carve c{static_cast<uint8_t *>(scratch)};
+    bases = c.take<uint64_t>(nChunks);
+    open = c.take<uint64_t>(nChunks);
+    sizes = c.take<uint64_t>(nCells);
+    outBases = c.take<uint64_t>(nCells + 1);
+    partials = c.take<uint64_t>(nPart);
+    misc = c.take<uint64_t>(8);
+    counts = c.take<uint32_t>(nChunks);
+    lines = c.take<uint32_t>(nCells);
+    c.align(16);
+    masks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    planes = c.take<uint16_t>(nPlanes * nChunks * (kSplitChunk / 16));
+    bytes = c.at;
+  }
+};
+
+uint64_t routeTextScratchBytes(uint64_t len, uint64_t nBins, int dropUnmatched) {
+  return RouteScratch(nullptr, splitChunks(len), nBins, dropUnmatched).bytes;
+}
+
+hipError_t launchRouteText(const DevDfa &d, int style, int doLeader, int dropUnmatched,
+                           const uint8_t *data, uint64_t len, uint8_t delim, uint64_t nBins,
+                           uint64_t *nLines, uint64_t *nRouted, uint64_t *binLines,
+                           uint64_t *binOffsets, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                           int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                           const char **kernelName) {
+  *kernelName = "k_route_text";
+  const uint64_t nChunks = splitChunks(len);
+  const RouteScratch m(scratch, nChunks, nBins, dropUnmatched);
+  // (TextHits loads a verb's bitmap beside the delimiters': there is none here, it gets the latter)
+  const GpBufs b{m.masks, m.masks, m.bases, m.open, nullptr, nullptr, nChunks};
+  const RoBufs r{m.planes, nChunks * (kSplitChunk / 16), m.counts, m.sizes, m.lines, m.outBases,
+                 uint32_t(nBins), m.nCodes, m.nPlanes, m.zeroCode, dropUnmatched ? 1 : 0};
+  // the grid of the passes without a table: a wave per chunk, four to a workgroup
+  uint64_t small = (nChunks + 3) / 4;
+  if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
+  if (phases & 1) {
+    // (no bitmap for k_gp_last to zero: the planes are zeroed here, all of them at once)
+    hipError_t e = launchTextIndex(data, len, delim, m.misc, m.counts, m.bases, m.masks, m.open,
+                                   nullptr, m.misc + 1, cfg.numCUs, stream);
+    if (e != hipSuccess) return e;
+    if (nChunks) {
+      if (m.nPlanes) {
+        e = hipMemsetAsync(m.planes, 0, size_t(m.nPlanes) * nChunks * (kSplitChunk / 8), stream);
+        if (e != hipSuccess) return e;
+      }
+      const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
+      int verb = kSearch;
+      normalizeVerbStyle(d, cfg, lead != 0, verb, style);
+#define RO_ARGS d, data, b, style, lead, r, cfg, stream
+#define RO_CALL(K) \
+  (verb == kSearch ? launchRouteClassK<K, kSearch>(RO_ARGS) : launchRouteClassK<K, kMatch>(RO_ARGS))
+      e = [&]() -> hipError_t { REDGPU_KIND_SWITCH(RO_CALL) }();
+#undef RO_CALL
+#undef RO_ARGS
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_ro_size, dim3(uint32_t(small)), dim3(256), 0, stream, b, r);
+      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.sizes,
+                         m.nCells, m.partials);
+      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
+      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.sizes,
+                         m.nCells, m.partials, m.outBases);
+    }
+    hipLaunchKernelGGL(k_ro_finish, dim3(m.nCodes), dim3(256), 0, stream, r, nChunks, m.misc, nLines,
+                       nRouted, binLines, binOffsets, outLen);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if ((phases & 2) && out && outCap && nChunks) {
+    hipLaunchKernelGGL(k_ro_write, dim3(uint32_t(small)), dim3(256), 0, stream, data, b, r, out,
+                       outCap);
+  }
+  return hipGetLastError();
+}
+#endif  // REDGPU_TU_ROUTE_TEXT
 
 #if REDGPU_TU_GENERIC
 hipError_t launchBatches(const DevDfa &d, const Batch *bs, uint32_t nb, int verb, int style,

@@ -1183,10 +1183,11 @@ int redgpu_match_text(const redgpu_dfa *dfa, int style, int do_leader, const uin
 // The arguments of both forms of a raw-text verb (grep_text, collect_text, tally_text,
 // replace_text): what can be refused without a device first, in this order - no handle, no `need`
 // buffer (needError), no data, the verb's own refusal (ownError, null = none), a bad style (style
-// null: the verb takes none), a text or (tally_text) a bin count too large, a handle that is not one.
+// null: the verb takes none), a text or (tally_text, route_text) a bin count too large, a handle
+// that is not one.
 static int checkRawText(const redgpu_dfa *dfa, const void *need, const char *needError,
                         const uint8_t *data, uint64_t len, const char *ownError, const int *style,
-                        uint64_t nBins = 0) {
+                        uint64_t nBins = 0, uint64_t maxBins = 1ull << 31) {
   if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
   if (!need) return fail(REDGPU_EAPI, needError);
   if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
@@ -1194,7 +1195,7 @@ static int checkRawText(const redgpu_dfa *dfa, const void *need, const char *nee
   if (style)
     if (int rc = checkStyle(*style)) return rc;
   if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
-  if (nBins > (1ull << 31)) return fail(REDGPU_ELIMIT, "n_bins too large");
+  if (nBins > maxBins) return fail(REDGPU_ELIMIT, "n_bins too large");
   return checkHandle(dfa);
 }
 
@@ -1489,6 +1490,78 @@ int redgpu_filter_text(const redgpu_dfa *dfa, int style, int do_leader, int inve
   call.run([&] {
     return filterTextDev(dfa, style, do_leader, invert, before, after, max_count, dData, len, delim,
                          dSizes, dSizes + 1, dSizes + 2, dSizes + 3, dOut, put, 2, call.stream());
+  });
+  call.download(out, dOut, put, "out");
+  return call.wait();
+}
+
+// the arguments of both route_text forms
+static int checkRouteText(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
+                          uint64_t nBins, const uint64_t *binOffsets, const uint64_t *outLen) {
+  if (dfa && !binOffsets) return fail(REDGPU_EAPI, "null bin_offsets buffer");
+  return checkRawText(dfa, outLen, "null out_len buffer", data, len, nullptr, &style, nBins, 255);
+}
+
+// raw text -> its lines grouped by result, as a text (k_route_text.h): everything on `stream`,
+// nothing read back; phases as launchRouteText's
+static int routeTextDev(const redgpu_dfa *dfa, int style, int doLeader, int dropUnmatched,
+                        const uint8_t *data, uint64_t len, uint8_t delim, uint64_t nBins,
+                        uint64_t *nLines, uint64_t *nRouted, uint64_t *binLines,
+                        uint64_t *binOffsets, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                        int phases, hipStream_t s) {
+  if (int rc = checkRouteText(dfa, style, data, len, nBins, binOffsets, outLen)) return rc;
+  return rawTextDev(dfa, s, routeTextScratchBytes(len, nBins, dropUnmatched ? 1 : 0),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchRouteText(dfa->im->dev, style, doLeader ? 1 : 0, dropUnmatched ? 1 : 0, data, len,
+                           delim, nBins, nLines, nRouted, binLines, binOffsets, outLen, out, outCap,
+                           phases, scratch, cfg, s, name);
+  });
+}
+
+int redgpu_route_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int drop_unmatched,
+                          const uint8_t *data, uint64_t len, uint8_t delim, uint64_t n_bins,
+                          uint64_t *n_lines, uint64_t *n_routed, uint64_t *bin_lines,
+                          uint64_t *bin_offsets, uint64_t *out_len, uint8_t *out, uint64_t out_cap,
+                          void *stream) {
+  return routeTextDev(dfa, style, do_leader, drop_unmatched, data, len, delim, n_bins, n_lines,
+                      n_routed, bin_lines, bin_offsets, out_len, out, out_cap, 3,
+                      static_cast<hipStream_t>(stream));
+}
+
+// host-buffer form, as redgpu_filter_text: the text goes up once; phase 1 leaves the sizes, the
+// bitmaps and the (bucket, chunk) output bases in the stream's scratch, the device output is sized
+// from *out_len, phase 2 copies the runs, and min(*out_len, out_cap) bytes come back
+int redgpu_route_text(const redgpu_dfa *dfa, int style, int do_leader, int drop_unmatched,
+                      const uint8_t *data, uint64_t len, uint8_t delim, uint64_t n_bins,
+                      uint64_t *n_lines, uint64_t *n_routed, uint64_t *bin_lines,
+                      uint64_t *bin_offsets, uint64_t *out_len, uint8_t *out, uint64_t out_cap) {
+  if (int rc = checkRouteText(dfa, style, data, len, n_bins, bin_offsets, out_len)) return rc;
+  // the three counts, bin_lines[n_bins + 1], bin_offsets[n_bins + 2]
+  const uint64_t nSizes = 3 + (n_bins + 1) + (n_bins + 2);
+  uint64_t sizes[3 + 256 + 257] = {};
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, nSizes, "sizes");
+  uint64_t *dLines = dSizes + 3, *dOffsets = dLines + n_bins + 1;
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return routeTextDev(dfa, style, do_leader, drop_unmatched, dData, len, delim, n_bins, dSizes,
+                        dSizes + 1, dLines, dOffsets, dSizes + 2, nullptr, 0, 1, call.stream());
+  });
+  call.download(sizes, dSizes, nSizes, "sizes");
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = sizes[0];
+  if (n_routed) *n_routed = sizes[1];
+  *out_len = sizes[2];
+  for (uint64_t i = 0; i <= n_bins && bin_lines; ++i) bin_lines[i] = sizes[3 + i];
+  for (uint64_t i = 0; i <= n_bins + 1; ++i) bin_offsets[i] = sizes[3 + n_bins + 1 + i];
+  const uint64_t put = sizes[2] < out_cap ? sizes[2] : out_cap;
+  if (!out || !put) return REDGPU_OK;
+  // (the streams are drained: growing the slot waits for nothing)
+  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
+  call.run([&] {
+    return routeTextDev(dfa, style, do_leader, drop_unmatched, dData, len, delim, n_bins, dSizes,
+                        dSizes + 1, dLines, dOffsets, dSizes + 2, dOut, put, 2, call.stream());
   });
   call.download(out, dOut, put, "out");
   return call.wait();

@@ -1230,6 +1230,71 @@ def filter_text(exe, data, style=styInstant, do_leader=True, *, invert=False, be
     return int(nl.value), int(ns.value), int(ne.value), buf[:int(olen.value)].tobytes()
 
 
+def route_text(exe, data, n_bins=None, style=styInstant, do_leader=True, *, drop_unmatched=False,
+               delim=b"\n", out=None, out_cap=None):
+    """redgpu_route_text[_dev]: awk '{ print > file[class] }' - every delimiter-terminated line of
+    a raw text buffer routed to the bucket of the result search<style,doLeader> reports for it
+    (tally_text's matches=False value and slot rule: bucket r for a result r < n_bins, bucket
+    n_bins for everything else), and the text put back together bucket by bucket: bucket 0's
+    lines, then bucket 1's, ..., inside a bucket in text order, each with its delimiter - a stable
+    partition.  n_bins=None means min(exe.info["max_result"] + 1, 255); more than 255 is refused.
+    drop_unmatched=True leaves the lines that do not match out of the output (they are still
+    counted in bin_lines[0]).  bin_lines has n_bins + 1 entries (tally_text's bins), bin_offsets
+    n_bins + 2: where each bucket's section begins in the output, and its length.  The tail
+    behind the last delimiter is not a line and is never emitted.
+    Host input -> (n_lines, n_routed, bin_lines, bin_offsets, bytes): the two as uint64 arrays.
+    A CUDA uint8 tensor needs out (a contiguous uint8 CUDA tensor to write into) or out_cap (one
+    of that size is made; 0 gives the sizes only) -> (n_lines, n_routed, bin_lines, bin_offsets,
+    out_len, out): the counts as int64 tensors, asynchronously on the current stream and without
+    any read-back; out_len may exceed the room, bytes of out from min(out_len, room) on are
+    untouched.  Every section of the output is a raw text that every text verb accepts."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    style, lead, drop = int(style), 1 if do_leader else 0, 1 if drop_unmatched else 0
+    n_bins = min(int(exe.info["max_result"]) + 1, 255) if n_bins is None else int(n_bins)
+    if n_bins < 0:
+        raise RedExceptApi("n_bins must not be negative")
+    if n_bins > 255:
+        raise RedExceptLimit("n_bins must not exceed 255")
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = data.device
+        if out is None and out_cap is None:
+            raise RedExceptApi("device route_text needs out or out_cap (room for the output)")
+        if out is None:
+            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
+        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
+              not out.is_contiguous() or out.device != dev):
+            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
+        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        # n_lines, n_routed, out_len, bin_lines[n_bins + 1], bin_offsets[n_bins + 2]
+        cnt = torch.empty(3 + 2 * n_bins + 3, dtype=torch.int64, device=dev)
+        lines_at, offs_at = 3, 3 + n_bins + 1
+        _check(l.redgpu_route_text_dev(
+            exe._h, style, lead, drop, data.data_ptr() if data.numel() else None, data.numel(), d,
+            n_bins, cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 8 * lines_at,
+            cnt.data_ptr() + 8 * offs_at, cnt.data_ptr() + 16, out.data_ptr() if room else None,
+            room, torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], cnt[lines_at:offs_at], cnt[offs_at:], cnt[2:3], out
+    if out is not None or out_cap is not None:
+        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    a = _host_u8(data)
+    nl, nr, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    bin_lines = np.zeros(n_bins + 1, dtype=np.uint64)
+    bin_offsets = np.zeros(n_bins + 2, dtype=np.uint64)
+    # the output is no longer than the text
+    cap = int(a.size)
+    buf = np.zeros(max(cap, 1), dtype=np.uint8)
+    _check(l.redgpu_route_text(
+        exe._h, style, lead, drop, a.ctypes.data if a.size else None, a.size, d, n_bins,
+        C.byref(nl), C.byref(nr), bin_lines.ctypes.data, bin_offsets.ctypes.data, C.byref(olen),
+        buf.ctypes.data, cap))
+    return (int(nl.value), int(nr.value), bin_lines, bin_offsets,
+            buf[:int(olen.value)].tobytes())
+
+
 def extract_text(exe, data, *, max_per_line=1 << 62, delim=b"\n", out=None, out_cap=None):
     """redgpu_extract_text[_dev]: grep -o as a text - every match of every delimiter-terminated
     line of a raw text buffer (Red::collect's chain, collect_text's records), as bytes: the span
