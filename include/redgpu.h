@@ -830,6 +830,71 @@ int redgpu_route_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int d
                           uint64_t *bin_offsets, uint64_t *out_len, uint8_t *out, uint64_t out_cap,
                           void *stream);
 
+/* grep -o | sort | uniq -c, by the matched BYTES: raw text in, one record per distinct byte string
+ * out - which IPs, URIs or error strings occur, and how often.  redgpu_tally_text counts by result
+ * number; this verb counts by content, and only the distinct strings leave the device.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter (the tail) are not a line and contribute nothing.
+ *  - what == REDGPU_UNIQ_MATCHES: the items are the pieces redgpu_extract_text would emit under
+ *    max_per_line - the same chain, the same span (from where the matching attempt began to the
+ *    record's end), without the delimiter extract_text puts behind each.  style and do_leader are
+ *    not looked at.
+ *  - what == REDGPU_UNIQ_LINES: the items are the lines redgpu_grep_text selects with
+ *    search<style,do_leader> and no invert (its verb and style normalisation), each without its
+ *    delimiter.  An empty selected line is an item of length 0.  max_per_line is not looked at.
+ *  - Record j is distinct string j, in the order of FIRST APPEARANCE in the text: first[j] = the
+ *    absolute offset of the string's earliest occurrence (strictly ascending in j), length[j] =
+ *    its length in bytes - the string is data[first[j], first[j] + length[j]) - and count[j] =
+ *    all its occurrences, exact.  Exactly min(*n_distinct, cap) records are written and nothing
+ *    behind them; each array may be NULL on its own; cap == 0 gives the counts only.
+ *  - *n_lines = delimiters found, *n_items = every item (dropped ones included), *n_distinct =
+ *    the records that exist, whatever cap is, *n_dropped = the items in no record.  Each may be
+ *    NULL.  Over ALL records, sum(count) + *n_dropped == *n_items.
+ *  - table_slots is the size of the hash table the strings are kept in: a power of two,
+ *    64 <= table_slots <= 2^32, 16 bytes each from the thread's scratch pool.  At most table_slots
+ *    distinct strings get a record; twice the expected number keeps the probes short.
+ *  - An item is dropped in exactly two cases.  It is 2^24 bytes or longer: decided before it is
+ *    hashed, deterministic.  Or the table is full and does not hold its string.
+ *  - *n_dropped == 0: every output is bit-identical from run to run.  When the table overflows,
+ *    every record written is still exact for its string (count = all its occurrences, first = its
+ *    earliest: an item is either counted in its string's record or dropped, never lost in
+ *    between), *n_distinct == table_slots, and WHICH strings got a record depends on scheduling.
+ *    The remedy is the caller's: call again with a larger table.
+ *  - REDGPU_EAPI for a NULL handle, a NULL data with len > 0, a `what` other than the two below, a
+ *    table_slots that is no power of two in [64, 2^32] (the argument checks run before the
+ *    handle's device is looked at) and for a REDGPU_DEVICE_NONE handle; REDGPU_EEXEC for a style
+ *    that does not exist (LINES only); REDGPU_ELIMIT for a text redgpu_split_lines refuses or one
+ *    of 2^40 - 1 bytes or more (an offset + 1 shares a 64-bit word with the 24-bit length).  In
+ *    every error case nothing the caller passed is written.
+ *  - An empty text, or one without a delimiter: all counts are 0 and no record is written (the
+ *    _dev form does this on the stream).
+ *  - A single line of megabytes is walked by one lane, and a table near full is probed slot by
+ *    slot: correct, and slow.
+ * redgpu_last_kernel() says "k_uniq_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - nothing is read
+ * back.  Scratch: 16 bytes per slot, two bitmaps (len / 4), 164 bytes per 16 KiB chunk, from the
+ * thread's pool.
+ * redgpu_uniq_text: host buffers - one upload of the text, a device table, the four counts and
+ * min(*n_distinct, cap) records back.
+ * redgpu_uniq_lds_slots: how many (string, count) slots a workgroup keeps in on-chip memory (LDS)
+ * in front of the table for this handle, for texts below 4 GiB: a power of two up to 1024, what
+ * the DFA's table leaves of a workgroup's share of the LDS; 0 when that is fewer than 64 - every
+ * item then goes to the table in device memory directly.  The results do not depend on it.  A
+ * pure host function, valid for REDGPU_DEVICE_NONE handles too; 0 for a NULL handle. */
+#define REDGPU_UNIQ_LINES   0  /* an item per selected line: search<style,do_leader> on the line */
+#define REDGPU_UNIQ_MATCHES 1  /* an item per match: redgpu_extract_text's pieces */
+int redgpu_uniq_text(const redgpu_dfa *dfa, int what, int style, int do_leader,
+                     const uint8_t *data, uint64_t len, uint8_t delim, uint64_t max_per_line,
+                     uint64_t table_slots, uint64_t cap, uint64_t *n_lines, uint64_t *n_items,
+                     uint64_t *n_distinct, uint64_t *n_dropped, uint64_t *first, uint64_t *length,
+                     uint64_t *count);
+int redgpu_uniq_text_dev(const redgpu_dfa *dfa, int what, int style, int do_leader,
+                         const uint8_t *data, uint64_t len, uint8_t delim, uint64_t max_per_line,
+                         uint64_t table_slots, uint64_t cap, uint64_t *n_lines, uint64_t *n_items,
+                         uint64_t *n_distinct, uint64_t *n_dropped, uint64_t *first,
+                         uint64_t *length, uint64_t *count, void *stream);
+uint32_t redgpu_uniq_lds_slots(const redgpu_dfa *dfa);
+
 /* Measurement aid, no counterpart in the reference: one streaming read of `bytes` of device
  * memory (16-byte aligned) on the handle's device, asynchronous on `stream` - the read-bandwidth
  * calibration bench.py reports beside the roofline.  `sink` is a device uint32 the kernel may

@@ -287,6 +287,40 @@ inline std::vector<uint64_t> tallyText(const Executable &exec, std::string_view 
   return bins;
 }
 
+// grep -o | sort | uniq -c keyed by the matched bytes (redgpu_uniq_text): one UniqRecord per
+// distinct byte string among the text's items, in the order of first appearance - the string is
+// text.substr(first, length), count all its occurrences.  matches = true: the items are
+// extractText's pieces (at most maxPerLine of a line); false: the lines search<style,doLeader>
+// selects, without their delimiters.  The hash table holds the power of two at or above
+// 2 * maxDistinct (at least 64) strings; *dropped = the items in no record (2^24 bytes or longer,
+// or the table was full: call again with a larger maxDistinct), *items = all items, *lines =
+// delimiters found.
+struct UniqRecord {
+  uint64_t first, length, count;
+};
+inline std::vector<UniqRecord> uniqText(const Executable &exec, std::string_view text,
+                                        bool matches = true, size_t maxDistinct = size_t(1) << 20,
+                                        Style style = styInstant, bool doLeader = true,
+                                        size_t maxPerLine = SIZE_MAX, char delim = '\n',
+                                        size_t *items = nullptr, size_t *dropped = nullptr,
+                                        size_t *lines = nullptr) {
+  uint64_t slots = 64;
+  while (slots < 2 * uint64_t(maxDistinct) && slots < (1ull << 32)) slots *= 2;
+  const uint64_t rows = slots < text.size() ? slots : text.size();
+  std::vector<uint64_t> first(rows), length(rows), count(rows);
+  uint64_t nLines = 0, nItems = 0, nDistinct = 0, nDropped = 0;
+  throwOnError(redgpu_uniq_text(exec.handle(), matches ? REDGPU_UNIQ_MATCHES : REDGPU_UNIQ_LINES,
+                                style, doLeader, reinterpret_cast<const Byte *>(text.data()),
+                                text.size(), Byte(delim), maxPerLine, slots, rows, &nLines, &nItems,
+                                &nDistinct, &nDropped, first.data(), length.data(), count.data()));
+  std::vector<UniqRecord> out(size_t(nDistinct < rows ? nDistinct : rows));
+  for (size_t j = 0; j < out.size(); ++j) out[j] = UniqRecord{first[j], length[j], count[j]};
+  if (items) *items = size_t(nItems);
+  if (dropped) *dropped = size_t(nDropped);
+  if (lines) *lines = size_t(nLines);
+  return out;
+}
+
 // sed (replace<style,doLeader>, include/Matcher.h:186-191, inside tools/skim_red.cpp:36-46's line
 // loop): every line of a text blob rewritten and the text put back together in `out` - the lines,
 // their delimiters, and the tail behind the last delimiter unchanged.  max is per line (1 = sed

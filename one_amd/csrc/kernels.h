@@ -305,6 +305,25 @@ hipError_t launchRouteText(const DevDfa &dfa, int style, int doLeader, int dropU
                            int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                            const char **kernelName);
 
+// a raw text's distinct items counted by their bytes (k_uniq_text.h): an item is a piece
+// launchExtractText would emit under maxPerLine (what = REDGPU_UNIQ_MATCHES) or a line
+// launchGrepText selects without invert (REDGPU_UNIQ_LINES, its normalisation), without its
+// delimiter.  Record j = distinct string j in the order of first appearance: first[j] its earliest
+// offset, length[j], count[j] all its occurrences; the first min(*nDistinct, cap) records written
+// and nothing behind them (each array may be null).  *nItems = all items, *nDropped = those in no
+// record (2^24 bytes or longer, or the table full); tableSlots a power of two.  plain = 1: no LDS
+// front.  Every counter may be null.  scratch: uniqTextScratchBytes(len, tableSlots) bytes of
+// device memory, 16-byte aligned.  *kernelName = "k_uniq_text".
+// uniqLdsSlots: the slots of the LDS front for a DFA of this table (0 = the table leaves no room).
+uint64_t uniqTextScratchBytes(uint64_t len, uint64_t tableSlots);
+uint32_t uniqLdsSlots(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates);
+hipError_t launchUniqText(const DevDfa &dfa, int what, int style, int doLeader, const uint8_t *data,
+                          uint64_t len, uint8_t delim, uint64_t maxPerLine, uint64_t tableSlots,
+                          uint64_t cap, int plain, uint64_t *nLines, uint64_t *nItems,
+                          uint64_t *nDistinct, uint64_t *nDropped, uint64_t *first,
+                          uint64_t *length, uint64_t *count, void *scratch, const LaunchCfg &cfg,
+                          hipStream_t stream, const char **kernelName);
+
 // bench.py's read-bandwidth calibration: one streaming pass over `bytes` (16-byte aligned).
 hipError_t launchDiagRead(const void *data, uint64_t bytes, uint32_t *sink, int numCUs,
                           hipStream_t stream);

@@ -60,6 +60,9 @@
 //   k_route_text.h    k_ro_*: a raw text's lines grouped by result - k_grep.h's walk leaves each line's
 //                     bucket in bit-planes, a sizing pass per (bucket, chunk), ONE scan, and
 //                     k_filter_text.h's run copy once per bucket present in a chunk
+//   k_uniq_text.h     k_uq_*: a raw text's distinct matches (or selected lines) counted by their BYTES -
+//                     k_tally_text.h's walk, a hash table keyed by the text's own bytes behind an LDS
+//                     front, and an ordering pass over a first-occurrence bitmap
 //   k_diag.h         bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
@@ -72,11 +75,11 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled nine times in parallel (Makefile: -DREDGPU_TU=1/2/.../9): the templates are
+// This file is compiled ten times in parallel (Makefile: -DREDGPU_TU=1/2/.../10): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
 // 3 = everything else and the dispatch, 4 = k_grep and k_filter_text (which runs k_grep's select), 5 = k_collect_text, 6 = k_replace_text,
-// 7 = k_tally_text, 8 = k_extract_text, 9 = k_route_text.
+// 7 = k_tally_text, 8 = k_extract_text, 9 = k_route_text, 10 = k_uniq_text.
 // REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
@@ -90,6 +93,7 @@
 #define REDGPU_TU_TALLY_TEXT (REDGPU_TU == 0 || REDGPU_TU == 7)
 #define REDGPU_TU_EXTRACT_TEXT (REDGPU_TU == 0 || REDGPU_TU == 8)
 #define REDGPU_TU_ROUTE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 9)
+#define REDGPU_TU_UNIQ_TEXT (REDGPU_TU == 0 || REDGPU_TU == 10)
 
 // return CALL(KIND) for the table kind of the DevDfa `d` in scope: a launcher's instantiation per kind
 #define REDGPU_KIND_SWITCH(CALL)                                                          \
@@ -136,6 +140,7 @@ namespace {
 #include "k_filter_text.h"
 #include "k_extract_text.h"
 #include "k_route_text.h"
+#include "k_uniq_text.h"
 
 } // namespace
 
@@ -1459,6 +1464,117 @@ hipError_t launchRouteText(const DevDfa &d, int style, int doLeader, int dropUnm
   return hipGetLastError();
 }
 #endif  // REDGPU_TU_ROUTE_TEXT
+
+#if REDGPU_TU_UNIQ_TEXT
+// a raw text's distinct items counted by their bytes (k_uniq_text.h): the line index
+// (launchTextIndex, which also zeroes the FIRST bitmap), k_uq_zero, the one pass of k_uniq_text, and
+// the ordering pass around k_misc.h's scan.  scratch: uniqTextScratchBytes(len, tableSlots) bytes,
+// 16-byte aligned: 16 bytes per slot, the two bitmaps (len / 4), 164 bytes per chunk, 8 per 1,024
+// chunks and 72, rounded up to 16.
+struct UniqScratch {
+  uint64_t *table;          // [2 * slots]
+  uint64_t *bases, *open;   // [nChunks] each
+  uint64_t *pops;           // [nChunks]
+  uint64_t *popBases;       // [nChunks + 1]
+  uint64_t *partials;       // [nPart]
+  uint64_t *misc;           // [8]: lines, the scan's two spare words, items, dropped, distinct, 2 spare
+  uint32_t *counts;         // [nChunks]
+  uint16_t *lanePre;        // [64 * nChunks]
+  uint16_t *masks, *firsts; // the delimiter bitmap, the FIRST bitmap
+  uint64_t nPart, bytes;
+  UniqScratch(void *scratch, uint64_t nChunks, uint64_t slots) : nPart((nChunks + 1023) / 1024) {
+    Carve c{static_cast<uint8_t *>(scratch)};
+    table = c.take<uint64_t>(2 * slots);
+    bases = c.take<uint64_t>(nChunks);
+    open = c.take<uint64_t>(nChunks);
+    pops = c.take<uint64_t>(nChunks);
+    popBases = c.take<uint64_t>(nChunks + 1);
+    partials = c.take<uint64_t>(nPart);
+    misc = c.take<uint64_t>(8);
+    counts = c.take<uint32_t>(nChunks);
+    lanePre = c.take<uint16_t>(64 * nChunks);
+    c.align(16);
+    masks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    firsts = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    bytes = c.at;
+  }
+};
+
+uint64_t uniqTextScratchBytes(uint64_t len, uint64_t tableSlots) {
+  return UniqScratch(nullptr, splitChunks(len), tableSlots).bytes;
+}
+
+uint32_t uniqLdsSlots(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates) {
+  DevDfa d{};
+  d.tableKind = tableKind;
+  d.tableBytes = tableBytes;
+  d.nStates = nStates;
+#define UQ_SLOTS(K) uniqLdsSlotsK<K>(d)
+  REDGPU_KIND_SWITCH(UQ_SLOTS)
+#undef UQ_SLOTS
+}
+
+hipError_t launchUniqText(const DevDfa &d, int what, int style, int doLeader, const uint8_t *data,
+                          uint64_t len, uint8_t delim, uint64_t maxPerLine, uint64_t tableSlots,
+                          uint64_t cap, int plain, uint64_t *nLines, uint64_t *nItems,
+                          uint64_t *nDistinct, uint64_t *nDropped, uint64_t *first,
+                          uint64_t *length, uint64_t *count, void *scratch, const LaunchCfg &cfg,
+                          hipStream_t stream, const char **kernelName) {
+  *kernelName = "k_uniq_text";
+  const uint64_t nChunks = splitChunks(len);
+  const UniqScratch m(scratch, nChunks, tableSlots);
+  hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                 m.firsts, m.misc, cfg.numCUs, stream);
+  if (e != hipSuccess) return e;
+  if (!nDistinct) nDistinct = m.misc + 5;
+  UqOut o{reinterpret_cast<unsigned long long *>(m.table), tableSlots,
+          reinterpret_cast<unsigned long long *>(nItems ? nItems : m.misc + 3),
+          reinterpret_cast<unsigned long long *>(nDropped ? nDropped : m.misc + 4), 0};
+  // the grid of the passes over the table
+  const uint64_t most = uint64_t(cfg.numCUs) * 8;
+  // (an empty text needs no table: the counters alone are zeroed)
+  const uint64_t words = nChunks ? 2 * tableSlots : 0;
+  uint64_t zb = (words + 255) / 256;
+  if (zb > most) zb = most;
+  hipLaunchKernelGGL(k_uq_zero, dim3(uint32_t(zb ? zb : 1)), dim3(256), 0, stream, o.table, words,
+                     o.nItems, o.nDropped, nDistinct);
+  e = hipGetLastError();
+  if (e != hipSuccess || nChunks == 0) return e;
+  const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
+  int verb = kSearch;
+  if (what == REDGPU_UNIQ_LINES) normalizeVerbStyle(d, cfg, lead != 0, verb, style);
+  // L: the front's slots.  32-bit counts hold a text below 4 GiB whatever it is (k_tally_text.h:
+  // tallyAdd); a longer text, and the plain form, go to the global table alone
+  if (!plain && len < (1ull << 32)) o.ldsSlots = uniqLdsSlots(d.tableKind, d.tableBytes, d.nStates);
+  const GpBufs b{m.masks, nullptr, m.bases, m.open, nullptr, nullptr, nChunks};
+#define UQ_ARGS d, data, len, b, style, lead, maxPerLine, o, cfg, stream
+#define UQ_CALL(K)                                                              \
+  (what == REDGPU_UNIQ_MATCHES ? launchUniqK<K, kUqMatches>(UQ_ARGS)            \
+   : verb == kSearch           ? launchUniqK<K, kUqLines>(UQ_ARGS)              \
+                               : launchUniqK<K, kUqLinesMatch>(UQ_ARGS))
+  e = [&]() -> hipError_t { REDGPU_KIND_SWITCH(UQ_CALL) }();
+#undef UQ_CALL
+#undef UQ_ARGS
+  if (e != hipSuccess) return e;
+  uint64_t tb = (tableSlots + 255) / 256;
+  if (tb > most) tb = most;
+  uint64_t small = (nChunks + 3) / 4;
+  if (small > most) small = most;
+  hipLaunchKernelGGL(k_uq_mark, dim3(uint32_t(tb)), dim3(256), 0, stream, o.table, tableSlots,
+                     reinterpret_cast<uint32_t *>(m.firsts));
+  hipLaunchKernelGGL(k_uq_pop, dim3(uint32_t(small)), dim3(256), 0, stream, m.firsts, nChunks,
+                     m.pops, m.lanePre);
+  hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.pops,
+                     nChunks, m.partials);
+  hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
+  hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.pops, nChunks,
+                     m.partials, m.popBases);
+  hipLaunchKernelGGL(k_uq_emit, dim3(uint32_t(tb)), dim3(256), 0, stream, o.table, tableSlots,
+                     reinterpret_cast<const uint32_t *>(m.firsts), m.popBases, m.lanePre, nChunks,
+                     cap, first, length, count, nDistinct);
+  return hipGetLastError();
+}
+#endif  // REDGPU_TU_UNIQ_TEXT
 
 #if REDGPU_TU_GENERIC
 hipError_t launchBatches(const DevDfa &d, const Batch *bs, uint32_t nb, int verb, int style,

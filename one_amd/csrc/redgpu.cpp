@@ -1183,18 +1183,20 @@ int redgpu_match_text(const redgpu_dfa *dfa, int style, int do_leader, const uin
 // The arguments of both forms of a raw-text verb (grep_text, collect_text, tally_text,
 // replace_text): what can be refused without a device first, in this order - no handle, no `need`
 // buffer (needError), no data, the verb's own refusal (ownError, null = none), a bad style (style
-// null: the verb takes none), a text or (tally_text, route_text) a bin count too large, a handle
-// that is not one.
+// null: the verb takes none), a text (uniq_text: of maxLen bytes or more) or (tally_text,
+// route_text) a bin count too large, a handle that is not one.
 static int checkRawText(const redgpu_dfa *dfa, const void *need, const char *needError,
                         const uint8_t *data, uint64_t len, const char *ownError, const int *style,
-                        uint64_t nBins = 0, uint64_t maxBins = 1ull << 31) {
+                        uint64_t nBins = 0, uint64_t maxBins = 1ull << 31,
+                        uint64_t maxLen = ~0ull) {
   if (!dfa) return fail(REDGPU_EAPI, "null dfa handle");
   if (!need) return fail(REDGPU_EAPI, needError);
   if (len && !data) return fail(REDGPU_EAPI, "null data buffer");
   if (ownError) return fail(REDGPU_EAPI, ownError);
   if (style)
     if (int rc = checkStyle(*style)) return rc;
-  if (splitChunks(len) >= (1ull << 31)) return fail(REDGPU_ELIMIT, "buffer too large");
+  if (splitChunks(len) >= (1ull << 31) || len >= maxLen)
+    return fail(REDGPU_ELIMIT, "buffer too large");
   if (nBins > maxBins) return fail(REDGPU_ELIMIT, "n_bins too large");
   return checkHandle(dfa);
 }
@@ -1565,6 +1567,88 @@ int redgpu_route_text(const redgpu_dfa *dfa, int style, int do_leader, int drop_
   });
   call.download(out, dOut, put, "out");
   return call.wait();
+}
+
+// the arguments of both uniq_text forms (every output may be NULL: the handle stands in for the
+// buffer checkRawText asks for)
+static int checkUniqText(const redgpu_dfa *dfa, int what, int style, const uint8_t *data,
+                         uint64_t len, uint64_t tableSlots) {
+  const bool lines = what == REDGPU_UNIQ_LINES;
+  const char *own = nullptr;
+  if (!lines && what != REDGPU_UNIQ_MATCHES)
+    own = "what is neither REDGPU_UNIQ_LINES nor REDGPU_UNIQ_MATCHES";
+  else if (tableSlots < 64 || tableSlots > (1ull << 32) || (tableSlots & (tableSlots - 1)))
+    own = "table_slots is no power of two in [64, 2^32]";
+  // (a key packs offset + 1 above a 24-bit length: texts of 2^40 - 1 bytes and more are refused)
+  return checkRawText(dfa, dfa, "", data, len, own, lines ? &style : nullptr, 0, 1ull << 31,
+                      (1ull << 40) - 1);
+}
+
+// raw text -> its distinct matches (or selected lines) counted by their bytes (k_uniq_text.h):
+// everything on `stream`, nothing read back
+int redgpu_uniq_text_dev(const redgpu_dfa *dfa, int what, int style, int do_leader,
+                         const uint8_t *data, uint64_t len, uint8_t delim, uint64_t max_per_line,
+                         uint64_t table_slots, uint64_t cap, uint64_t *n_lines, uint64_t *n_items,
+                         uint64_t *n_distinct, uint64_t *n_dropped, uint64_t *first,
+                         uint64_t *length, uint64_t *count, void *stream) {
+  if (int rc = checkUniqText(dfa, what, style, data, len, table_slots)) return rc;
+  // REDGPU_UNIQ_PLAIN=1: no LDS front, every item goes to the global table (measurements, DESIGN
+  // 4.3m)
+  const char *env = getenv("REDGPU_UNIQ_PLAIN");
+  const int plain = env && env[0] == '1';
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return rawTextDev(dfa, s, uniqTextScratchBytes(len, table_slots),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchUniqText(dfa->im->dev, what, style, do_leader ? 1 : 0, data, len, delim,
+                          max_per_line, table_slots, cap, plain, n_lines, n_items, n_distinct,
+                          n_dropped, first, length, count, scratch, cfg, s, name);
+  });
+}
+
+// host-buffer form: one upload of the text, the table in the stream's scratch, device records of
+// the call's own, then the four counts and the records that exist back
+int redgpu_uniq_text(const redgpu_dfa *dfa, int what, int style, int do_leader,
+                     const uint8_t *data, uint64_t len, uint8_t delim, uint64_t max_per_line,
+                     uint64_t table_slots, uint64_t cap, uint64_t *n_lines, uint64_t *n_items,
+                     uint64_t *n_distinct, uint64_t *n_dropped, uint64_t *first, uint64_t *length,
+                     uint64_t *count) {
+  if (int rc = checkUniqText(dfa, what, style, data, len, table_slots)) return rc;
+  // no more records than slots, nor than bytes: an item has a byte of its own (a line its
+  // delimiter, a match at least the byte it ends behind)
+  if (cap > table_slots) cap = table_slots;
+  if (cap > len) cap = len;
+  if (!first && !length && !count) cap = 0;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dN = call.buf<uint64_t>(kSlAux0, 4, "counts");
+  uint64_t *dFirst = first && cap ? call.buf<uint64_t>(kSlAux1, cap, "first") : nullptr;
+  uint64_t *dLength = length && cap ? call.buf<uint64_t>(kSlAux2, cap, "length") : nullptr;
+  uint64_t *dCount = count && cap ? call.buf<uint64_t>(kSlAux3, cap, "count") : nullptr;
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return redgpu_uniq_text_dev(dfa, what, style, do_leader, dData, len, delim, max_per_line,
+                                table_slots, cap, dN, dN + 1, dN + 2, dN + 3, dFirst, dLength,
+                                dCount, call.stream());
+  });
+  uint64_t counts[4] = {0, 0, 0, 0};
+  call.download(counts, dN, 4, "counts");
+  if (int rc = call.wait()) return rc;
+  const uint64_t put = counts[2] < cap ? counts[2] : cap;
+  if (dFirst && put) call.download(first, dFirst, put, "first");
+  if (dLength && put) call.download(length, dLength, put, "length");
+  if (dCount && put) call.download(count, dCount, put, "count");
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = counts[0];
+  if (n_items) *n_items = counts[1];
+  if (n_distinct) *n_distinct = counts[2];
+  if (n_dropped) *n_dropped = counts[3];
+  return REDGPU_OK;
+}
+
+uint32_t redgpu_uniq_lds_slots(const redgpu_dfa *dfa) {
+  if (!dfa) return 0;
+  const DfaImage &img = dfa->im->img;
+  return uniqLdsSlots(img.tableKind, (img.primaryBytes + 15u) & ~15u, img.nStates);
 }
 
 // raw text -> every match of every line as bytes, one per output line (k_extract_text.h):

@@ -1056,6 +1056,7 @@ def collect_text(exe, data, *, delim=b"\n", cap=None, want_positions=True):
 
 
 TALLY_LINES, TALLY_MATCHES = 0, 1
+UNIQ_LINES, UNIQ_MATCHES = 0, 1
 
 
 def tally_text(exe, data, n_bins=None, *, matches=True, style=styInstant, do_leader=True,
@@ -1113,6 +1114,66 @@ def tally_text(exe, data, n_bins=None, *, matches=True, style=styInstant, do_lea
                                0 if into is None else 1, C.byref(nl), C.byref(ni),
                                bins.ctypes.data))
     return int(nl.value), int(ni.value), bins
+
+
+def uniq_text(exe, data, *, matches=True, style=styInstant, do_leader=True, max_per_line=1 << 62,
+              delim=b"\n", max_distinct=1 << 20, cap=None):
+    """redgpu_uniq_text[_dev]: grep -o | sort | uniq -c keyed by the matched BYTES - the distinct
+    byte strings among a raw text's items and how often each occurs, in the order of first
+    appearance.  matches=True: the items are extract_text's pieces (at most max_per_line of a
+    line); matches=False: the lines grep_text selects with search<style,doLeader>, without their
+    delimiters.  Record j is (first[j], length[j], count[j]): the string is
+    data[first[j] : first[j] + length[j]], first[j] its earliest occurrence (strictly ascending),
+    count[j] all its occurrences, exact.  The hash table has table_slots = the power of two at or
+    above 2 * max_distinct (at least 64) slots of 16 bytes; n_dropped counts the items in no
+    record - those of 2^24 bytes or more, and those that found the table full (then call again
+    with a larger max_distinct).  While n_dropped is 0 every output is bit-identical from run to
+    run.
+    Host input -> (n_lines, n_items, n_dropped, first, length, count): uint64 arrays of
+    min(n_distinct, cap) rows, cap=None meaning all of them.
+    A CUDA uint8 tensor -> (n_lines, n_items, n_dropped, n_distinct, first, length, count): the
+    counts as 1-element int64 tensors, the arrays int64 of cap rows (cap=None: max_distinct) of
+    which the first min(n_distinct, cap) are written, asynchronously on the current stream and
+    without any read-back."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    what = UNIQ_MATCHES if matches else UNIQ_LINES
+    style, lead, per = int(style), 1 if do_leader else 0, int(max_per_line)
+    max_distinct = int(max_distinct)
+    if max_distinct < 1 or max_distinct > 1 << 31:
+        raise RedExceptApi("max_distinct must be in [1, 2^31]")
+    if per < 0 or (cap is not None and int(cap) < 0):
+        raise RedExceptApi("max_per_line and cap must not be negative")
+    slots = 64
+    while slots < 2 * max_distinct:
+        slots *= 2
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = data.device
+        rows = max_distinct if cap is None else int(cap)
+        cnt = torch.empty(4, dtype=torch.int64, device=dev)
+        rec = torch.empty((3, rows), dtype=torch.int64, device=dev)
+        _check(l.redgpu_uniq_text_dev(
+            exe._h, what, style, lead, data.data_ptr() if data.numel() else None, data.numel(), d,
+            per, slots, rows, cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 16,
+            cnt.data_ptr() + 24, rec[0].data_ptr() if rows else None,
+            rec[1].data_ptr() if rows else None, rec[2].data_ptr() if rows else None,
+            torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], cnt[3:4], cnt[2:3], rec[0], rec[1], rec[2]
+    a = _host_u8(data)
+    # no more records than slots, nor than bytes
+    rows = min(slots, int(a.size)) if cap is None else min(int(cap), slots, int(a.size))
+    rec = np.zeros((3, max(rows, 1)), dtype=np.uint64)
+    nl, ni, nd, nx = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(l.redgpu_uniq_text(
+        exe._h, what, style, lead, a.ctypes.data if a.size else None, a.size, d, per, slots, rows,
+        C.byref(nl), C.byref(ni), C.byref(nd), C.byref(nx), rec[0].ctypes.data, rec[1].ctypes.data,
+        rec[2].ctypes.data))
+    n = min(int(nd.value), rows)
+    return (int(nl.value), int(ni.value), int(nx.value), rec[0, :n].copy(), rec[1, :n].copy(),
+            rec[2, :n].copy())
 
 
 def replace_text(exe, data, repl, style=styLast, do_leader=True, max_count=1 << 62, *,
