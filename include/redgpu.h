@@ -774,6 +774,67 @@ int redgpu_extract_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t
                             uint64_t max_per_line, uint64_t *n_lines, uint64_t *n_matches,
                             uint64_t *out_len, uint8_t *out, uint64_t out_cap, void *stream);
 
+/* awk -F / cut: raw text in, the selected COLUMNS of every line out as a text - what a log pipeline
+ * does behind selecting and rewriting: cut -d, -f1,3, awk -F'[ \t]+' '{print $1, $4}'.  The DFA
+ * describes the SEPARATOR; a field is what lies between two separators.
+ *  - Lines are redgpu_split_lines' lines (lib/Util.cpp:109-130): [start, delimiter), the next one
+ *    begins behind the delimiter, bytes after the last delimiter are not a line and contribute
+ *    nothing (redgpu_extract_text's rule).
+ *  - The SEPARATORS of a line are exactly the pieces redgpu_extract_text would emit for it: the
+ *    spans replace<styLast,false> substitutes (include/Matcher.h:643-706), [a_j, e_j) along
+ *    Red::collect's chain (lib/Red.cpp:103-116), never empty, never holding the delimiter.  No
+ *    style or leader argument, as in redgpu_collect_text / redgpu_extract_text.  Only the first S
+ *    separators of a line count: S = max_fields - 1 when max_fields > 0, all of them when it is 0.
+ *  - With m counted separators a line has m + 1 FIELDS: field 1 is line[0, a_1), field j is
+ *    line[e_{j-1}, a_j), the last is line[e_m, end).  Fields may be empty: a leading separator gives
+ *    an empty field 1 - awk -F',' and re.split, not awk's default whitespace mode.  An empty line
+ *    has one empty field; max_fields = 1 makes every line one field (and no line has a counted
+ *    separator then).
+ *  - select is a mask: bit k - 1 stands for field k (1..63), bit 63 for field 64 AND every later
+ *    one, so cut's 5- is bits 4..63.  select == 0 is REDGPU_EAPI.
+ *  - An emitted line becomes exactly one output line: its selected fields that exist, in ascending
+ *    order, joined by sep, then delim - cut's rule: a selected field the line does not have adds
+ *    nothing (no padding), and a line with none of them becomes an empty output line.  sep is 0..8
+ *    bytes, passed BY VALUE: the sep_len low bytes of sep, little-endian (byte i of the joiner is
+ *    (sep >> 8 i) & 255).  sep_len > 8 is REDGPU_EAPI.  Fields are not reordered.
+ *  - only_delimited (cut -s): lines without a counted separator are not emitted.  Otherwise every
+ *    line is emitted, and output line k corresponds to input line k.
+ *  - *n_lines = delimiters found, *n_emitted = output lines, *n_fields = fields written,
+ *    *out_len = the length of the whole output, whatever out_cap is.  out_len is required; the
+ *    others may be NULL, each on its own.
+ *  - out == NULL or out_cap == 0 gives the sizes only, and no line is walked a second time.
+ *    Otherwise exactly the first min(*out_len, out_cap) bytes of the output are written - the cut
+ *    may fall anywhere - and bytes of out from there on are NOT written (redgpu_filter_text's
+ *    rule).  out must not overlap data.
+ *  - The output is a raw text every text verb accepts: fields -> uniq_text of lines is
+ *    cut -f3 | sort | uniq -c on the device.
+ *  - A line is not walked behind the last field anyone asked for: with k the highest selected
+ *    field (bit 63 clear), the search for separators ends behind the line's k-th.
+ *  - REDGPU_EAPI for a NULL handle, a NULL out_len, a NULL data with len > 0, select == 0,
+ *    sep_len > 8 (the argument checks run before the handle's device is looked at) and for a
+ *    REDGPU_DEVICE_NONE handle; REDGPU_ELIMIT for a text redgpu_split_lines refuses.  In every
+ *    error case nothing of the caller's is written.
+ *  - An empty text, or one without a delimiter: all four counts are 0 and nothing is written to
+ *    out (the _dev form writes the counts on the stream).
+ *  - A single line of megabytes is walked by one lane: correct, and slow.
+ * redgpu_last_kernel() says "k_fields_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - nothing is read
+ * back, and no per-line or per-field array is needed from the caller or in scratch (scratch is
+ * what redgpu_replace_text_dev takes plus 8 bytes per 16 KiB chunk: len / 4 + 52 bytes per chunk +
+ * 8 bytes per 1,024 chunks + 72, rounded up to 16, from the thread's pool).
+ * redgpu_fields_text: host buffers, as redgpu_extract_text - one upload of the text, a sizes pass,
+ * a device output sized from *out_len, and min(*out_len, out_cap) bytes downloaded. */
+int redgpu_fields_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                       uint64_t select, uint64_t max_fields, int only_delimited,
+                       uint64_t sep, uint32_t sep_len,
+                       uint64_t *n_lines, uint64_t *n_emitted, uint64_t *n_fields,
+                       uint64_t *out_len, uint8_t *out, uint64_t out_cap);
+int redgpu_fields_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                           uint64_t select, uint64_t max_fields, int only_delimited,
+                           uint64_t sep, uint32_t sep_len,
+                           uint64_t *n_lines, uint64_t *n_emitted, uint64_t *n_fields,
+                           uint64_t *out_len, uint8_t *out, uint64_t out_cap, void *stream);
+
 /* awk '{ print > file[class] }': raw text in, ALL its lines out as a text, grouped by the result
  * search reports for each - the fourth thing a log pipeline does with a many-pattern DFA, beside
  * selecting (grep_text, filter_text), rewriting (replace_text, extract_text) and counting

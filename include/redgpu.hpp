@@ -419,6 +419,35 @@ inline size_t extractText(const Executable &exec, std::string_view text, std::st
   return size_t(found);
 }
 
+// awk -F / cut as a text (redgpu_fields_text): the DFA describes the separator; the fields of every
+// line of a text blob that `select` names (bit k - 1 = field k, bit 63 = field 64 and every later
+// one) put in `out`, joined by sep (at most 8 bytes), one output line per emitted line.  maxFields
+// > 0: a line has at most that many fields, the last is the rest of the line.  onlyDelimited
+// (cut -s): lines without a separator are left out.  Returns the lines emitted; *lines =
+// delimiters found, *fields = fields written.  `out` is sized from a first call that only sizes.
+inline size_t fieldsText(const Executable &exec, std::string_view text, uint64_t select,
+                         std::string &out, std::string_view sep = " ", size_t maxFields = 0,
+                         bool onlyDelimited = false, char delim = '\n', size_t *lines = nullptr,
+                         size_t *fields = nullptr) {
+  if (sep.size() > 8) throw RedExceptApi("fieldsText: sep is longer than 8 bytes");
+  const Byte *p = reinterpret_cast<const Byte *>(text.data());
+  uint64_t sepWord = 0;
+  for (size_t i = 0; i < sep.size(); ++i) sepWord |= uint64_t(Byte(sep[i])) << (8 * i);
+  const uint32_t sepLen = uint32_t(sep.size());
+  uint64_t nLines = 0, emitted = 0, nFields = 0, outLen = 0;
+  throwOnError(redgpu_fields_text(exec.handle(), p, text.size(), Byte(delim), select, maxFields,
+                                  onlyDelimited, sepWord, sepLen, &nLines, &emitted, &nFields,
+                                  &outLen, nullptr, 0));
+  out.resize(size_t(outLen));
+  if (outLen)
+    throwOnError(redgpu_fields_text(exec.handle(), p, text.size(), Byte(delim), select, maxFields,
+                                    onlyDelimited, sepWord, sepLen, &nLines, &emitted, &nFields,
+                                    &outLen, reinterpret_cast<Byte *>(out.data()), outLen));
+  if (lines) *lines = size_t(nLines);
+  if (fields) *fields = size_t(nFields);
+  return size_t(emitted);
+}
+
 // ---- several GPUs of one node: one image per device, contiguous shards, results in the caller's
 // arrays - the device form of tools/thr_red.cpp:84-91 (N workers over one shared Red).  devices
 // may name a device more than once (the shards then share it). ----------------------------------

@@ -207,6 +207,12 @@ def lib() -> C.CDLL:
         l.redgpu_extract_text.argtypes = [vp, vp, u64, C.c_uint8, u64, vp, vp, vp, vp, u64]
         l.redgpu_extract_text_dev.restype = C.c_int
         l.redgpu_extract_text_dev.argtypes = [vp, vp, u64, C.c_uint8, u64, vp, vp, vp, vp, u64, vp]
+        l.redgpu_fields_text.restype = C.c_int
+        l.redgpu_fields_text.argtypes = [vp, vp, u64, C.c_uint8, u64, u64, C.c_int, u64,
+                                         C.c_uint32, vp, vp, vp, vp, vp, u64]
+        l.redgpu_fields_text_dev.restype = C.c_int
+        l.redgpu_fields_text_dev.argtypes = [vp, vp, u64, C.c_uint8, u64, u64, C.c_int, u64,
+                                             C.c_uint32, vp, vp, vp, vp, vp, u64, vp]
         l.redgpu_replace_text.restype = C.c_int
         l.redgpu_replace_text.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, u64, C.c_uint8, vp, u64,
                                           u64, vp, vp, vp, vp, u64]

@@ -287,6 +287,24 @@ hipError_t launchExtractText(const DevDfa &dfa, const uint8_t *data, uint64_t le
                              int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                              const char **kernelName);
 
+// awk -F's columns of a raw text (k_fields_text.h): the separators of a line of launchSplitLines'
+// rule are the first maxFields - 1 (maxFields = 0: all) pieces launchExtractText would emit for it,
+// its fields what lies between them; an emitted line holds its fields selected by `select` (bit
+// k - 1 = field k, bit 63 = field 64 and every later one; not 0) that exist, in order, joined by the
+// sepLen (0..8) low bytes of sep, then delim.  onlyDelimited: lines without a separator are not
+// emitted.  *nEmitted = output lines, *nFields = fields written, *outLen = the output's bytes, the
+// first min(*outLen, outCap) bytes in out and nothing behind them (out, nLines, nEmitted and
+// nFields may be null).  phases: 1 = index and size, 2 = write out from what phase 1 left in
+// scratch, 3 = both.  scratch: fieldsTextScratchBytes(len) bytes of device memory, 16-byte
+// aligned.  *kernelName = "k_fields_text".
+uint64_t fieldsTextScratchBytes(uint64_t len);
+hipError_t launchFieldsText(const DevDfa &dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                            uint64_t select, uint64_t maxFields, int onlyDelimited, uint64_t sep,
+                            uint32_t sepLen, uint64_t *nLines, uint64_t *nEmitted,
+                            uint64_t *nFields, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                            int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                            const char **kernelName);
+
 // a raw text's lines grouped by result (k_route_text.h): every line of launchSplitLines' rule goes to
 // bucket r (its launchTallyText LINES value, (uint32_t)r < nBins) or nBins; the output is bucket
 // 0's lines, then bucket 1's, ..., each in text order with its delimiter - lines of value 0 left

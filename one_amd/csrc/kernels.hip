@@ -63,6 +63,9 @@
 //   k_uniq_text.h     k_uq_*: a raw text's distinct matches (or selected lines) counted by their BYTES -
 //                     k_tally_text.h's walk, a hash table keyed by the text's own bytes behind an LDS
 //                     front, and an ordering pass over a first-occurrence bitmap
+//   k_fields_text.h   k_fd_*: awk -F's columns of a raw text - k_extract_text.h's chain per line with the
+//                     GAPS between the matches as the fields, left behind the last field asked for;
+//                     a sizing pass, a scan, and a write pass through k_extract_text.h's window
 //   k_diag.h         bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
@@ -75,11 +78,12 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled ten times in parallel (Makefile: -DREDGPU_TU=1/2/.../10): the templates are
+// This file is compiled eleven times in parallel (Makefile: -DREDGPU_TU=1/2/.../11): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
 // 3 = everything else and the dispatch, 4 = k_grep and k_filter_text (which runs k_grep's select), 5 = k_collect_text, 6 = k_replace_text,
-// 7 = k_tally_text, 8 = k_extract_text, 9 = k_route_text, 10 = k_uniq_text.
+// 7 = k_tally_text, 8 = k_extract_text, 9 = k_route_text, 10 = k_uniq_text,
+// 11 = k_fields_text.
 // REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
@@ -94,6 +98,7 @@
 #define REDGPU_TU_EXTRACT_TEXT (REDGPU_TU == 0 || REDGPU_TU == 8)
 #define REDGPU_TU_ROUTE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 9)
 #define REDGPU_TU_UNIQ_TEXT (REDGPU_TU == 0 || REDGPU_TU == 10)
+#define REDGPU_TU_FIELDS_TEXT (REDGPU_TU == 0 || REDGPU_TU == 11)
 
 // return CALL(KIND) for the table kind of the DevDfa `d` in scope: a launcher's instantiation per kind
 #define REDGPU_KIND_SWITCH(CALL)                                                          \
@@ -141,6 +146,7 @@ namespace {
 #include "k_extract_text.h"
 #include "k_route_text.h"
 #include "k_uniq_text.h"
+#include "k_fields_text.h"
 
 } // namespace
 
@@ -1363,6 +1369,91 @@ hipError_t launchExtractText(const DevDfa &d, const uint8_t *data, uint64_t len,
   return hipGetLastError();
 }
 #endif  // REDGPU_TU_EXTRACT_TEXT
+
+#if REDGPU_TU_FIELDS_TEXT
+// awk -F's columns of a raw text (k_fields_text.h): the line index (launchTextIndex), then the
+// k_fd_* passes around k_misc.h's 64-bit scan.  scratch: fieldsTextScratchBytes(len) bytes, 16-byte
+// aligned: what sed takes (ReplaceScratch's layout) plus one u64 per chunk - the two bitmaps, and
+// 52 bytes per chunk, 8 per 1,024 chunks and 72, rounded up to 16.
+struct FieldsScratch {
+  uint64_t *bases, *open, *outBytes, *lineCounts, *fieldCounts;  // [nChunks] each
+  uint64_t *outBases;                                            // [nChunks + 1]
+  uint64_t *partials;                                            // [nPart]
+  uint64_t *misc;               // [8]: lines, the scan's spare word, emitted, fields, 4 spare
+  uint32_t *counts;             // [nChunks]
+  uint16_t *masks, *hitMasks;   // the delimiter bitmap, the hit bitmap (only_delimited)
+  uint64_t nPart, bytes;
+  FieldsScratch(void *scratch, uint64_t nChunks) : nPart((nChunks + 1023) / 1024) {
+    Carve c{static_cast<uint8_t *>(scratch)};
+    bases = c.take<uint64_t>(nChunks);
+    open = c.take<uint64_t>(nChunks);
+    outBytes = c.take<uint64_t>(nChunks);
+    lineCounts = c.take<uint64_t>(nChunks);
+    fieldCounts = c.take<uint64_t>(nChunks);
+    outBases = c.take<uint64_t>(nChunks + 1);
+    partials = c.take<uint64_t>(nPart);
+    misc = c.take<uint64_t>(8);
+    counts = c.take<uint32_t>(nChunks);
+    c.align(16);
+    masks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    hitMasks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    bytes = c.at;
+  }
+};
+
+uint64_t fieldsTextScratchBytes(uint64_t len) {
+  return FieldsScratch(nullptr, splitChunks(len)).bytes;
+}
+
+hipError_t launchFieldsText(const DevDfa &d, const uint8_t *data, uint64_t len, uint8_t delim,
+                            uint64_t select, uint64_t maxFields, int onlyDelimited, uint64_t sep,
+                            uint32_t sepLen, uint64_t *nLines, uint64_t *nEmitted,
+                            uint64_t *nFields, uint64_t *outLen, uint8_t *out, uint64_t outCap,
+                            int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                            const char **kernelName) {
+  *kernelName = "k_fields_text";
+  const uint64_t nChunks = splitChunks(len);
+  const FieldsScratch m(scratch, nChunks);
+  // without only_delimited every line is emitted: the write pass is driven from the delimiter
+  // bitmap itself, and there is no hit bitmap to zero or to fill
+  uint16_t *emitted = onlyDelimited ? m.hitMasks : m.masks;
+  const GpBufs b{m.masks, emitted, m.bases, m.open, nullptr, nullptr, nChunks};
+  const FdBufs x{m.outBytes, m.lineCounts, m.fieldCounts, m.outBases};
+  // the chain is left behind separator min(S, hi): S = maxFields - 1 (0 = unbounded), hi = the
+  // highest selected field (bit 63 = unbounded)
+  const uint64_t most = maxFields ? maxFields - 1 : ~0ull;
+  uint64_t hi = ~0ull;
+  if (!(select >> 63)) {
+    hi = 0;
+    while (select >> hi) ++hi;
+  }
+  const FdArgs a{select, most < hi ? most : hi, sep, sepLen, uint32_t(delim), onlyDelimited ? 1 : 0};
+#define FD_CALL(K) launchFieldsTextK<K>(d, data, len, b, x, a, size, out, outCap, cfg, stream)
+  auto pass = [&](bool size) { REDGPU_KIND_SWITCH(FD_CALL) };
+#undef FD_CALL
+  if (phases & 1) {
+    hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                   onlyDelimited ? m.hitMasks : nullptr, m.misc, cfg.numCUs, stream);
+    if (e != hipSuccess) return e;
+    if (nChunks) {
+      e = pass(true);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream,
+                         m.outBytes, nChunks, m.partials);
+      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
+      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.outBytes,
+                         nChunks, m.partials, m.outBases);
+    }
+    hipLaunchKernelGGL(k_fd_totals, dim3(1), dim3(1024), 0, stream, m.lineCounts, m.fieldCounts,
+                       nChunks, nChunks ? m.outBases + nChunks : nullptr, outLen,
+                       nEmitted ? nEmitted : m.misc + 2, nFields ? nFields : m.misc + 3);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if ((phases & 2) && out && outCap && nChunks) return pass(false);
+  return hipGetLastError();
+}
+#endif  // REDGPU_TU_FIELDS_TEXT
 
 #if REDGPU_TU_ROUTE_TEXT
 // a raw text's lines grouped by result (k_route_text.h): the line index (launchTextIndex), then the

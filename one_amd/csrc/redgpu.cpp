@@ -1711,6 +1711,76 @@ int redgpu_extract_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len
   return call.wait();
 }
 
+// the arguments of both fields_text forms
+static int checkFieldsText(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
+                           uint64_t select, uint32_t sepLen, const uint64_t *outLen) {
+  const char *own = nullptr;
+  if (select == 0) own = "select is 0: no field is selected";
+  else if (sepLen > 8) own = "sep_len is above 8";
+  return checkRawText(dfa, outLen, "null out_len buffer", data, len, own, nullptr);
+}
+
+// raw text -> the selected fields of every line, joined by sep, one line per output line
+// (k_fields_text.h): everything on `stream`, nothing read back; phases as launchFieldsText's
+static int fieldsTextDev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                         uint64_t select, uint64_t maxFields, int onlyDelimited, uint64_t sep,
+                         uint32_t sepLen, uint64_t *nLines, uint64_t *nEmitted, uint64_t *nFields,
+                         uint64_t *outLen, uint8_t *out, uint64_t outCap, int phases,
+                         hipStream_t s) {
+  if (int rc = checkFieldsText(dfa, data, len, select, sepLen, outLen)) return rc;
+  return rawTextDev(dfa, s, fieldsTextScratchBytes(len),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchFieldsText(dfa->im->dev, data, len, delim, select, maxFields, onlyDelimited, sep,
+                            sepLen, nLines, nEmitted, nFields, outLen, out, outCap, phases,
+                            scratch, cfg, s, name);
+  });
+}
+
+int redgpu_fields_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                           uint64_t select, uint64_t max_fields, int only_delimited, uint64_t sep,
+                           uint32_t sep_len, uint64_t *n_lines, uint64_t *n_emitted,
+                           uint64_t *n_fields, uint64_t *out_len, uint8_t *out, uint64_t out_cap,
+                           void *stream) {
+  return fieldsTextDev(dfa, data, len, delim, select, max_fields, only_delimited, sep, sep_len,
+                       n_lines, n_emitted, n_fields, out_len, out, out_cap, 3,
+                       static_cast<hipStream_t>(stream));
+}
+
+// host-buffer form, as redgpu_extract_text: the text goes up once; phase 1 leaves the sizes, the
+// bitmaps and the chunks' output bases in the stream's scratch, the device output is sized from
+// *out_len, phase 2 assembles the lines, and min(*out_len, out_cap) bytes come back
+int redgpu_fields_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
+                       uint64_t select, uint64_t max_fields, int only_delimited, uint64_t sep,
+                       uint32_t sep_len, uint64_t *n_lines, uint64_t *n_emitted,
+                       uint64_t *n_fields, uint64_t *out_len, uint8_t *out, uint64_t out_cap) {
+  if (int rc = checkFieldsText(dfa, data, len, select, sep_len, out_len)) return rc;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 4, "sizes");
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return fieldsTextDev(dfa, dData, len, delim, select, max_fields, only_delimited, sep, sep_len,
+                         dSizes, dSizes + 1, dSizes + 2, dSizes + 3, nullptr, 0, 1, call.stream());
+  });
+  uint64_t sizes[4] = {0, 0, 0, 0};
+  call.download(sizes, dSizes, 4, "sizes");
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = sizes[0];
+  if (n_emitted) *n_emitted = sizes[1];
+  if (n_fields) *n_fields = sizes[2];
+  *out_len = sizes[3];
+  const uint64_t put = sizes[3] < out_cap ? sizes[3] : out_cap;
+  if (!out || !put) return REDGPU_OK;
+  // (the streams are drained: growing the slot waits for nothing)
+  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
+  call.run([&] {
+    return fieldsTextDev(dfa, dData, len, delim, select, max_fields, only_delimited, sep, sep_len,
+                         dSizes, dSizes + 1, dSizes + 2, dSizes + 3, dOut, put, 2, call.stream());
+  });
+  call.download(out, dOut, put, "out");
+  return call.wait();
+}
+
 int redgpu_split_lines(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                        uint64_t *offsets, uint64_t cap, uint64_t *n_lines) {
   if (int rc = checkHandle(dfa)) return rc;

@@ -1408,6 +1408,98 @@ def extract_text(exe, data, *, max_per_line=1 << 62, delim=b"\n", out=None, out_
     return int(nl.value), int(nm.value), buf[:int(olen.value)].tobytes()
 
 
+def fields_mask(fields) -> int:
+    """The 64-bit select mask of redgpu_fields_text: bit k - 1 stands for field k (1..63), bit 63
+    for field 64 and every later one.  fields is a cut-style list - "1,3,5-": single 1-based
+    indices and open ranges "k-", comma-separated - or an iterable of 1-based ints.  A closed range
+    ("2-7") or an index above 63 is refused: bit 63 cannot stand for field 64 alone."""
+    if isinstance(fields, (bytes, bytearray)):
+        fields = bytes(fields).decode("ascii", "replace")
+    mask = 0
+    if isinstance(fields, str):
+        for part in fields.split(","):
+            part = part.strip()
+            open_range = part.endswith("-")
+            digits = part[:-1] if open_range else part
+            if not digits.isdigit() or not digits.isascii():
+                raise RedExceptApi("fields: %r is neither an index k nor an open range k-" % part)
+            k = int(digits)
+            if k < 1 or (k > 64 if open_range else k > 63):
+                raise RedExceptApi("fields: %r is outside 1..63 (open ranges: 1..64)" % part)
+            mask |= ((1 << 64) - 1) & ~((1 << (k - 1)) - 1) if open_range else 1 << (k - 1)
+    else:
+        for k in fields:
+            if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= 63:
+                raise RedExceptApi("fields: %r is no index in 1..63" % (k,))
+            mask |= 1 << (int(k) - 1)
+    if mask == 0:
+        raise RedExceptApi("fields selects nothing")
+    return mask
+
+
+def fields_text(exe, data, fields, *, sep=b" ", max_fields=0, only_delimited=False, delim=b"\n",
+                out=None, out_cap=None):
+    """redgpu_fields_text[_dev]: awk -F / cut - exe's DFA describes the SEPARATOR; of every
+    delimiter-terminated line of a raw text buffer the selected fields that exist, in ascending
+    order, joined by sep (0..8 bytes), then the delimiter.  The separators of a line are the pieces
+    extract_text emits for it, only the first max_fields - 1 of them when max_fields > 0 (the last
+    field is then the rest of the line); fields may be empty (re.split's, not awk's whitespace
+    mode).  fields: fields_mask's argument.  only_delimited (cut -s): lines without a separator
+    are not emitted; otherwise output line k corresponds to input line k.
+    Host input -> (n_lines, n_emitted, n_fields, bytes).
+    A CUDA uint8 tensor needs out (a contiguous uint8 CUDA tensor to write into) or out_cap (one
+    of that size is made; 0 gives the sizes only) -> (n_lines, n_emitted, n_fields, out_len, out):
+    the counts as 1-element int64 tensors, asynchronously on the current stream and without any
+    read-back; out_len may exceed the room, bytes of out from min(out_len, room) on are
+    untouched.  The output is a raw text that every text verb accepts."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    select = fields_mask(fields)
+    sep = bytes(sep)
+    if len(sep) > 8:
+        raise RedExceptApi("sep is longer than 8 bytes")
+    sep_word = int.from_bytes(sep, "little")
+    max_fields = int(max_fields)
+    only = 1 if only_delimited else 0
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = data.device
+        if out is None and out_cap is None:
+            raise RedExceptApi("device fields_text needs out or out_cap (room for the output)")
+        if out is None:
+            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
+        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
+              not out.is_contiguous() or out.device != dev):
+            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
+        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        cnt = torch.empty(4, dtype=torch.int64, device=dev)
+        _check(l.redgpu_fields_text_dev(
+            exe._h, data.data_ptr() if data.numel() else None, data.numel(), d, select, max_fields,
+            only, sep_word, len(sep), cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 16,
+            cnt.data_ptr() + 24, out.data_ptr() if room else None, room,
+            torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], cnt[2:3], cnt[3:4], out
+    if out is not None or out_cap is not None:
+        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    a = _host_u8(data)
+    nl, ne, nf, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    # first guess: output about as long as the input (a long sep between short fields makes it
+    # longer); once more with the exact size otherwise
+    cap = int(a.size + 64)
+    for _ in range(2):
+        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+        _check(l.redgpu_fields_text(
+            exe._h, a.ctypes.data if a.size else None, a.size, d, select, max_fields, only,
+            sep_word, len(sep), C.byref(nl), C.byref(ne), C.byref(nf), C.byref(olen),
+            buf.ctypes.data, cap))
+        if int(olen.value) <= cap:
+            break
+        cap = int(olen.value)
+    return int(nl.value), int(ne.value), int(nf.value), buf[:int(olen.value)].tobytes()
+
+
 class StatefulMatcher:
     """Mirror of zezax::red::StatefulMatcher (include/Matcher.h:770-792): `advance(byte)` and
     `result()`; `advance_bytes` feeds a whole chunk in one kernel launch.  The executable must
