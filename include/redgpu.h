@@ -613,7 +613,9 @@ int redgpu_collect_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t
  * redgpu_tally_lds_bins: how many leading bins the kernel keeps in on-chip memory (LDS) for this
  * handle, for texts below 4 GiB: min(4096, what the table leaves of a workgroup's share of the
  * LDS), 0 when the table leaves no room; values from there on are counted in device memory
- * directly.  A pure host function, valid for REDGPU_DEVICE_NONE handles too; 0 for a NULL handle. */
+ * directly.  A text of 4 GiB or more runs WITHOUT the LDS bins - every value is counted in device
+ * memory directly: the same counts, at a lower rate where few values take most of the items.  A
+ * pure host function, valid for REDGPU_DEVICE_NONE handles too; 0 for a NULL handle. */
 #define REDGPU_TALLY_LINES   0  /* one item per line: search<style,do_leader> on the line */
 #define REDGPU_TALLY_MATCHES 1  /* one item per match: Red::collect on the line */
 int redgpu_tally_text(const redgpu_dfa *dfa, int what, int style, int do_leader,
@@ -941,7 +943,9 @@ int redgpu_route_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int d
  * in front of the table for this handle, for texts below 4 GiB: a power of two up to 1024, what
  * the DFA's table leaves of a workgroup's share of the LDS; 0 when that is fewer than 64 - every
  * item then goes to the table in device memory directly.  The results do not depend on it.  A
- * pure host function, valid for REDGPU_DEVICE_NONE handles too; 0 for a NULL handle. */
+ * text of 4 GiB or more runs WITHOUT the LDS front, whatever this returns: the same records, at
+ * a lower rate where few strings take most of the items.  A pure host function, valid for
+ * REDGPU_DEVICE_NONE handles too; 0 for a NULL handle. */
 #define REDGPU_UNIQ_LINES   0  /* an item per selected line: search<style,do_leader> on the line */
 #define REDGPU_UNIQ_MATCHES 1  /* an item per match: redgpu_extract_text's pieces */
 int redgpu_uniq_text(const redgpu_dfa *dfa, int what, int style, int do_leader,

@@ -58,11 +58,12 @@ def _lines_of(text, delim=0x0A):
     return np.cumsum([0] + [len(x) + 1 for x in lines]).astype(np.uint64)
 
 
-def _standard(piece: bytes, seed=1, n=4 * CHUNK + 5):
+def _standard(piece: bytes, seed=1, n=4 * CHUNK + 5, end_in_delim=False):
     """Four split chunks and a tail of alphabet text, delimiters at pseudo-random gaps of 1-199
     bytes; the piece in every line that crosses an odd multiple of 16384 and in every third other
-    line - but never in a line that crosses an even multiple."""
-    key = (piece, seed, n)
+    line - but never in a line that crosses an even multiple.  end_in_delim: the last byte is a
+    delimiter too, so the text is whole lines."""
+    key = (piece, seed, n, end_in_delim)
     if key in _texts:
         return _texts[key]
     a = W.alphabet_bytes(n, seed).copy()
@@ -75,6 +76,9 @@ def _standard(piece: bytes, seed=1, n=4 * CHUNK + 5):
             break
         a[pos] = 0x0A
         ends.append(pos)
+    if end_in_delim and ends[-1] != n - 1:
+        a[n - 1] = 0x0A
+        ends.append(n - 1)
     begin, other = 0, 0
     p = np.frombuffer(piece, dtype=np.uint8)
     for e in ends:
