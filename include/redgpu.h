@@ -960,6 +960,72 @@ int redgpu_uniq_text_dev(const redgpu_dfa *dfa, int what, int style, int do_lead
                          uint64_t *length, uint64_t *count, void *stream);
 uint32_t redgpu_uniq_lds_slots(const redgpu_dfa *dfa);
 
+/* awk '{ n[c]++; s[c] += $x; if ($x > m[c]) m[c] = $x }': raw text in, per result the count, sum,
+ * minimum and maximum of the decimal numbers found in the matches out - Red::collect
+ * (lib/Red.cpp:103-116) inside the line loop of tools/skim_red.cpp:36-46, over the lines
+ * lib/Util.cpp:109-130 cuts, with only four 64-bit words per slot leaving the device.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter are not a line and contribute nothing.
+ *  - The items are exactly the pieces redgpu_extract_text would emit under the same max_per_line:
+ *    piece j of a line is the span [a_j, e_j) along Red::collect's chain - from where the matching
+ *    attempt began to the match's end.  An item's result is the result of redgpu_collect_text's
+ *    record for that match.  There is no style or leader argument, as in redgpu_extract_text.
+ *    max_per_line: 1 << 62 = all pieces, 1 = the first match of each line, 0 = nothing.
+ *  - The number of an item.  A digit is a byte 0x30..0x39; the runs of a piece are its maximal
+ *    substrings of digits - only the piece's OWN bytes are looked at, so a digit next to the piece
+ *    in the text is not part of a run.  which == REDGPU_SUM_FIRST takes the first run,
+ *    which == REDGPU_SUM_LAST the last (for patterns such as " 200 [0-9]+", whose context carries
+ *    digits of its own).  The item's value is that run read as an unsigned decimal integer;
+ *    leading zeros are allowed and count against nothing.  The item is NUMERIC iff it has a run
+ *    and the value is below 2^64; otherwise (no digit, or 2^64 and more) it is counted in *n_items
+ *    and in no statistic.  Signs, fractions, hex and thousands separators are not interpreted:
+ *    "-5" is 5, "3.14" is 3 under FIRST and 14 under LAST.
+ *  - Slots follow redgpu_tally_text's rule: an item of result r goes to slot r when
+ *    (uint32_t)r < n_bins, else to slot n_bins.  n_bins == 0 is legal: one slot.
+ *  - stats holds 4 * (n_bins + 1) 64-bit words, row-major: stats[row * (n_bins + 1) + slot], the
+ *    rows REDGPU_SUM_COUNT, REDGPU_SUM_SUM, REDGPU_SUM_MIN, REDGPU_SUM_MAX over the slot's numeric
+ *    items.  A slot without numeric items has count 0, sum 0, min 2^64 - 1, max 0.  Sums are
+ *    modulo 2^64.
+ *  - accumulate == 0: all slots are overwritten.  accumulate != 0: the call's statistics are merged
+ *    into what the slots hold - counts and sums added (modulo 2^64), the smaller min and the larger
+ *    max kept: a stream of buffers reduced into one table.  The three scalars are always
+ *    overwritten.
+ *  - *n_lines = delimiters found; *n_items = pieces considered (redgpu_extract_text's n_matches
+ *    for the same max_per_line); *n_numeric = items in the statistics (what this call adds to the
+ *    count row).  Each of the three may be NULL, on its own; stats is required.
+ *  - Every operation is a commutative integer operation: all outputs are exact and bit-identical
+ *    from run to run, whatever the scheduling.  A text of 4 GiB and more is treated as any other.
+ *  - REDGPU_EAPI for a NULL handle, a NULL stats, a NULL data with len > 0, a `which` other than
+ *    the two above (the argument checks run before the handle's device is looked at) and for a
+ *    REDGPU_DEVICE_NONE handle; REDGPU_ELIMIT for a text redgpu_split_lines refuses or
+ *    n_bins > 2^31.  In every error case nothing the caller passed is written.
+ *  - An empty text, or one without a delimiter: the three scalars 0, the slots emptied (left alone
+ *    under accumulate); the _dev form does this on the stream.
+ * redgpu_last_kernel() says "k_sum_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - nothing is read
+ * back.  Scratch is what redgpu_tally_text_dev takes (ONE bitmap and 20 bytes per 16 KiB chunk):
+ * nothing proportional to n_bins.
+ * redgpu_sum_text: host buffers - one upload of the text, device stats of its own, the table and
+ * the three scalars back; under accumulate the merge happens on the host.
+ * redgpu_sum_lds_bins: how many leading slots the kernel keeps in on-chip memory (LDS) for this
+ * handle: min(512, what the table leaves of a workgroup's share of the LDS / 32), a multiple of 4;
+ * slots from there on are kept in device memory directly.  The results do not depend on it.  A
+ * pure host function, valid for REDGPU_DEVICE_NONE handles too; 0 for a NULL handle. */
+#define REDGPU_SUM_FIRST 0  /* an item's number is its first run of digits */
+#define REDGPU_SUM_LAST  1  /* ... its last run of digits */
+#define REDGPU_SUM_COUNT 0  /* the rows of stats */
+#define REDGPU_SUM_SUM   1
+#define REDGPU_SUM_MIN   2
+#define REDGPU_SUM_MAX   3
+int redgpu_sum_text(const redgpu_dfa *dfa, int which, const uint8_t *data, uint64_t len,
+                    uint8_t delim, uint64_t max_per_line, uint64_t n_bins, int accumulate,
+                    uint64_t *n_lines, uint64_t *n_items, uint64_t *n_numeric, uint64_t *stats);
+int redgpu_sum_text_dev(const redgpu_dfa *dfa, int which, const uint8_t *data, uint64_t len,
+                        uint8_t delim, uint64_t max_per_line, uint64_t n_bins, int accumulate,
+                        uint64_t *n_lines, uint64_t *n_items, uint64_t *n_numeric, uint64_t *stats,
+                        void *stream);
+uint32_t redgpu_sum_lds_bins(const redgpu_dfa *dfa);
+
 /* Measurement aid, no counterpart in the reference: one streaming read of `bytes` of device
  * memory (16-byte aligned) on the handle's device, asynchronous on `stream` - the read-bandwidth
  * calibration bench.py reports beside the roofline.  `sink` is a device uint32 the kernel may

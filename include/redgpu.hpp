@@ -287,6 +287,36 @@ inline std::vector<uint64_t> tallyText(const Executable &exec, std::string_view 
   return bins;
 }
 
+// per result the count, sum, minimum and maximum of the numbers in the matches (redgpu_sum_text):
+// nBins + 1 slots, [r] = the items of result r < nBins, [nBins] = everything else.  The items are
+// extractText's pieces (at most maxPerLine of a line); an item's number is the first (last = false)
+// or last run of digits 0-9 inside the piece, read as an unsigned decimal.  An item without a digit,
+// or with a run of 2^64 or more, is in `items` and in no statistic.  Sums are modulo 2^64; a slot
+// without numeric items has count 0, sum 0, min 2^64 - 1, max 0.
+struct SumStats {
+  std::vector<uint64_t> count, sum, min, max;  // nBins + 1 each
+  uint64_t lines = 0, items = 0, numeric = 0;  // delimiters found, pieces, pieces with a number
+};
+inline SumStats sumText(const Executable &exec, std::string_view text, size_t nBins,
+                        bool last = false, size_t maxPerLine = SIZE_MAX, char delim = '\n') {
+  const size_t slots = nBins + 1;
+  const uint64_t most = maxPerLine > (uint64_t(1) << 62) ? uint64_t(1) << 62 : uint64_t(maxPerLine);
+  std::vector<uint64_t> stats(4 * slots);
+  SumStats out;
+  throwOnError(redgpu_sum_text(exec.handle(), last ? REDGPU_SUM_LAST : REDGPU_SUM_FIRST,
+                               reinterpret_cast<const Byte *>(text.data()), text.size(),
+                               Byte(delim), most, nBins, 0, &out.lines, &out.items, &out.numeric,
+                               stats.data()));
+  auto row = [&](int r) {
+    return std::vector<uint64_t>(stats.begin() + r * slots, stats.begin() + (r + 1) * slots);
+  };
+  out.count = row(REDGPU_SUM_COUNT);
+  out.sum = row(REDGPU_SUM_SUM);
+  out.min = row(REDGPU_SUM_MIN);
+  out.max = row(REDGPU_SUM_MAX);
+  return out;
+}
+
 // grep -o | sort | uniq -c keyed by the matched bytes (redgpu_uniq_text): one UniqRecord per
 // distinct byte string among the text's items, in the order of first appearance - the string is
 // text.substr(first, length), count all its occurrences.  matches = true: the items are

@@ -230,6 +230,14 @@ def lib() -> C.CDLL:
                                             C.c_int, vp, vp, vp, vp]
         l.redgpu_tally_lds_bins.restype = C.c_uint32
         l.redgpu_tally_lds_bins.argtypes = [vp]
+        l.redgpu_sum_text.restype = C.c_int
+        l.redgpu_sum_text.argtypes = [vp, C.c_int, vp, u64, C.c_uint8, u64, u64, C.c_int, vp, vp,
+                                      vp, vp]
+        l.redgpu_sum_text_dev.restype = C.c_int
+        l.redgpu_sum_text_dev.argtypes = [vp, C.c_int, vp, u64, C.c_uint8, u64, u64, C.c_int, vp,
+                                          vp, vp, vp, vp]
+        l.redgpu_sum_lds_bins.restype = C.c_uint32
+        l.redgpu_sum_lds_bins.argtypes = [vp]
         l.redgpu_diag_read_dev.restype = C.c_int
         l.redgpu_diag_read_dev.argtypes = [vp, vp, u64, vp, vp]
         l.redgpu_diag_lds_dev.restype = C.c_int

@@ -241,6 +241,26 @@ hipError_t launchTallyText(const DevDfa &dfa, int what, int style, int doLeader,
                            uint64_t *nLines, uint64_t *nItems, uint64_t *bins, void *scratch,
                            const LaunchCfg &cfg, hipStream_t stream, const char **kernelName);
 
+// per result the count, sum, minimum and maximum of the numbers in a raw text's matches
+// (k_sum_text.h): an item is a piece launchExtractText would emit under maxPerLine, its slot the
+// result launchCollectText reports for it ((uint32_t)result < nBins, else nBins), its number the
+// first (which = REDGPU_SUM_FIRST) or last (REDGPU_SUM_LAST) run of digits inside the piece, read as
+// an unsigned decimal; an item without a digit or with a run of 2^64 or more enters no statistic.
+// stats[row * (nBins + 1) + slot], rows count, sum (modulo 2^64), min, max: overwritten (an empty
+// slot 0, 0, 2^64 - 1, 0), or merged into under accumulate.  *nItems = all items, *nNumeric = those
+// in the statistics; nLines, nItems and nNumeric may be null.  plain != 0: four atomics per item (the
+// form the carried run and the peel are measured against).  scratch: sumTextScratchBytes(len) bytes
+// of device memory, 16-byte aligned.  *kernelName = "k_sum_text".  sumLdsBins: the leading slots the
+// kernel keeps in LDS for a DFA of this table kind, staged table size and state count - a host
+// function.
+uint64_t sumTextScratchBytes(uint64_t len);
+uint32_t sumLdsBins(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates);
+hipError_t launchSumText(const DevDfa &dfa, int which, const uint8_t *data, uint64_t len,
+                         uint8_t delim, uint64_t maxPerLine, uint64_t nBins, int accumulate,
+                         int plain, uint64_t *nLines, uint64_t *nItems, uint64_t *nNumeric,
+                         uint64_t *stats, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                         const char **kernelName);
+
 // sed over a raw text (k_replace_text.h): replace<style, doLeader>(line, repl, max) over every line
 // of launchSplitLines' rule, the rewritten lines and their delimiters put back together (and the
 // tail behind them; under onlyChanged the changed lines alone, no tail): *outLen = the output's

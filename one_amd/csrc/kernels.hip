@@ -66,6 +66,9 @@
 //   k_fields_text.h   k_fd_*: awk -F's columns of a raw text - k_extract_text.h's chain per line with the
 //                     GAPS between the matches as the fields, left behind the last field asked for;
 //                     a sizing pass, a scan, and a write pass through k_extract_text.h's window
+//   k_sum_text.h      k_sum_text: per result the count, sum, min and max of the numbers in a raw text's
+//                     matches - k_tally_text.h's walk, the digits read once a piece's span is known,
+//                     four 64-bit words per slot behind an LDS front
 //   k_diag.h         bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
@@ -78,12 +81,12 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled eleven times in parallel (Makefile: -DREDGPU_TU=1/2/.../11): the templates are
+// This file is compiled twelve times in parallel (Makefile: -DREDGPU_TU=1/2/.../12): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
 // 3 = everything else and the dispatch, 4 = k_grep and k_filter_text (which runs k_grep's select), 5 = k_collect_text, 6 = k_replace_text,
 // 7 = k_tally_text, 8 = k_extract_text, 9 = k_route_text, 10 = k_uniq_text,
-// 11 = k_fields_text.
+// 11 = k_fields_text, 12 = k_sum_text.
 // REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
@@ -99,6 +102,7 @@
 #define REDGPU_TU_ROUTE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 9)
 #define REDGPU_TU_UNIQ_TEXT (REDGPU_TU == 0 || REDGPU_TU == 10)
 #define REDGPU_TU_FIELDS_TEXT (REDGPU_TU == 0 || REDGPU_TU == 11)
+#define REDGPU_TU_SUM_TEXT (REDGPU_TU == 0 || REDGPU_TU == 12)
 
 // return CALL(KIND) for the table kind of the DevDfa `d` in scope: a launcher's instantiation per kind
 #define REDGPU_KIND_SWITCH(CALL)                                                          \
@@ -147,6 +151,7 @@ namespace {
 #include "k_route_text.h"
 #include "k_uniq_text.h"
 #include "k_fields_text.h"
+#include "k_sum_text.h"
 
 } // namespace
 
@@ -1160,7 +1165,7 @@ hipError_t launchCollectText(const DevDfa &d, const uint8_t *data, uint64_t len,
 }
 #endif  // REDGPU_TU_COLLECT_TEXT
 
-#if REDGPU_TU_TALLY_TEXT
+#if REDGPU_TU_TALLY_TEXT || REDGPU_TU_SUM_TEXT
 // grep -c per result over a raw text (k_tally_text.h): the line index (launchTextIndex), then
 // k_tl_zero and the one pass of k_tally_text.  scratch: tallyTextScratchBytes(len) bytes, 16-byte
 // aligned: ONE bitmap and 20 bytes per chunk.
@@ -1182,7 +1187,9 @@ struct TallyScratch {
     bytes = c.at;
   }
 };
+#endif
 
+#if REDGPU_TU_TALLY_TEXT
 uint64_t tallyTextScratchBytes(uint64_t len) {
   return TallyScratch(nullptr, splitChunks(len)).bytes;
 }
@@ -1236,6 +1243,57 @@ hipError_t launchTallyText(const DevDfa &d, int what, int style, int doLeader, c
 #undef TL_ARGS
 }
 #endif  // REDGPU_TU_TALLY_TEXT
+
+#if REDGPU_TU_SUM_TEXT
+// per result the count, sum, min and max of the numbers in a raw text's matches (k_sum_text.h): the
+// line index (launchTextIndex), then k_sm_zero and the one pass of k_sum_text.  scratch:
+// sumTextScratchBytes(len) bytes, 16-byte aligned: launchTallyText's.
+uint64_t sumTextScratchBytes(uint64_t len) {
+  return TallyScratch(nullptr, splitChunks(len)).bytes;
+}
+
+uint32_t sumLdsBins(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates) {
+  DevDfa d{};
+  d.tableKind = tableKind;
+  d.tableBytes = tableBytes;
+  d.nStates = nStates;
+#define SM_BINS(K) sumLdsBinsK<K>(d)
+  REDGPU_KIND_SWITCH(SM_BINS)
+#undef SM_BINS
+}
+
+hipError_t launchSumText(const DevDfa &d, int which, const uint8_t *data, uint64_t len,
+                         uint8_t delim, uint64_t maxPerLine, uint64_t nBins, int accumulate,
+                         int plain, uint64_t *nLines, uint64_t *nItems, uint64_t *nNumeric,
+                         uint64_t *stats, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                         const char **kernelName) {
+  *kernelName = "k_sum_text";
+  const uint64_t nChunks = splitChunks(len);
+  const TallyScratch m(scratch, nChunks);
+  // (no selected bitmap to zero)
+  hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                 nullptr, m.misc, cfg.numCUs, stream);
+  if (e != hipSuccess) return e;
+  const uint64_t toZero = accumulate ? 0 : nBins + 1;
+  uint64_t zb = (toZero + 255) / 256;
+  if (zb > uint64_t(cfg.numCUs) * 8) zb = uint64_t(cfg.numCUs) * 8;
+  SumOut o{reinterpret_cast<unsigned long long *>(stats),
+           reinterpret_cast<unsigned long long *>(nItems ? nItems : m.misc + 2),
+           reinterpret_cast<unsigned long long *>(nNumeric ? nNumeric : m.misc + 3),
+           nBins + 1, uint32_t(nBins), 0};
+  hipLaunchKernelGGL(k_sm_zero, dim3(uint32_t(zb ? zb : 1)), dim3(256), 0, stream, o.stats, toZero,
+                     o.nItems, o.nNumeric);
+  e = hipGetLastError();
+  if (e != hipSuccess || nChunks == 0 || maxPerLine == 0) return e;
+  // L: the leading slots kept in LDS; 64-bit words, so a text of any length may use them
+  const uint32_t room = sumLdsBins(d.tableKind, d.tableBytes, d.nStates);
+  o.ldsBins = nBins + 1 < room ? uint32_t(nBins + 1) : room;
+  const GpBufs b{m.masks, nullptr, m.bases, m.open, nullptr, nullptr, nChunks};
+#define SM_CALL(K) launchSumK<K>(d, data, len, b, which, maxPerLine, plain, o, cfg, stream)
+  REDGPU_KIND_SWITCH(SM_CALL)
+#undef SM_CALL
+}
+#endif  // REDGPU_TU_SUM_TEXT
 
 #if REDGPU_TU_REPLACE_TEXT || REDGPU_TU_EXTRACT_TEXT
 // the scratch of sed and of grep -o's text, for a text of nChunks split chunks: what launchTextIndex

@@ -1365,6 +1365,89 @@ uint32_t redgpu_tally_lds_bins(const redgpu_dfa *dfa) {
   return tallyLdsBins(img.tableKind, (img.primaryBytes + 15u) & ~15u, img.nStates);
 }
 
+// the arguments of both sum_text forms
+static int checkSumText(const redgpu_dfa *dfa, int which, const uint8_t *data, uint64_t len,
+                        uint64_t nBins, const uint64_t *stats) {
+  return checkRawText(dfa, stats, "null stats buffer", data, len,
+                      which == REDGPU_SUM_FIRST || which == REDGPU_SUM_LAST
+                          ? nullptr
+                          : "which is neither REDGPU_SUM_FIRST nor REDGPU_SUM_LAST",
+                      nullptr, nBins);
+}
+
+// raw text -> per result the count, sum, min and max of the numbers in the matches
+// (k_sum_text.h): everything on `stream`, nothing read back
+int redgpu_sum_text_dev(const redgpu_dfa *dfa, int which, const uint8_t *data, uint64_t len,
+                        uint8_t delim, uint64_t max_per_line, uint64_t n_bins, int accumulate,
+                        uint64_t *n_lines, uint64_t *n_items, uint64_t *n_numeric, uint64_t *stats,
+                        void *stream) {
+  if (int rc = checkSumText(dfa, which, data, len, n_bins, stats)) return rc;
+  // REDGPU_SUM_PLAIN=1: four atomics per item, no carried run and no peel (measurements)
+  const char *env = getenv("REDGPU_SUM_PLAIN");
+  const int plain = env && env[0] == '1';
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return rawTextDev(dfa, s, sumTextScratchBytes(len),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchSumText(dfa->im->dev, which, data, len, delim, max_per_line, n_bins,
+                         accumulate ? 1 : 0, plain, n_lines, n_items, n_numeric, stats, scratch, cfg,
+                         s, name);
+  });
+}
+
+// host-buffer form: one upload of the text, device stats of the call's own, then the three
+// scalars and the 4 x (n_bins + 1) words back - merged into the caller's on the host under
+// accumulate
+int redgpu_sum_text(const redgpu_dfa *dfa, int which, const uint8_t *data, uint64_t len,
+                    uint8_t delim, uint64_t max_per_line, uint64_t n_bins, int accumulate,
+                    uint64_t *n_lines, uint64_t *n_items, uint64_t *n_numeric, uint64_t *stats) {
+  if (int rc = checkSumText(dfa, which, data, len, n_bins, stats)) return rc;
+  const uint64_t slots = n_bins + 1, words = 4 * slots;
+  std::vector<uint64_t> got;
+  if (accumulate) {
+    try {
+      got.resize(size_t(words));
+    } catch (const std::bad_alloc &) {
+      return fail(REDGPU_ELIMIT, "out of host memory");
+    }
+  }
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dN = call.buf<uint64_t>(kSlAux0, 3, "counts");
+  uint64_t *dStats = call.buf<uint64_t>(kSlAux1, words, "stats");
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return redgpu_sum_text_dev(dfa, which, dData, len, delim, max_per_line, n_bins, 0, dN, dN + 1,
+                               dN + 2, dStats, call.stream());
+  });
+  uint64_t counts[3] = {0, 0, 0};
+  call.download(counts, dN, 3, "counts");
+  // (nothing of the caller's is written before the last copy has arrived)
+  if (accumulate) call.download(got.data(), dStats, words, "stats");
+  if (int rc = call.wait()) return rc;
+  if (!accumulate) {
+    call.download(stats, dStats, words, "stats");
+    if (int rc = call.wait()) return rc;
+  } else {
+    for (uint64_t i = 0; i < slots; ++i) {
+      stats[i] += got[size_t(i)];
+      stats[slots + i] += got[size_t(slots + i)];
+      uint64_t &lo = stats[2 * slots + i], &hi = stats[3 * slots + i];
+      if (got[size_t(2 * slots + i)] < lo) lo = got[size_t(2 * slots + i)];
+      if (got[size_t(3 * slots + i)] > hi) hi = got[size_t(3 * slots + i)];
+    }
+  }
+  if (n_lines) *n_lines = counts[0];
+  if (n_items) *n_items = counts[1];
+  if (n_numeric) *n_numeric = counts[2];
+  return REDGPU_OK;
+}
+
+uint32_t redgpu_sum_lds_bins(const redgpu_dfa *dfa) {
+  if (!dfa) return 0;
+  const DfaImage &img = dfa->im->img;
+  return sumLdsBins(img.tableKind, (img.primaryBytes + 15u) & ~15u, img.nStates);
+}
+
 // the arguments of both replace_text forms
 static int checkReplaceText(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
                             const uint8_t *repl, uint64_t replLen, const uint64_t *outLen) {

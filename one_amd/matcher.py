@@ -1057,6 +1057,9 @@ def collect_text(exe, data, *, delim=b"\n", cap=None, want_positions=True):
 
 TALLY_LINES, TALLY_MATCHES = 0, 1
 UNIQ_LINES, UNIQ_MATCHES = 0, 1
+SUM_FIRST, SUM_LAST = 0, 1
+SUM_COUNT, SUM_SUM, SUM_MIN, SUM_MAX = 0, 1, 2, 3  # the rows of sum_text's stats
+_SUM_WHICH = {"first": SUM_FIRST, "last": SUM_LAST}
 
 
 def tally_text(exe, data, n_bins=None, *, matches=True, style=styInstant, do_leader=True,
@@ -1114,6 +1117,68 @@ def tally_text(exe, data, n_bins=None, *, matches=True, style=styInstant, do_lea
                                0 if into is None else 1, C.byref(nl), C.byref(ni),
                                bins.ctypes.data))
     return int(nl.value), int(ni.value), bins
+
+
+def sum_text(exe, data, n_bins=None, *, which="first", max_per_line=1 << 62, delim=b"\n",
+             into=None):
+    """redgpu_sum_text[_dev]: per result the count, sum, minimum and maximum of the decimal numbers
+    found in a raw text's matches - awk '{ n[c]++; s[c] += $x; if ($x > m[c]) m[c] = $x }'.  The
+    items are extract_text's pieces (at most max_per_line of a line), an item's slot is
+    collect_text's result for it (slot r for r < n_bins, else slot n_bins; n_bins=None means
+    exe.info["max_result"] + 1), its number the first (which="first") or last (which="last") run
+    of digits 0-9 inside the piece, read as an unsigned decimal.  An item without a digit, or
+    whose run is 2^64 or more, is counted in n_items and in no statistic; signs, fractions, hex and
+    thousands separators are not interpreted.  stats has shape (4, n_bins + 1), the rows SUM_COUNT,
+    SUM_SUM (modulo 2^64), SUM_MIN, SUM_MAX; a slot without numeric items reads 0, 0, 2^64 - 1, 0.
+    Everything is exact and bit-identical from run to run.
+    Host input -> (n_lines, n_items, n_numeric, stats): stats a uint64 array; into= takes such an
+    array, MERGES into it (counts and sums added, min and max merged: a stream of buffers reduced
+    into one table) and returns it.
+    A CUDA uint8 tensor -> the same tuple as device tensors, the three counts as 1-element int64
+    tensors and stats as int64 of shape (4, n_bins + 1) (into= such a CUDA tensor), asynchronously
+    on the current stream and without any read-back.  The words are unsigned: an empty slot's min
+    reads -1 there, and stats.cpu().numpy().view(numpy.uint64) gives the values as they are."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    if which not in _SUM_WHICH:
+        raise RedExceptApi('which must be "first" or "last"')
+    w, per = _SUM_WHICH[which], int(max_per_line)
+    n_bins = int(exe.info["max_result"]) + 1 if n_bins is None else int(n_bins)
+    if n_bins < 0 or per < 0:
+        raise RedExceptApi("n_bins and max_per_line must not be negative")
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = data.device
+        if into is None:
+            stats = torch.empty((4, n_bins + 1), dtype=torch.int64, device=dev)
+        else:
+            if (not _is_torch(into) or not into.is_cuda or into.device != dev or
+                    into.dtype != torch.int64 or not into.is_contiguous() or
+                    tuple(into.shape) != (4, n_bins + 1)):
+                raise RedExceptApi("into must be a contiguous int64 CUDA tensor of shape "
+                                   "(4, n_bins + 1) on the input's device")
+            stats = into
+        cnt = torch.empty(3, dtype=torch.int64, device=dev)
+        _check(l.redgpu_sum_text_dev(
+            exe._h, w, data.data_ptr() if data.numel() else None, data.numel(), d, per, n_bins,
+            0 if into is None else 1, cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 16,
+            stats.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], cnt[2:3], stats
+    a = _host_u8(data)
+    dp = a.ctypes.data if a.size else None
+    if into is None:
+        stats = np.zeros((4, n_bins + 1), dtype=np.uint64)
+    else:
+        if (not isinstance(into, np.ndarray) or into.dtype != np.uint64 or
+                into.shape != (4, n_bins + 1) or not into.flags.c_contiguous):
+            raise RedExceptApi("into must be a contiguous uint64 array of shape (4, n_bins + 1)")
+        stats = into
+    nl, ni, nn = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(l.redgpu_sum_text(exe._h, w, dp, a.size, d, per, n_bins, 0 if into is None else 1,
+                             C.byref(nl), C.byref(ni), C.byref(nn), stats.ctypes.data))
+    return int(nl.value), int(ni.value), int(nn.value), stats
 
 
 def uniq_text(exe, data, *, matches=True, style=styInstant, do_leader=True, max_per_line=1 << 62,
