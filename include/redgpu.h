@@ -893,6 +893,75 @@ int redgpu_route_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int d
                           uint64_t *bin_offsets, uint64_t *out_len, uint8_t *out, uint64_t out_cap,
                           void *stream);
 
+/* sed -n '/open/,/close/p': raw text in, the lines of its RANGES out as a text - the first verb in
+ * which a line's fate depends on the lines in front of it: a stack trace, a request from "start"
+ * to "done", a -----BEGIN / -----END block, a fenced block whose one pattern toggles.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter (the tail) are not a line and are never emitted.
+ *  - Line k's VALUE v_k is search<style,do_leader>(line k).result_, 0 when it does not match:
+ *    exactly redgpu_route_text's and redgpu_tally_text's REDGPU_TALLY_LINES value, with
+ *    redgpu_grep_text's verb and style normalisation.
+ *  - The lines are read in text order with a state that is OUTSIDE or INSIDE; it starts outside,
+ *    and ranges are numbered from 0:
+ *      outside, v == open_result:  range r begins at this line, its OPEN line; the state becomes
+ *        inside.  The line is never also the close line, even when open_result == close_result:
+ *        sed tests the second address from the next line on;
+ *      inside, v == close_result:  the range's CLOSE line; the state becomes outside behind it;
+ *      inside, anything else:      a BODY line - also v == open_result when the two results differ;
+ *      outside, anything else:     the line is outside - also a close line with no range open.
+ *    A range still open at the last line ends there, as sed's does.  open_result == close_result
+ *    is the TOGGLE form, sed -n '/```/,/```/p'.
+ *  - Only ranges numbered below max_ranges are COUNTED; the lines of later ranges are outside.
+ *  - Without invert a line of a counted range is emitted if it is a body line, if it is the open
+ *    line and emit_open != 0, or if it is the close line and emit_close != 0.  Under invert exactly
+ *    the other lines are emitted: sed '/A/,/B/d' is invert with both flags set.
+ *  - The output is the emitted lines in text order, each once, each with its delimiter: a raw text
+ *    every text verb accepts.
+ *  - *n_lines = delimiters found, *n_ranges = min(ranges, max_ranges), *n_emitted = lines emitted,
+ *    *out_len = the length of the whole output, whatever out_cap is.  out_len is required; the
+ *    other three may be NULL, each on its own.
+ *  - out == NULL or out_cap == 0 gives the sizes only.  Otherwise exactly the first
+ *    min(*out_len, out_cap) bytes of the output are written - the cut may fall inside a line - and
+ *    bytes of out from there on are NOT written (redgpu_filter_text's rule).  out must not overlap
+ *    data.
+ *  - The RECORDS are optional and do not depend on emit_open, emit_close or invert: first_line,
+ *    last_line, begin and end hold rec_cap entries each, and each may be NULL on its own.  For every
+ *    counted range r < rec_cap: first_line[r] and last_line[r] are the numbers of its open line and
+ *    of its last line, begin[r] is the offset of the open line's first byte, end[r] is one past the
+ *    delimiter of its last line - data[begin[r], end[r]) is a raw text.  Nothing is written at or
+ *    behind min(*n_ranges, rec_cap).
+ *  - REDGPU_EAPI for a NULL handle, a NULL out_len, a NULL data with len > 0, open_result < 1 or
+ *    close_result < 1 - the message names the argument - (the argument checks run before the
+ *    handle's device is looked at) and for a REDGPU_DEVICE_NONE handle; REDGPU_EEXEC for a style
+ *    that does not exist; REDGPU_ELIMIT for a text redgpu_split_lines refuses.  In every error case
+ *    nothing of the caller's is written.
+ *  - An empty text, or one without a delimiter: all four counts are 0 and nothing is written to out
+ *    or to the records (the _dev form writes the counts on the stream).
+ *  - A single line of megabytes is walked by one lane; a text whose ranges are one line long is
+ *    copied as many short runs, each by a whole wave: correct, and slow.
+ * redgpu_last_kernel() says "k_range_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - nothing is read
+ * back, and no per-line array is needed from the caller or in scratch ("is open" and "is close"
+ * live in two bit-planes of the delimiter bitmap's layout, the state is carried across the 16 KiB
+ * chunks by a scan; scratch is 3 * len / 8 for the bitmaps + 64 bytes per chunk + 8 bytes per 1,024
+ * chunks + 72, rounded up to 16, from the thread's pool).
+ * redgpu_range_text: host buffers, as redgpu_filter_text - one upload of the text, a sizes pass,
+ * a device output sized from *out_len, and min(*out_len, out_cap) bytes and
+ * min(*n_ranges, rec_cap) records downloaded. */
+int redgpu_range_text(const redgpu_dfa *dfa, int style, int do_leader, int32_t open_result,
+                      int32_t close_result, int emit_open, int emit_close, int invert,
+                      uint64_t max_ranges, const uint8_t *data, uint64_t len, uint8_t delim,
+                      uint64_t *n_lines, uint64_t *n_ranges, uint64_t *n_emitted, uint64_t *out_len,
+                      uint8_t *out, uint64_t out_cap, uint64_t rec_cap, uint64_t *first_line,
+                      uint64_t *last_line, uint64_t *begin, uint64_t *end);
+int redgpu_range_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int32_t open_result,
+                          int32_t close_result, int emit_open, int emit_close, int invert,
+                          uint64_t max_ranges, const uint8_t *data, uint64_t len, uint8_t delim,
+                          uint64_t *n_lines, uint64_t *n_ranges, uint64_t *n_emitted,
+                          uint64_t *out_len, uint8_t *out, uint64_t out_cap, uint64_t rec_cap,
+                          uint64_t *first_line, uint64_t *last_line, uint64_t *begin,
+                          uint64_t *end, void *stream);
+
 /* grep -o | sort | uniq -c, by the matched BYTES: raw text in, one record per distinct byte string
  * out - which IPs, URIs or error strings occur, and how often.  redgpu_tally_text counts by result
  * number; this verb counts by content, and only the distinct strings leave the device.

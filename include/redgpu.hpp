@@ -427,6 +427,52 @@ inline size_t routeText(const Executable &exec, Style style, bool doLeader, std:
   return size_t(routed);
 }
 
+// one /open/,/close/ range of rangeText: its first and last line, and text[begin, end)
+struct TextRange {
+  uint64_t firstLine, lastLine, begin, end;
+};
+
+// sed -n '/open/,/close/p' (redgpu_range_text): the lines of a text blob read in text order -
+// outside a range a line whose search<style,doLeader> result is openResult begins one, inside it
+// the next line whose result is closeResult ends it (openResult == closeResult: one pattern
+// toggles), a range still open at the last line ends there; only the first `most` ranges count.
+// `out` gets a counted range's body lines, its open line under emitOpen and its close line under
+// emitClose - under invert exactly the other lines (sed '/A/,/B/d') - in text order with their
+// delimiters; the tail behind the last delimiter is never emitted.  ranges, when given, gets one
+// record per counted range, whatever is emitted.  Returns the ranges counted; *emitted = the lines
+// in `out`.  `out` and the records are sized from a first call that only sizes.
+inline size_t rangeText(const Executable &exec, Style style, bool doLeader, std::string_view text,
+                        int32_t openResult, int32_t closeResult, std::string &out,
+                        bool emitOpen = true, bool emitClose = true, bool invert = false,
+                        size_t most = SIZE_MAX, char delim = '\n',
+                        std::vector<TextRange> *ranges = nullptr, size_t *emitted = nullptr) {
+  const Byte *p = reinterpret_cast<const Byte *>(text.data());
+  const uint64_t cnt = most > (uint64_t(1) << 62) ? uint64_t(1) << 62 : uint64_t(most);
+  uint64_t found = 0, lines = 0, outLen = 0;
+  throwOnError(redgpu_range_text(exec.handle(), style, doLeader, openResult, closeResult, emitOpen,
+                                 emitClose, invert, cnt, p, text.size(), Byte(delim), nullptr,
+                                 &found, &lines, &outLen, nullptr, 0, 0, nullptr, nullptr, nullptr,
+                                 nullptr));
+  out.resize(size_t(outLen));
+  std::vector<uint64_t> rec(ranges ? size_t(found) * 4 : 0);
+  uint64_t *r = rec.empty() ? nullptr : rec.data();
+  const uint64_t n = rec.size() / 4;
+  if (outLen || n)
+    throwOnError(redgpu_range_text(exec.handle(), style, doLeader, openResult, closeResult,
+                                   emitOpen, emitClose, invert, cnt, p, text.size(), Byte(delim),
+                                   nullptr, &found, &lines, &outLen,
+                                   reinterpret_cast<Byte *>(out.data()), outLen, n, r,
+                                   r ? r + n : nullptr, r ? r + 2 * n : nullptr,
+                                   r ? r + 3 * n : nullptr));
+  if (ranges) {
+    ranges->clear();
+    for (uint64_t i = 0; i < n; ++i)
+      ranges->push_back(TextRange{rec[i], rec[n + i], rec[2 * n + i], rec[3 * n + i]});
+  }
+  if (emitted) *emitted = size_t(lines);
+  return size_t(found);
+}
+
 // grep -o as a text (redgpu_extract_text): every match of every line of a text blob put in `out`,
 // one per line - the bytes replace<styLast,false> would substitute, each followed by the delimiter,
 // in text order; at most maxPerLine of a line (1 = its first match).  Output line j is the bytes of

@@ -195,6 +195,14 @@ def lib() -> C.CDLL:
         l.redgpu_route_text_dev.restype = C.c_int
         l.redgpu_route_text_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, u64, C.c_uint8, u64,
                                             vp, vp, vp, vp, vp, vp, u64, vp]
+        l.redgpu_range_text.restype = C.c_int
+        l.redgpu_range_text.argtypes = [vp, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_int,
+                                        C.c_int, u64, vp, u64, C.c_uint8, vp, vp, vp, vp, vp, u64,
+                                        u64, vp, vp, vp, vp]
+        l.redgpu_range_text_dev.restype = C.c_int
+        l.redgpu_range_text_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int,
+                                            C.c_int, C.c_int, u64, vp, u64, C.c_uint8, vp, vp, vp,
+                                            vp, vp, u64, u64, vp, vp, vp, vp, vp]
         l.redgpu_uniq_text.restype = C.c_int
         l.redgpu_uniq_text.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, u64, C.c_uint8, u64, u64,
                                        u64, vp, vp, vp, vp, vp, vp, vp]

@@ -343,6 +343,29 @@ hipError_t launchRouteText(const DevDfa &dfa, int style, int doLeader, int dropU
                            int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
                            const char **kernelName);
 
+// sed's /open/,/close/ line ranges of a raw text (k_range_text.h): over the lines of
+// launchSplitLines' rule, in text order, a range begins at a line of value openResult met outside a
+// range (its launchTallyText LINES value) and ends with the next line of value closeResult behind
+// it, or with the last line; only ranges numbered below maxRanges count.  Emitted are a counted
+// range's body lines, its open line under emitOpen and its close line under emitClose - under invert
+// exactly the other lines - in text order with their delimiters.  *nRanges = min(ranges,
+// maxRanges), *nEmitted = lines emitted, *outLen = the whole output's length, the first
+// min(*outLen, outCap) bytes in out and nothing behind them; for every counted range r < recCap
+// firstLine[r], lastLine[r] = its line numbers, begin[r], end[r] = its bytes (out, nLines, nRanges,
+// nEmitted and the four arrays may be null).  openResult, closeResult >= 1.  phases: 1 = index,
+// class, carry, mark (the records too) and scan, 2 = write out from what phase 1 left in scratch,
+// 3 = both.  scratch: rangeTextScratchBytes(len) bytes of device memory, 16-byte aligned.
+// *kernelName = "k_range_text".
+uint64_t rangeTextScratchBytes(uint64_t len);
+hipError_t launchRangeText(const DevDfa &dfa, int style, int doLeader, int32_t openResult,
+                           int32_t closeResult, int emitOpen, int emitClose, int invert,
+                           uint64_t maxRanges, const uint8_t *data, uint64_t len, uint8_t delim,
+                           uint64_t *nLines, uint64_t *nRanges, uint64_t *nEmitted,
+                           uint64_t *outLen, uint8_t *out, uint64_t outCap, uint64_t recCap,
+                           uint64_t *firstLine, uint64_t *lastLine, uint64_t *begin, uint64_t *end,
+                           int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                           const char **kernelName);
+
 // a raw text's distinct items counted by their bytes (k_uniq_text.h): an item is a piece
 // launchExtractText would emit under maxPerLine (what = REDGPU_UNIQ_MATCHES) or a line
 // launchGrepText selects without invert (REDGPU_UNIQ_LINES, its normalisation), without its

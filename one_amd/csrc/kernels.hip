@@ -60,6 +60,9 @@
 //   k_route_text.h    k_ro_*: a raw text's lines grouped by result - k_grep.h's walk leaves each line's
 //                     bucket in bit-planes, a sizing pass per (bucket, chunk), ONE scan, and
 //                     k_filter_text.h's run copy once per bucket present in a chunk
+//   k_range_text.h    k_rg_*: sed's /open/,/close/ line ranges of a raw text - k_route_text.h's walk leaves
+//                     "is open" / "is close" in two bit-planes, a two-state machine is carried across
+//                     the chunks by k_gp_open's or k_split_scan's scan, and k_filter_text.h's run copy
 //   k_uniq_text.h     k_uq_*: a raw text's distinct matches (or selected lines) counted by their BYTES -
 //                     k_tally_text.h's walk, a hash table keyed by the text's own bytes behind an LDS
 //                     front, and an ordering pass over a first-occurrence bitmap
@@ -81,12 +84,12 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled twelve times in parallel (Makefile: -DREDGPU_TU=1/2/.../12): the templates are
+// This file is compiled thirteen times in parallel (Makefile: -DREDGPU_TU=1/2/.../13): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
 // 3 = everything else and the dispatch, 4 = k_grep and k_filter_text (which runs k_grep's select), 5 = k_collect_text, 6 = k_replace_text,
 // 7 = k_tally_text, 8 = k_extract_text, 9 = k_route_text, 10 = k_uniq_text,
-// 11 = k_fields_text, 12 = k_sum_text.
+// 11 = k_fields_text, 12 = k_sum_text, 13 = k_range_text.
 // REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
@@ -103,6 +106,7 @@
 #define REDGPU_TU_UNIQ_TEXT (REDGPU_TU == 0 || REDGPU_TU == 10)
 #define REDGPU_TU_FIELDS_TEXT (REDGPU_TU == 0 || REDGPU_TU == 11)
 #define REDGPU_TU_SUM_TEXT (REDGPU_TU == 0 || REDGPU_TU == 12)
+#define REDGPU_TU_RANGE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 13)
 
 // return CALL(KIND) for the table kind of the DevDfa `d` in scope: a launcher's instantiation per kind
 #define REDGPU_KIND_SWITCH(CALL)                                                          \
@@ -152,6 +156,7 @@ namespace {
 #include "k_uniq_text.h"
 #include "k_fields_text.h"
 #include "k_sum_text.h"
+#include "k_range_text.h"
 
 } // namespace
 
@@ -1613,6 +1618,117 @@ hipError_t launchRouteText(const DevDfa &d, int style, int doLeader, int dropUnm
   return hipGetLastError();
 }
 #endif  // REDGPU_TU_ROUTE_TEXT
+
+#if REDGPU_TU_RANGE_TEXT
+// sed's /open/,/close/ line ranges of a raw text (k_range_text.h): the line index (launchTextIndex),
+// the class walk, the machine's carry (k_gp_open or k_split_scan), the k_rg_* passes around
+// k_split_scan and k_misc.h's scan, and k_filter_text.h's write pass.  scratch:
+// rangeTextScratchBytes(len) bytes, 16-byte aligned: three bitmaps (len / 8 each), and 64 bytes per
+// chunk, 8 per 1,024 chunks and 72, rounded up to 16.
+struct RangeScratch {
+  uint64_t *bases, *open, *carry, *startBases, *emitBytes;  // [nChunks] each
+  uint64_t *outBases;                                       // [nChunks + 1]
+  uint64_t *partials;                                       // [nPart]
+  // [8]: lines, the index scan's two spare words, ranges begun, a scan's spare word, events, the
+  // state behind the last line, the position behind the last delimiter
+  uint64_t *misc;
+  uint32_t *counts, *events, *starts, *emitLines;  // [nChunks] each
+  uint16_t *masks, *openBits, *closeBits;  // the delimiter bitmap, the two planes (open: then EMIT)
+  uint64_t nPart, bytes;
+  RangeScratch(void *scratch, uint64_t nChunks) : nPart((nChunks + 1023) / 1024) {
+    Carve c{static_cast<uint8_t *>(scratch)};
+    bases = c.take<uint64_t>(nChunks);
+    open = c.take<uint64_t>(nChunks);
+    carry = c.take<uint64_t>(nChunks);
+    startBases = c.take<uint64_t>(nChunks);
+    emitBytes = c.take<uint64_t>(nChunks);
+    outBases = c.take<uint64_t>(nChunks + 1);
+    partials = c.take<uint64_t>(nPart);
+    misc = c.take<uint64_t>(8);
+    counts = c.take<uint32_t>(nChunks);
+    events = c.take<uint32_t>(nChunks);
+    starts = c.take<uint32_t>(nChunks);
+    emitLines = c.take<uint32_t>(nChunks);
+    c.align(16);
+    masks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    openBits = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    closeBits = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    bytes = c.at;
+  }
+};
+
+uint64_t rangeTextScratchBytes(uint64_t len) {
+  return RangeScratch(nullptr, splitChunks(len)).bytes;
+}
+
+hipError_t launchRangeText(const DevDfa &d, int style, int doLeader, int32_t openResult,
+                           int32_t closeResult, int emitOpen, int emitClose, int invert,
+                           uint64_t maxRanges, const uint8_t *data, uint64_t len, uint8_t delim,
+                           uint64_t *nLines, uint64_t *nRanges, uint64_t *nEmitted,
+                           uint64_t *outLen, uint8_t *out, uint64_t outCap, uint64_t recCap,
+                           uint64_t *firstLine, uint64_t *lastLine, uint64_t *begin, uint64_t *end,
+                           int phases, void *scratch, const LaunchCfg &cfg, hipStream_t stream,
+                           const char **kernelName) {
+  *kernelName = "k_range_text";
+  const uint64_t nChunks = splitChunks(len);
+  const RangeScratch m(scratch, nChunks);
+  const int toggle = openResult == closeResult;
+  // (TextHits' verb bitmap is the open plane, which k_rg_mark turns into the EMIT bitmap)
+  const GpBufs b{m.masks, m.openBits, m.bases, m.open, nullptr, nullptr, nChunks};
+  const RgBufs r{m.openBits, m.closeBits, m.carry, m.events, m.starts, m.startBases, m.emitBytes,
+                 m.emitLines, m.misc + 6, openResult, closeResult, toggle};
+  const RgArgs a{emitOpen, emitClose, invert, maxRanges, recCap, firstLine, lastLine, begin, end};
+  // the grid of the passes without a table: a wave per chunk, four to a workgroup
+  uint64_t small = (nChunks + 3) / 4;
+  if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
+  if (phases & 1) {
+    // (no bitmap for k_gp_last to zero: the planes are zeroed here, both at once)
+    hipError_t e = launchTextIndex(data, len, delim, m.misc, m.counts, m.bases, m.masks, m.open,
+                                   nullptr, m.misc + 1, cfg.numCUs, stream);
+    if (e != hipSuccess) return e;
+    if (nChunks) {
+      e = hipMemsetAsync(m.openBits, 0, size_t(toggle ? 1 : 2) * nChunks * (kSplitChunk / 8), stream);
+      if (e != hipSuccess) return e;
+      const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
+      int verb = kSearch;
+      normalizeVerbStyle(d, cfg, lead != 0, verb, style);
+#define RG_ARGS d, data, b, style, lead, r, cfg, stream
+#define RG_CALL(K) \
+  (verb == kSearch ? launchRangeClassK<K, kSearch>(RG_ARGS) : launchRangeClassK<K, kMatch>(RG_ARGS))
+      e = [&]() -> hipError_t { REDGPU_KIND_SWITCH(RG_CALL) }();
+#undef RG_CALL
+#undef RG_ARGS
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_rg_events, dim3(uint32_t(small)), dim3(256), 0, stream, r, nChunks);
+      if (toggle) {
+        hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, m.events, nChunks, m.carry,
+                           m.misc + 5, m.misc + 4, uint64_t(0));
+      } else {
+        hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, m.carry, nChunks);
+      }
+      hipLaunchKernelGGL(k_rg_starts, dim3(uint32_t(small)), dim3(256), 0, stream, r, nChunks);
+      hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, m.starts, nChunks,
+                         m.startBases, m.misc + 3, m.misc + 4, uint64_t(0));
+      hipLaunchKernelGGL(k_rg_mark, dim3(uint32_t(small)), dim3(256), 0, stream, b, r, a);
+      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream,
+                         m.emitBytes, nChunks, m.partials);
+      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
+      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.emitBytes,
+                         nChunks, m.partials, m.outBases);
+    }
+    hipLaunchKernelGGL(k_rg_totals, dim3(1), dim3(1024), 0, stream, r, a, nChunks,
+                       nChunks ? m.outBases + nChunks : nullptr, m.misc + 3, m.misc, nLines, nRanges,
+                       nEmitted, outLen);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if ((phases & 2) && out && outCap && nChunks) {
+    hipLaunchKernelGGL(k_ft_write, dim3(uint32_t(small)), dim3(256), 0, stream, data, b,
+                       m.emitBytes, m.outBases, out, outCap);
+  }
+  return hipGetLastError();
+}
+#endif  // REDGPU_TU_RANGE_TEXT
 
 #if REDGPU_TU_UNIQ_TEXT
 // a raw text's distinct items counted by their bytes (k_uniq_text.h): the line index

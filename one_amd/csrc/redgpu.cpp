@@ -1652,6 +1652,104 @@ int redgpu_route_text(const redgpu_dfa *dfa, int style, int do_leader, int drop_
   return call.wait();
 }
 
+// the arguments of both range_text forms
+static int checkRangeText(const redgpu_dfa *dfa, int style, int32_t openResult,
+                          int32_t closeResult, const uint8_t *data, uint64_t len,
+                          const uint64_t *outLen) {
+  const char *own = nullptr;
+  if (openResult < 1) own = "open_result is less than 1";
+  else if (closeResult < 1) own = "close_result is less than 1";
+  return checkRawText(dfa, outLen, "null out_len buffer", data, len, own, &style);
+}
+
+// raw text -> the lines of its /open/,/close/ ranges, as a text, and a record per range
+// (k_range_text.h): everything on `stream`, nothing read back; phases as launchRangeText's
+static int rangeTextDev(const redgpu_dfa *dfa, int style, int doLeader, int32_t openResult,
+                        int32_t closeResult, int emitOpen, int emitClose, int invert,
+                        uint64_t maxRanges, const uint8_t *data, uint64_t len, uint8_t delim,
+                        uint64_t *nLines, uint64_t *nRanges, uint64_t *nEmitted, uint64_t *outLen,
+                        uint8_t *out, uint64_t outCap, uint64_t recCap, uint64_t *firstLine,
+                        uint64_t *lastLine, uint64_t *begin, uint64_t *end, int phases,
+                        hipStream_t s) {
+  if (int rc = checkRangeText(dfa, style, openResult, closeResult, data, len, outLen)) return rc;
+  return rawTextDev(dfa, s, rangeTextScratchBytes(len),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchRangeText(dfa->im->dev, style, doLeader ? 1 : 0, openResult, closeResult,
+                           emitOpen ? 1 : 0, emitClose ? 1 : 0, invert ? 1 : 0, maxRanges, data, len,
+                           delim, nLines, nRanges, nEmitted, outLen, out, outCap, recCap, firstLine,
+                           lastLine, begin, end, phases, scratch, cfg, s, name);
+  });
+}
+
+int redgpu_range_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int32_t open_result,
+                          int32_t close_result, int emit_open, int emit_close, int invert,
+                          uint64_t max_ranges, const uint8_t *data, uint64_t len, uint8_t delim,
+                          uint64_t *n_lines, uint64_t *n_ranges, uint64_t *n_emitted,
+                          uint64_t *out_len, uint8_t *out, uint64_t out_cap, uint64_t rec_cap,
+                          uint64_t *first_line, uint64_t *last_line, uint64_t *begin,
+                          uint64_t *end, void *stream) {
+  return rangeTextDev(dfa, style, do_leader, open_result, close_result, emit_open, emit_close,
+                      invert, max_ranges, data, len, delim, n_lines, n_ranges, n_emitted, out_len,
+                      out, out_cap, rec_cap, first_line, last_line, begin, end, 3,
+                      static_cast<hipStream_t>(stream));
+}
+
+// host-buffer form, as redgpu_filter_text: the text goes up once; phase 1 leaves the sizes, the
+// bitmaps, the chunks' output bases and the records on the device, the device output is sized from
+// *out_len, phase 2 copies the runs, and min(*out_len, out_cap) bytes and the records that exist
+// come back
+int redgpu_range_text(const redgpu_dfa *dfa, int style, int do_leader, int32_t open_result,
+                      int32_t close_result, int emit_open, int emit_close, int invert,
+                      uint64_t max_ranges, const uint8_t *data, uint64_t len, uint8_t delim,
+                      uint64_t *n_lines, uint64_t *n_ranges, uint64_t *n_emitted, uint64_t *out_len,
+                      uint8_t *out, uint64_t out_cap, uint64_t rec_cap, uint64_t *first_line,
+                      uint64_t *last_line, uint64_t *begin, uint64_t *end) {
+  if (int rc = checkRangeText(dfa, style, open_result, close_result, data, len, out_len)) return rc;
+  // no more ranges than lines, nor lines than bytes
+  if (rec_cap > len) rec_cap = len;
+  if (rec_cap > max_ranges) rec_cap = max_ranges;
+  uint64_t *host[4] = {first_line, last_line, begin, end};
+  if (!first_line && !last_line && !begin && !end) rec_cap = 0;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 4, "sizes");
+  uint64_t *dRec = rec_cap ? call.buf<uint64_t>(kSlAux0, 4 * rec_cap, "records") : nullptr;
+  uint64_t *dev[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 4 && dRec; ++i)
+    if (host[i]) dev[i] = dRec + uint64_t(i) * rec_cap;
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return rangeTextDev(dfa, style, do_leader, open_result, close_result, emit_open, emit_close,
+                        invert, max_ranges, dData, len, delim, dSizes, dSizes + 1, dSizes + 2,
+                        dSizes + 3, nullptr, 0, rec_cap, dev[0], dev[1], dev[2], dev[3], 1,
+                        call.stream());
+  });
+  uint64_t sizes[4] = {0, 0, 0, 0};
+  call.download(sizes, dSizes, 4, "sizes");
+  if (int rc = call.wait()) return rc;
+  const uint64_t got = sizes[1] < rec_cap ? sizes[1] : rec_cap;
+  const uint64_t put = sizes[3] < out_cap ? sizes[3] : out_cap;
+  if (out && put) {
+    // (the streams are drained: growing the slot waits for nothing)
+    uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
+    call.run([&] {
+      return rangeTextDev(dfa, style, do_leader, open_result, close_result, emit_open, emit_close,
+                          invert, max_ranges, dData, len, delim, dSizes, dSizes + 1, dSizes + 2,
+                          dSizes + 3, dOut, put, 0, nullptr, nullptr, nullptr, nullptr, 2,
+                          call.stream());
+    });
+    call.download(out, dOut, put, "out");
+  }
+  for (int i = 0; i < 4 && got; ++i)
+    if (dev[i]) call.download(host[i], dev[i], got, "records");
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = sizes[0];
+  if (n_ranges) *n_ranges = sizes[1];
+  if (n_emitted) *n_emitted = sizes[2];
+  *out_len = sizes[3];
+  return REDGPU_OK;
+}
+
 // the arguments of both uniq_text forms (every output may be NULL: the handle stands in for the
 // buffer checkRawText asks for)
 static int checkUniqText(const redgpu_dfa *dfa, int what, int style, const uint8_t *data,

@@ -1421,6 +1421,84 @@ def route_text(exe, data, n_bins=None, style=styInstant, do_leader=True, *, drop
             buf[:int(olen.value)].tobytes())
 
 
+def range_text(exe, data, open_result, close_result=None, style=styInstant, do_leader=True, *,
+               emit_open=True, emit_close=True, invert=False, max_ranges=1 << 62, delim=b"\n",
+               out=None, out_cap=None, rec_cap=0):
+    """redgpu_range_text[_dev]: sed -n '/open/,/close/p' - the delimiter-terminated lines of a raw
+    text buffer read in text order with a state that is outside or inside: outside, a line whose
+    search<style,doLeader> result is open_result begins a range (its open line); inside, the next
+    line whose result is close_result ends it (its close line), every other line is a body line; a
+    range still open at the last line ends there.  close_result=None means open_result: the
+    toggle form, sed -n '/```/,/```/p'.  Only ranges numbered below max_ranges count.  Emitted are
+    a counted range's body lines, its open line under emit_open and its close line under
+    emit_close - under invert=True exactly the other lines (sed '/A/,/B/d') - in text order, each
+    with its delimiter.  The records do not depend on emit_open, emit_close or invert: for every
+    counted range r < rec_cap its first and last line numbers and data[begin[r]:end[r]], its bytes.
+    The tail behind the last delimiter is not a line and is never emitted.
+    Host input -> (n_lines, n_ranges, n_emitted, bytes, first_line, last_line, begin, end): the
+    records as uint64 arrays of min(n_ranges, rec_cap) entries.
+    A CUDA uint8 tensor needs out (a contiguous uint8 CUDA tensor to write into) or out_cap (one
+    of that size is made; 0 gives the sizes only) -> (n_lines, n_ranges, n_emitted, out_len, out,
+    first_line, last_line, begin, end): the counts as 1-element int64 tensors, the records as
+    int64 tensors of rec_cap entries of which the first min(n_ranges, rec_cap) are written,
+    asynchronously on the current stream and without any read-back; out_len may exceed the room,
+    bytes of out from min(out_len, room) on are untouched.  The output is a raw text that every
+    text verb accepts."""
+    l = _lib.lib()
+    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    style, lead, inv = int(style), 1 if do_leader else 0, 1 if invert else 0
+    eo, ec = 1 if emit_open else 0, 1 if emit_close else 0
+    open_result = int(open_result)
+    close_result = open_result if close_result is None else int(close_result)
+    max_ranges, rec_cap = int(max_ranges), int(rec_cap)
+    if open_result < 1 or close_result < 1:
+        raise RedExceptApi("open_result and close_result must be at least 1")
+    if open_result >= 1 << 31 or close_result >= 1 << 31:
+        raise RedExceptApi("open_result and close_result must fit 31 bits")
+    if max_ranges < 0 or rec_cap < 0:
+        raise RedExceptApi("max_ranges and rec_cap must not be negative")
+    if _is_torch(data):
+        import torch
+        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev = data.device
+        if out is None and out_cap is None:
+            raise RedExceptApi("device range_text needs out or out_cap (room for the output)")
+        if out is None:
+            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
+        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
+              not out.is_contiguous() or out.device != dev):
+            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
+        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        cnt = torch.empty(4, dtype=torch.int64, device=dev)
+        rec = torch.empty((4, rec_cap), dtype=torch.int64, device=dev)
+        at = [rec[k].data_ptr() if rec_cap else None for k in range(4)]
+        _check(l.redgpu_range_text_dev(
+            exe._h, style, lead, open_result, close_result, eo, ec, inv, max_ranges,
+            data.data_ptr() if data.numel() else None, data.numel(), d, cnt.data_ptr(),
+            cnt.data_ptr() + 8, cnt.data_ptr() + 16, cnt.data_ptr() + 24,
+            out.data_ptr() if room else None, room, rec_cap, at[0], at[1], at[2], at[3],
+            torch.cuda.current_stream(dev).cuda_stream))
+        return cnt[0:1], cnt[1:2], cnt[2:3], cnt[3:4], out, rec[0], rec[1], rec[2], rec[3]
+    if out is not None or out_cap is not None:
+        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    a = _host_u8(data)
+    nl, nr, ne, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    # the output is no longer than the text, and there are no more ranges than bytes
+    cap = int(a.size)
+    rec_cap = min(rec_cap, cap)
+    buf = np.zeros(max(cap, 1), dtype=np.uint8)
+    rec = np.zeros((4, max(rec_cap, 1)), dtype=np.uint64)
+    _check(l.redgpu_range_text(
+        exe._h, style, lead, open_result, close_result, eo, ec, inv, max_ranges,
+        a.ctypes.data if a.size else None, a.size, d, C.byref(nl), C.byref(nr), C.byref(ne),
+        C.byref(olen), buf.ctypes.data, cap, rec_cap, rec[0].ctypes.data, rec[1].ctypes.data,
+        rec[2].ctypes.data, rec[3].ctypes.data))
+    got = min(int(nr.value), rec_cap)
+    return (int(nl.value), int(nr.value), int(ne.value), buf[:int(olen.value)].tobytes(),
+            rec[0, :got].copy(), rec[1, :got].copy(), rec[2, :got].copy(), rec[3, :got].copy())
+
+
 def extract_text(exe, data, *, max_per_line=1 << 62, delim=b"\n", out=None, out_cap=None):
     """redgpu_extract_text[_dev]: grep -o as a text - every match of every delimiter-terminated
     line of a raw text buffer (Red::collect's chain, collect_text's records), as bytes: the span
