@@ -1,7 +1,7 @@
 """Differential fuzz on the GPU: random DFAs x random line shapes x every verb / style / leader x
 random placement and kernel-selection flags, against the CPU oracle.  Not part of the pytest
 suite (it is open-ended); a failure prints the case and exits non-zero.
-usage: fuzz_gpu.py [cases] [seed] [hot | cls | lists | blocks | long | text]
+usage: fuzz_gpu.py [cases] [seed] [hot | cls | lists | blocks | long | text | lines | pieces] [dry]
 long: the DFAs and placement flags of the general mode, one buffer of 2 KiB to 128 KiB as ONE
 text through collect_long, replace_long, search_long and match_all_long (random style, leader
 setting, chunk size, cap / max count and replacement).  Without a pure dead state an attempt that
@@ -12,7 +12,29 @@ text: the same DFAs and flags, one buffer of 0 to 96 KiB as a raw text through g
 collect_text, replace_text and match_text, each against sampleLines' loop (oracle.split_lines_loop)
 plus the oracle's verb on every line alone.  The delimiter is '\n', 0, ' ' or a byte of the data, put
 at a random density over whatever the data holds of it; where walks do not die (as above) a
-delimiter comes at least every 1024 bytes, since search over a line is quadratic there."""
+delimiter comes at least every 1024 bytes, since search over a line is quadratic there.
+lines: text's DFAs (the random ones with max_result drawn from 1 to 5000 too, so that results above
+route_text's 255 buckets and the LDS bins exist), flags, delimiters and densities - the draws
+weighted so that most cases have an item: fewer golden DFAs, tiny and never-accepting ones, fewer
+texts without a line or of empty lines only, something planted for a golden DFA to find - text's
+buffer kinds and one of digit runs, 0 to 96 KiB (one case in twenty empty), through the verbs whose item
+is a line's search result - tally_text(matches=False), filter_text, route_text, range_text and
+uniq_text(matches=False) - each once with random parameters against tests/text_rules.py.  The verbs
+that write a text run through their host form one time in three, else through the device form: the
+text at a pointer offset of 0 to 15, the output a 0x55-filled buffer handed over at out_cap = exact,
+0 or half the expected length - the counts, min(out_len, out_cap) bytes and the sentinels behind
+them (range_text's records likewise, behind min(n_ranges, rec_cap)).  The others take the host form
+or the device form at an odd offset.
+pieces: the same, through the verbs whose items come from collect's chain -
+tally_text(matches=True), extract_text, uniq_text(matches=True), sum_text and fields_text.
+dry (a fifth argument, lines and pieces only): no device is touched - DFA facts come from a
+device-less handle, the case generator and text_rules run, the GPU calls do not.  Both modes end
+with one `cover` line per verb: in how many cases the oracle's side had an item at all (in front
+of any cap: max_count, max_ranges, max_per_line, max_fields), a text
+longer than one 16 KiB chunk, an item in the overflow slot, a truncated output, a piece of 64
+bytes or more, a piece that begins in front of its record's start, a number from 2^64, a range or a
+merged context across a chunk border; and one `special` line for the inputs nobody designs.
+tests/test_text_rules.py holds the dry run of the smoke test's cases and seed to floors on these."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -31,6 +53,10 @@ BLOCKS = len(sys.argv) > 3 and sys.argv[3] == "blocks"          # >= 4096 lines,
                                                                 # match_all: the block kernels
 LONG = len(sys.argv) > 3 and sys.argv[3] == "long"              # one text, the *_long verbs
 TEXT = len(sys.argv) > 3 and sys.argv[3] == "text"              # one raw text, the *_text verbs
+LINES = len(sys.argv) > 3 and sys.argv[3] == "lines"            # ... the newer ones: a line's result
+PIECES = len(sys.argv) > 3 and sys.argv[3] == "pieces"          # ... the newer ones: collect's chain
+NEWER = LINES or PIECES
+DRY = NEWER and len(sys.argv) > 4 and sys.argv[4] == "dry"      # the generator and the rules alone
 rng = np.random.default_rng(seed)
 ALPHA = np.frombuffer(b"abcdefghijklmnopqrstuvwxyz0123456789 ./:-_=&?%@[]", dtype=np.uint8)
 
@@ -304,17 +330,419 @@ def text_case(desc, blob, exe, cpu, data):
     return None
 
 
+# the newer raw-text verbs: modes lines and pieces -------------------------------------------------
+if NEWER:
+    import text_rules as TR
+    from one_amd import workloads as W
+    from one_amd.matcher import fields_mask
+    PLANTS_WIDE = [b"error", b"an error: x", b"New York", b"123abcd ", b"aab", W.URI_PLANT,
+                   W.URI_USER_PLANT, W.URI_V6_PLANT] + W.log100_heads()[::9]
+CHUNK = 16384
+SENT64 = 0x5555555555555555
+SEPS = np.frombuffer(b" ,.:-x", dtype=np.uint8)
+WRITERS = ("filter_text", "route_text", "range_text", "extract_text", "fields_text")
+VERBS_OF = {"lines": ("tally_text", "filter_text", "route_text", "range_text", "uniq_text"),
+            "pieces": ("tally_text", "extract_text", "uniq_text", "sum_text", "fields_text")}
+# which of the dry run's items belong to which verb (item and chunk belong to all)
+COVER_OF = {"overflow": ("tally_text", "route_text", "sum_text"), "truncated": WRITERS,
+            "piece64": ("extract_text", "fields_text"),
+            "loose": ("extract_text", "fields_text", "uniq_text", "sum_text"),
+            "over64bit": ("sum_text",), "numeric": ("sum_text",), "range_border": ("range_text",),
+            "merged_border": ("filter_text",)}
+cover = {}
+special = dict(empty=0, all_delims=0, delim0=0, no_dead=0, acc09=0)
+
+
+def make_dfa_wide():
+    """make_dfa's general draw - fewer golden DFAs, more accepting states, so that most cases have
+    an item - the random DFAs with max_result drawn as well"""
+    k = int(rng.integers(0, 10))
+    if k < 3:
+        name = CONFIG_DFAS[int(rng.integers(0, len(CONFIG_DFAS)))]
+        return name, load_dfa(name)
+    n = int(rng.choice([2, 5, 17, 17, 100, 100, 255, 256, 257, 300, 800, 2500]))
+    c = int(rng.choice([1, 2, 7, 30, 64, 128, 256]))
+    dead = float(rng.choice([0.0, 0.0, 0.01, 0.05, 0.3, 0.9]))
+    acc = float(rng.choice([0.0, 0.05, 0.05, 0.2, 0.2, 0.2, 0.2, 0.9, 0.9, 0.9, 0.9, 0.9]))
+    most = int(rng.choice([1, 5, 40, 300, 5000]))
+    s = int(rng.integers(0, 1 << 30))
+    special["acc09"] += acc == 0.9
+    return "rnd(%d,%d,%d,dead=%.2f,acc=%.2f,max_result=%d)" % (n, c, s, dead, acc, most), \
+        random_dfa(n, c, s, dead_frac=dead, accept_frac=acc, max_result=most)
+
+
+def make_data_wide(nbytes, blob_name):
+    """make_data's four kinds and a fifth: runs of 1 to 25 digits, a separator between two; under
+    a golden DFA mostly with something planted that it matches, every 100 bytes or so"""
+    if rng.random() >= 0.25:
+        d = make_data(nbytes, blob_name)
+    else:
+        d = rng.integers(0x30, 0x3A, nbytes, dtype=np.uint8)
+        ends = np.cumsum(rng.integers(1, 26, nbytes // 2 + 1) + 1) - 1
+        ends = ends[ends < nbytes]
+        d[ends] = SEPS[rng.integers(0, len(SEPS), len(ends))]
+    if blob_name in CONFIG_DFAS and rng.random() < 0.8:
+        d = d.copy()
+        for _ in range(nbytes // 100):
+            p = np.frombuffer(PLANTS_WIDE[int(rng.integers(0, len(PLANTS_WIDE)))], dtype=np.uint8)
+            if nbytes > len(p):
+                at = int(rng.integers(0, nbytes - len(p)))
+                d[at:at + len(p)] = p
+    return np.ascontiguousarray(d)
+
+
+def raw_text(exe, cpu, data):
+    """text_case's delimiters and densities over data, the two densities at which most texts have no
+    item (no line at all, every line empty) drawn less often: (data, delim, density)"""
+    delim = [0x0A, 0x00, 0x20, int(data[int(rng.integers(0, len(data)))]) if len(data) else 0x0A][
+        int(rng.integers(0, 4))]
+    density = float(rng.choice([0.0, 1 / 2000, 1 / 100, 1 / 8, 1.0], p=[0.1, 0.2, 0.3, 0.3, 0.1]))
+    data = data.copy()
+    data[rng.random(len(data)) < density] = delim
+    if exe.info["n_pure_dead"] == 0 or not walks_die(cpu, data):
+        data[1023::1024] = delim
+    special["empty"] += len(data) == 0
+    special["all_delims"] += len(data) > 0 and bool((data == delim).all())
+    special["delim0"] += delim == 0
+    special["no_dead"] += exe.info["n_pure_dead"] == 0
+    return data, delim, density
+
+
+def draw_bins(most, limit=None):
+    """n_bins from {0, 1, a value below the DFA's largest result, max_result + 1, None}"""
+    nb = [0, 1, int(rng.integers(1, max(2, most))), most + 1, None][int(rng.integers(0, 5))]
+    return nb if nb is None or limit is None else min(nb, limit)
+
+
+def draw_form(writer):
+    """(device form?, the text's pointer offset, out_cap's kind): a writer's host form one time in
+    three, else the device form at an offset of 0 to 15; the others' one time in two, else the
+    device form at an odd offset"""
+    if writer:
+        return (int(rng.integers(0, 3)) > 0, int(rng.integers(0, 16)),
+                ["exact", 0, "half"][int(rng.integers(0, 3))])
+    return bool(rng.integers(0, 2)), 2 * int(rng.integers(0, 8)) + 1, None
+
+
+def noted(verb, big, **flags):
+    """count what this case had for the verb's row of the dry run's table"""
+    row = cover.setdefault(verb, dict(cases=0, item=0, chunk=0))
+    row["cases"] += 1
+    row["chunk"] += big
+    for k, v in flags.items():
+        assert k == "item" or verb in COVER_OF[k], (verb, k)
+        row[k] = row.get(k, 0) + bool(v)
+
+
+def dev_text(data, shift):
+    import torch
+    buf = torch.zeros(len(data) + 32, dtype=torch.uint8, device="cuda")
+    dev = buf[shift:shift + len(data)]
+    if len(data):
+        dev.copy_(torch.from_numpy(data))
+    return dev
+
+
+def room_of(kind, out):
+    return len(out) if kind == "exact" else 0 if kind == 0 else len(out) // 2
+
+
+def same_arrays(got, want):
+    return len(got) == len(want) and all(
+        np.array_equal(np.asarray(g).astype(np.uint64), np.asarray(w).astype(np.uint64))
+        for g, w in zip(got, want))
+
+
+def wrote(call, data, shift, kind, want, at):
+    """a writer's device form into a sentinel-filled buffer: want is the host form's tuple, its
+    bytes at index `at`; the counts, min(out_len, room) bytes and every sentinel behind them"""
+    import torch
+    out = want[at]
+    room = room_of(kind, out)
+    buf = torch.full((len(out) + 16,), SENT, dtype=torch.uint8, device="cuda")
+    got = call(dev_text(data, shift), out=buf, out_cap=room)
+    torch.cuda.synchronize()
+    back = buf.cpu().numpy().tobytes()
+    rest = [g.cpu().numpy() for g in got[:at] + got[at + 2:]]
+    return int(got[at].item()) == len(out) and back[:room] == out[:room] and \
+        back[room:] == bytes([SENT]) * (len(back) - room) and \
+        same_arrays(rest, [np.atleast_1d(w) for w in want[:at] + want[at + 1:]])
+
+
+def range_dev(exe, data, shift, kind, want, rec_cap, sty, lead, o, c, eo, ec, inv, mx, delim):
+    """range_text's device form through the C ABI, so that the records too lie in sentinel-filled
+    memory: nothing is written at or behind min(n_ranges, rec_cap)"""
+    import torch
+    from one_amd import _lib
+    out = want[3]
+    room = room_of(kind, out)
+    buf = torch.full((len(out) + 16,), SENT, dtype=torch.uint8, device="cuda")
+    cnt = torch.full((4,), -1, dtype=torch.int64, device="cuda")
+    rec = torch.full((4, rec_cap + 2), SENT64, dtype=torch.int64, device="cuda")
+    dev = dev_text(data, shift)
+    rc = _lib.lib().redgpu_range_text_dev(
+        exe._h, sty, lead, o, c, int(eo), int(ec), int(inv), mx,
+        dev.data_ptr() if len(data) else None, len(data), delim, cnt.data_ptr(), cnt.data_ptr() + 8,
+        cnt.data_ptr() + 16, cnt.data_ptr() + 24, buf.data_ptr() if room else None, room, rec_cap,
+        rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(), rec[3].data_ptr(),
+        torch.cuda.current_stream().cuda_stream)
+    if rc != _lib.OK:
+        raise one_amd.RedExcept(_lib.lib().redgpu_last_error().decode())
+    torch.cuda.synchronize()
+    back = buf.cpu().numpy().tobytes()
+    k = min(want[1], rec_cap)
+    rows = rec.cpu().numpy().view(np.uint64)
+    return cnt.tolist() == [want[0], want[1], want[2], len(out)] and back[:room] == out[:room] and \
+        back[room:] == bytes([SENT]) * (len(back) - room) and \
+        same_arrays(list(rows[:, :k]), want[4:]) and bool((rows[:, k:] == SENT64).all())
+
+
+def counted(call, data, dev, shift, want):
+    """a verb that returns counts and arrays, host form or device form at an odd offset, against
+    that form's tuple `want`"""
+    if not dev:
+        got = call(data)
+    else:
+        import torch
+        got = call(dev_text(data, shift))
+        torch.cuda.synchronize()
+        got = [g.cpu().numpy().view(np.uint64) for g in got]
+    return same_arrays([np.atleast_1d(g) for g in got], [np.atleast_1d(w) for w in want])
+
+
+def lines_case(desc, blob, exe, cpu, data):
+    """the verbs whose item is a line's search result, each once; the failing call or None"""
+    data, delim, density = raw_text(exe, cpu, data)
+    t = TR.Text(cpu, data.tobytes(), delim)
+    most, big = int(exe.info["max_result"]), len(data) > CHUNK
+    shape = (len(data), delim, density, t.n_lines)
+    for verb in VERBS_OF["lines"]:
+        sty = int(rng.integers(1, 6))
+        lead = int(rng.integers(0, 2))
+        v = t.values(sty, lead)
+        dev, shift, kind = draw_form(verb in WRITERS)
+        if verb == "tally_text":
+            nb = draw_bins(most)
+            n_bins = most + 1 if nb is None else nb
+            prev = rng.integers(0, 1000, n_bins + 1).astype(np.uint64) if rng.random() < 1 / 3 else None
+            want = TR.tally(t, n_bins, False, sty, lead, into=prev)
+            noted(verb, big, item=(v > 0).any(), overflow=(v >= max(n_bins, 1)).any())
+            what = (verb, sty, lead, nb, prev is not None, dev, shift)
+            if not DRY:
+                def call(x):
+                    import torch
+                    into = None if prev is None else prev.copy() if not dev else \
+                        torch.from_numpy(prev.astype(np.int64)).cuda()
+                    return one_amd.tally_text(exe, x, nb, matches=False, style=sty,
+                                              do_leader=bool(lead), delim=delim, into=into)
+                ok = counted(call, data, dev, shift, want)
+        elif verb == "filter_text":
+            invert = bool(rng.integers(0, 2))
+            before, after = (int(x) for x in rng.choice([0, 1, 2, 7, 100000], 2))
+            mx = int(rng.choice([0, 1, 7, UNLIMITED]))
+            want = TR.filter(t, sty, lead, invert, before, after, mx)
+            sel = TR.selected(t, sty, lead, invert, mx)
+            merged = [1 for a, b in zip(sel, sel[1:]) if b - a >= 2 and b - before <= a + after + 1
+                      and (t.offs[a + 1] - 1) // CHUNK < t.offs[b] // CHUNK]
+            noted(verb, big, item=((v > 0) != invert).any(), merged_border=merged,
+                  truncated=dev and room_of(kind, want[3]) < len(want[3]))
+            what = (verb, sty, lead, invert, before, after, mx, dev, shift, kind)
+            if not DRY:
+                kw = dict(invert=invert, before=before, after=after, max_count=mx, delim=delim)
+                if dev:
+                    ok = wrote(lambda x, **o: one_amd.filter_text(exe, x, sty, bool(lead), **kw, **o),
+                               data, shift, kind, want, 3)
+                else:
+                    ok = one_amd.filter_text(exe, data, sty, bool(lead), **kw) == want
+        elif verb == "route_text":
+            nb = draw_bins(most, 255)
+            n_bins = min(most + 1, 255) if nb is None else nb
+            drop = bool(rng.integers(0, 2))
+            want = TR.route(t, n_bins, sty, lead, drop)
+            noted(verb, big, item=(v > 0).any(), overflow=(v >= max(n_bins, 1)).any(),
+                  truncated=dev and room_of(kind, want[4]) < len(want[4]))
+            what = (verb, sty, lead, nb, drop, dev, shift, kind)
+            if not DRY:
+                if dev:
+                    ok = wrote(lambda x, **o: one_amd.route_text(exe, x, nb, sty, bool(lead),
+                                                                 drop_unmatched=drop, delim=delim, **o),
+                               data, shift, kind, want, 4)
+                else:
+                    got = one_amd.route_text(exe, data, nb, sty, bool(lead), drop_unmatched=drop,
+                                             delim=delim)
+                    ok = got[:2] == want[:2] and got[4] == want[4] and same_arrays(got[2:4], want[2:4])
+        elif verb == "range_text":
+            # the two most frequent positive results of this text (1 where there is none), both
+            # ways round, the toggle form, or one that the text does not have
+            seen = np.bincount(v[v > 0])
+            top = [int(r) for r in np.argsort(-seen, kind="stable")[:2] if seen[r]] or [1]
+            k = int(rng.integers(0, 4))
+            o, c = top[0], top[-1]
+            if k == 1:
+                o, c = c, o
+            elif k == 2:
+                c = o
+            elif k == 3:
+                o, c = (most + 1, c) if rng.integers(0, 2) else (o, most + 1)
+            eo, ec, inv = (bool(x) for x in rng.integers(0, 2, 3))
+            mx = int(rng.choice([0, 1, 3, UNLIMITED]))
+            x = TR.range_expect(t, o, c, sty, lead, eo, ec, inv, mx)
+            rec_cap = [0, 2, x.n_ranges + 2][int(rng.integers(0, 3))]
+            want = TR.range(t, o, c, sty, lead, eo, ec, inv, mx, rec_cap)
+            noted(verb, big, item=(v == o).any(),
+                  range_border=(x.begin // CHUNK < (x.end - 1) // CHUNK).any(),
+                  truncated=dev and room_of(kind, want[3]) < len(want[3]))
+            what = (verb, sty, lead, o, c, eo, ec, inv, mx, rec_cap, dev, shift, kind)
+            if not DRY:
+                if dev:
+                    ok = range_dev(exe, data, shift, kind, want, rec_cap, sty, lead, o, c, eo, ec,
+                                   inv, mx, delim)
+                else:
+                    got = one_amd.range_text(exe, data, o, c, sty, bool(lead), emit_open=eo,
+                                             emit_close=ec, invert=inv, max_ranges=mx, delim=delim,
+                                             rec_cap=rec_cap)
+                    ok = got[:4] == want[:4] and same_arrays(got[4:], want[4:])
+        else:
+            want = TR.uniq(t, False, sty, lead)
+            n = len(want[3])
+            md = max(1, n) + [0, 1, 100][int(rng.integers(0, 3))]
+            noted(verb, big, item=(v > 0).any())
+            what = (verb, sty, lead, md, dev, shift)
+            if not DRY:
+                def call(x):
+                    return one_amd.uniq_text(exe, x, matches=False, style=sty, do_leader=bool(lead),
+                                             delim=delim, max_distinct=md,
+                                             **(dict(cap=n) if dev else {}))
+                # (the device form reports n_distinct too, and writes cap = n rows)
+                ok = counted(call, data, dev, shift, want[:3] + (n,) + want[3:] if dev else want)
+        if DRY:
+            continue
+        kern = one_amd.last_kernel()
+        stats[kern] = stats.get(kern, 0) + 1
+        if not ok:
+            return what + shape + (kern,)
+    return None
+
+
+def pieces_case(desc, blob, exe, cpu, data):
+    """the verbs whose items come from collect's chain, each once; the failing call or None"""
+    data, delim, density = raw_text(exe, cpu, data)
+    t = TR.Text(cpu, data.tobytes(), delim)
+    most, big = int(exe.info["max_result"]), len(data) > CHUNK
+    shape = (len(data), delim, density, t.n_lines)
+    has = any(t.pieces())
+    for verb in VERBS_OF["pieces"]:
+        dev, shift, kind = draw_form(verb in WRITERS)
+        per = int(rng.choice([0, 1, 3, UNLIMITED]))
+        got = t.items(per)
+        loose = any(it[3] < it[2] for it in got)
+        if verb == "tally_text":
+            nb = draw_bins(most)
+            n_bins = most + 1 if nb is None else nb
+            prev = rng.integers(0, 1000, n_bins + 1).astype(np.uint64) if rng.random() < 1 / 3 else None
+            want = TR.tally(t, n_bins, True, into=prev)
+            noted(verb, big, item=has, overflow=any(it[1] >= n_bins for it in t.items()))
+            what = (verb, nb, prev is not None, dev, shift)
+            if not DRY:
+                def call(x):
+                    import torch
+                    into = None if prev is None else prev.copy() if not dev else \
+                        torch.from_numpy(prev.astype(np.int64)).cuda()
+                    return one_amd.tally_text(exe, x, nb, matches=True, delim=delim, into=into)
+                ok = counted(call, data, dev, shift, want)
+        elif verb == "extract_text":
+            want = TR.extract(t, per)
+            noted(verb, big, item=has, loose=loose,
+                  piece64=any(it[4] - it[3] >= 64 for it in got),
+                  truncated=dev and room_of(kind, want[2]) < len(want[2]))
+            what = (verb, per, dev, shift, kind)
+            if not DRY:
+                if dev:
+                    ok = wrote(lambda x, **o: one_amd.extract_text(exe, x, max_per_line=per,
+                                                                   delim=delim, **o),
+                               data, shift, kind, want, 2)
+                else:
+                    ok = one_amd.extract_text(exe, data, max_per_line=per, delim=delim) == want
+        elif verb == "uniq_text":
+            want = TR.uniq(t, True, max_per_line=per)
+            n = len(want[3])
+            md = max(1, n) + [0, 1, 100][int(rng.integers(0, 3))]
+            noted(verb, big, item=has, loose=loose)
+            what = (verb, per, md, dev, shift)
+            if not DRY:
+                def call(x):
+                    return one_amd.uniq_text(exe, x, matches=True, max_per_line=per, delim=delim,
+                                             max_distinct=md, **(dict(cap=n) if dev else {}))
+                ok = counted(call, data, dev, shift, want[:3] + (n,) + want[3:] if dev else want)
+        elif verb == "sum_text":
+            which = ["first", "last"][int(rng.integers(0, 2))]
+            nb = draw_bins(most)
+            n_bins = most + 1 if nb is None else nb
+            prev = None
+            if rng.random() < 1 / 3:        # an earlier table: small counts, sums that wrap
+                prev = np.stack([rng.integers(0, 1000, n_bins + 1).astype(np.uint64)] +
+                                [rng.integers(0, 1 << 64, n_bins + 1, dtype=np.uint64)
+                                 for _ in range(3)])
+            want = TR.sum(t, n_bins, which, per, into=prev)
+            parts = [t.piece_bytes(it) for it in got]
+            noted(verb, big, item=has, loose=loose, numeric=want[2] > 0,
+                  overflow=any(it[1] >= n_bins for it in got),
+                  over64bit=any(TR.number(p, which == "last") is None and any(48 <= b <= 57 for b in p)
+                                for p in parts))
+            what = (verb, which, per, nb, prev is not None, dev, shift)
+            if not DRY:
+                def call(x):
+                    import torch
+                    into = None if prev is None else prev.copy() if not dev else \
+                        torch.from_numpy(prev.view(np.int64).copy()).cuda()
+                    return one_amd.sum_text(exe, x, nb, which=which, max_per_line=per, delim=delim,
+                                            into=into)
+                ok = counted(call, data, dev, shift, want)
+        else:
+            k = int(rng.integers(0, 5))
+            fields = ["1", "1,3", "2-", "64-", None][k]
+            if fields is None:              # a random 64-bit mask, as a cut-style list
+                mask = int(rng.integers(1, 1 << 63)) | int(rng.integers(0, 2)) << 63
+                fields = ",".join(["%d" % (b + 1) for b in range(63) if mask >> b & 1] +
+                                  ["64-"] * (mask >> 63))
+            sep = rng.integers(0, 256, int(rng.choice([0, 1, 3, 8])), dtype=np.uint8).tobytes()
+            max_fields = int(rng.choice([0, 1, 2, 5]))
+            only = bool(rng.integers(0, 2))
+            want = TR.fields(t, fields_mask(fields), sep, max_fields, only)
+            cut = t.items(max_fields - 1 if max_fields else UNLIMITED)
+            noted(verb, big, item=has, loose=any(it[3] < it[2] for it in cut),
+                  piece64=any(it[4] - it[3] >= 64 for it in cut),
+                  truncated=dev and room_of(kind, want[3]) < len(want[3]))
+            what = (verb, fields, sep, max_fields, only, dev, shift, kind)
+            if not DRY:
+                kw = dict(sep=sep, max_fields=max_fields, only_delimited=only, delim=delim)
+                if dev:
+                    ok = wrote(lambda x, **o: one_amd.fields_text(exe, x, fields, **kw, **o),
+                               data, shift, kind, want, 3)
+                else:
+                    ok = one_amd.fields_text(exe, data, fields, **kw) == want
+        if DRY:
+            continue
+        kern = one_amd.last_kernel()
+        stats[kern] = stats.get(kern, 0) + 1
+        if not ok:
+            return what + shape + (kern,)
+    return None
+
+
 t0 = time.time()
 stats = {}
 for case in range(cases):
-    name, blob = make_dfa()
+    name, blob = make_dfa_wide() if NEWER else make_dfa()
     if LONG:
         shape, nbytes = {}, int(rng.integers(2048, 128 * 1024 + 1))
     elif TEXT:
         shape, nbytes = {}, int(rng.integers(0, 96 * 1024 + 1))
+    elif NEWER:                                # one case in twenty is the empty text
+        shape, nbytes = {}, 0 if rng.random() < 0.05 else int(rng.integers(0, 96 * 1024 + 1))
     else:
         shape, nbytes = make_lines()
-    data = make_data(nbytes, name)
+    data = make_data_wide(nbytes, name) if NEWER else make_data(nbytes, name)
     flags = {}
     for f, p in ((("force_generic", 0.05), ("no_bucketing", 0.3), ("force_stream", 0.5)) if CLS_BIAS else
                  (("force_generic", 0.05), ("force_global", 0.0), ("force_hot", 0.8),
@@ -330,15 +758,16 @@ for case in range(cases):
     if rng.random() < 0.3 and not CLS_BIAS:
         flags["lds_table_max"] = int(rng.choice([8 * 256, 40 * 256, 100 * 256, 20000, 70000]))
     try:
-        exe = one_amd.Executable(blob, **flags)
+        exe = one_amd.Executable(blob, **(dict(device="none") if DRY else {}), **flags)
     except one_amd.RedExcept as e:
         print("create refused:", name, flags, e)
         continue
     cpu = O.CpuOracle(blob)
     desc = (case, name, {k: (v if not hasattr(v, "shape") else "offsets[%d]" % (len(v) - 1)) for k, v in shape.items()}, flags, exe.info["table_kind"])
-    if LONG or TEXT:
+    if LONG or TEXT or NEWER:
         try:
-            bad = (long_case if LONG else text_case)(desc, blob, exe, cpu, data)
+            bad = (long_case if LONG else text_case if TEXT else lines_case if LINES else
+                   pieces_case)(desc, blob, exe, cpu, data)
         except one_amd.RedExcept as e:
             print("ERROR", desc, e)
             sys.exit(1)
@@ -419,4 +848,8 @@ for case in range(cases):
             sys.exit(1)
     if case % 25 == 0:
         print("case", case, "%.0fs" % (time.time() - t0), flush=True)
-print("fuzz ok:", cases, "cases; kernels:", dict(sorted(stats.items())))
+if NEWER:       # what the oracle's side of the cases held, per verb (see the docstring)
+    for verb in VERBS_OF[sys.argv[3]]:
+        print("cover", sys.argv[3], verb, " ".join("%s=%d" % kv for kv in cover.get(verb, {}).items()))
+    print("special", sys.argv[3], " ".join("%s=%d" % kv for kv in special.items()))
+print("fuzz dry:" if DRY else "fuzz ok:", cases, "cases; kernels:", dict(sorted(stats.items())))

@@ -1672,7 +1672,8 @@ def test_stateful_matcher_on_gpu():
     assert np.array_equal(res3.cpu().numpy(), exp3)
 
 
-@pytest.mark.parametrize("mode", ["general", "hot", "cls", "long", "lists", "blocks", "text"])
+@pytest.mark.parametrize("mode", ["general", "hot", "cls", "long", "lists", "blocks", "text",
+                                  "lines", "pieces"])
 def test_differential_fuzz_smoke(mode):
     """scripts/fuzz_gpu.py (random DFAs x line shapes x verbs x styles x placement / kernel flags
     vs the oracle), a short fixed-seed run of each bias; the open-ended campaign is run by hand."""
