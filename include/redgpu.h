@@ -1147,9 +1147,13 @@ int redgpu_diag_walked_dev(const redgpu_dfa *dfa, int do_leader, const uint8_t *
  * call).  They - and the thread's launch scratch - are released when the thread exits; a
  * long-lived thread that is done with the library may release them early.
  * redgpu_scratch_entries: launch scratch buffers currently cached by all threads together
- * (bounded per thread; diagnostics / tests). */
+ * (bounded per thread; diagnostics / tests).
+ * redgpu_host_pins_held: over the calling thread's stages, the registrations made for a call that
+ * are not yet released plus the downloads not yet copied into the caller's buffers - 0 whenever a
+ * host-buffer entry point has returned (diagnostics / tests). */
 void redgpu_thread_release(void);
 uint64_t redgpu_scratch_entries(void);
+uint64_t redgpu_host_pins_held(void);
 /* Diagnostics: how the host-buffer entry points have moved caller memory so far, transfers by
  * route - [0] memory the caller pinned, [1] through the calling thread's pinned arena (calls that
  * upload < 8 MiB), [2] registered for the duration of the call, [3] handed to the runtime

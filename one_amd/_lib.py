@@ -262,6 +262,8 @@ def lib() -> C.CDLL:
         l.redgpu_host_unregister.argtypes = [vp]
         l.redgpu_thread_release.restype = None
         l.redgpu_scratch_entries.restype = u64
+        l.redgpu_host_pins_held.restype = u64
+        l.redgpu_host_pins_held.argtypes = []
         l.redgpu_host_route_counts.restype = None
         l.redgpu_host_route_counts.argtypes = [vp]
         l.redgpu_group_create.restype = C.c_int

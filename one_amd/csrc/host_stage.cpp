@@ -218,8 +218,12 @@ void HostStage::flush(int idx) {
   pending_.resize(keep);
   keep = 0;
   for (size_t i = 0; i < tempPins_.size(); ++i) {
-    if (idx < 0 || tempPins_[i].idx == idx) (void)hipHostUnregister(tempPins_[i].p);
-    else tempPins_[keep++] = tempPins_[i];
+    if (idx < 0 || tempPins_[i].idx == idx) {
+      // (a release the runtime refuses must not stay behind as the thread's last error)
+      if (hipHostUnregister(tempPins_[i].p) != hipSuccess) (void)hipGetLastError();
+    } else {
+      tempPins_[keep++] = tempPins_[i];
+    }
   }
   tempPins_.resize(keep);
 }
@@ -236,11 +240,21 @@ bool isPinnedHost(const void *p) {
 }
 
 bool HostStage::pinForCall(const void *p, size_t bytes, int idx) {
+  // A buffer that goes up and comes back in one call (advance_batch's states) is registered
+  // already: asking again would register the pages a second time, and the second release then
+  // fails and leaves its error for the next call's launch check to find.  Pages this call holds
+  // on the same stream are taken as they are; any other overlap goes through the arena.
+  const uint8_t *lo = static_cast<const uint8_t *>(p), *hi = lo + bytes;
+  for (const TempPin &t : tempPins_) {
+    const uint8_t *tlo = static_cast<const uint8_t *>(t.p), *thi = tlo + t.bytes;
+    if (hi <= tlo || thi <= lo) continue;
+    return t.idx == idx && tlo <= lo && hi <= thi;
+  }
   if (hipHostRegister(const_cast<void *>(p), bytes, hipHostRegisterDefault) != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
-  tempPins_.push_back(TempPin{const_cast<void *>(p), idx});
+  tempPins_.push_back(TempPin{const_cast<void *>(p), bytes, idx});
   return true;
 }
 
@@ -298,41 +312,38 @@ hipError_t HostStage::move(void *dev, void *host, size_t bytes, int idx, bool di
     return toDevice ? hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s)
                     : hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s);
   };
-  // through the arena, in pieces the arena can hold (bounceTake waits and starts over when full)
-  auto bounced = [&](uint8_t *d, uint8_t *h, size_t n) -> hipError_t {
-    constexpr size_t kPiece = size_t(4) << 20;
-    for (size_t at = 0; at < n; at += kPiece) {
-      const size_t m = n - at < kPiece ? n - at : kPiece;
-      void *p = bounceTake(m);
-      if (!p) return hipErrorOutOfMemory;
-      hipError_t e;
-      if (toDevice) {
-        memcpy(p, h + at, m);
-        e = hipMemcpyAsync(d + at, p, m, hipMemcpyHostToDevice, s);
-      } else {
-        e = hipMemcpyAsync(p, d + at, m, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) pending_.push_back(Pending{h + at, p, m, idx});
-      }
-      if (e != hipSuccess) return e;
+  // one piece through the arena (bounceTake waits and starts over when the arena is full)
+  auto bounced = [&](uint8_t *d, uint8_t *h, size_t m) -> hipError_t {
+    void *p = bounceTake(m);
+    if (!p) return hipErrorOutOfMemory;
+    hipError_t e;
+    if (toDevice) {
+      memcpy(p, h, m);
+      e = hipMemcpyAsync(d, p, m, hipMemcpyHostToDevice, s);
+    } else {
+      e = hipMemcpyAsync(p, d, m, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) pending_.push_back(Pending{h, p, m, idx});
     }
-    return hipSuccess;
+    return e;
   };
   uint8_t *d8 = static_cast<uint8_t *>(dev), *h8 = static_cast<uint8_t *>(host);
-  if (!direct && !callDirect_ && bytes <= kBounceMax) { ++gRoute[1]; return bounced(d8, h8, bytes); }
-  if (direct || (isPinnedHost(h8) && isPinnedHost(h8 + bytes - 1))) { ++gRoute[0]; return plain(dev, host, bytes); }
-  constexpr uintptr_t kPage = 4096;
+  // the decision is stagePlan's (host_stage_plan.h); the runtime is only asked what the plan
+  // depends on: pinnedness where the transfer does not go through the arena anyway, and the
+  // registration itself - refused, the plan is made again without it
   const uintptr_t a = reinterpret_cast<uintptr_t>(h8);
-  const uintptr_t lo = (a + kPage - 1) & ~(kPage - 1), hi = (a + bytes) & ~(kPage - 1);
-  if (hi > lo && hi - lo >= 16 * kPage && pinForCall(reinterpret_cast<void *>(lo), hi - lo, idx)) {
-    ++gRoute[2];
-    const size_t head = lo - a, tail = a + bytes - hi;
-    hipError_t e = plain(d8 + head, reinterpret_cast<void *>(lo), hi - lo);
-    if (e == hipSuccess && head) e = bounced(d8, h8, head);
-    if (e == hipSuccess && tail) e = bounced(d8 + (bytes - tail), h8 + (bytes - tail), tail);
-    return e;
+  const bool arena = !direct && !callDirect_ && bytes <= kBounceMax;
+  const bool pinned = !arena && !direct && isPinnedHost(h8) && isPinnedHost(h8 + bytes - 1);
+  StagePlan plan = stagePlan(a, bytes, callDirect_, direct, pinned, true);
+  if (plan.route == kRouteRegistered &&
+      !pinForCall(h8 + plan.segs[0].offset, plan.segs[0].bytes, idx))
+    plan = stagePlan(a, bytes, callDirect_, direct, pinned, false);
+  ++gRoute[plan.route];
+  for (const StageSegment &g : plan.segs) {
+    const hipError_t e = g.bounced ? bounced(d8 + g.offset, h8 + g.offset, g.bytes)
+                                   : plain(d8 + g.offset, h8 + g.offset, g.bytes);
+    if (e != hipSuccess) return e;
   }
-  ++gRoute[1];
-  return bounced(d8, h8, bytes);
+  return hipSuccess;
 }
 
 hipError_t HostStage::copyIn(void *dDst, const void *hSrc, size_t bytes, int idx, bool direct) {
@@ -400,6 +411,12 @@ hipError_t hostStage(int device, HostStage **out) {
   *out = st.get();
   tlsStages.v.push_back(std::move(st));
   return hipSuccess;
+}
+
+size_t hostStageHeld() {
+  size_t held = 0;
+  for (auto &s : tlsStages.v) held += s->held();
+  return held;
 }
 
 void hostStageReleaseThread() {

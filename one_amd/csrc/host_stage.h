@@ -16,6 +16,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "host_stage_plan.h"
+
 namespace redgpu {
 
 class HostStage {
@@ -48,8 +50,9 @@ class HostStage {
   // why) - so the runtime's own on-the-fly path is never taken.  A range the runtime refuses to
   // register goes through the arena in pieces.
   // copyOut()'s bytes are in the caller's buffer after syncStream(idx) / sync().
-  static constexpr size_t kBounceMax = size_t(16) << 20;
-  static constexpr size_t kDirectFrom = size_t(8) << 20;
+  // (the thresholds and the decision itself: host_stage_plan.h)
+  static constexpr size_t kBounceMax = kStageBounceMax;
+  static constexpr size_t kDirectFrom = kStageDirectFrom;
   hipError_t copyIn(void *dDst, const void *hSrc, size_t bytes, int idx, bool direct = false);
   hipError_t copyOut(void *hDst, const void *dSrc, size_t bytes, int idx, bool direct = false);
   hipError_t syncStream(int idx);
@@ -67,9 +70,15 @@ class HostStage {
   bool pinForCall(const void *p, size_t bytes, int idx);
   struct TempPin {
     void *p;
+    size_t bytes;
     int idx;
   };
   std::vector<TempPin> tempPins_;
+ public:
+  // temporary registrations not yet released + downloads not yet flushed (redgpu_host_pins_held)
+  size_t held() const { return tempPins_.size() + pending_.size(); }
+
+ private:
   void flush(int idx);  // the finished downloads of stream idx (-1: all) into the caller's buffers
   bool callDirect_ = false;
   void *bounce_ = nullptr;
@@ -97,6 +106,9 @@ void hostRouteCounts(uint64_t out[4]);
 
 // The calling thread's stage for `device` (created on first use; the device must be current).
 hipError_t hostStage(int device, HostStage **out);
+// Temporary registrations not yet released plus downloads not yet flushed, over the calling
+// thread's stages: 0 once a host-buffer call has returned.
+size_t hostStageHeld();
 // Frees every stage the calling thread holds.
 void hostStageReleaseThread();
 

@@ -343,34 +343,7 @@ k_rebase(const uint64_t *in, uint64_t n1, uint64_t base, uint64_t *out) {
     out[i] = in[i] - base;
 }
 
-// chunk plan of a host-buffer batch: cuts[c] .. cuts[c + 1] are the lines of chunk c
-std::vector<uint64_t> chunkCuts(const uint64_t *offsets, uint64_t stride, uint64_t n,
-                                uint64_t total, uint64_t chunkBytes) {
-  std::vector<uint64_t> cuts{0};
-  const uint64_t base0 = offsets ? offsets[0] : 0;
-  if (total - base0 > 2 * chunkBytes && n >= 4096) {
-    if (!offsets) {
-      uint64_t per = (chunkBytes / (stride ? stride : 1)) & ~uint64_t(1023);
-      if (per < 1024) per = 1024;
-      for (uint64_t lo = per; lo < n; lo += per) cuts.push_back(lo);
-    } else {
-      uint64_t lo = 0;
-      while (lo < n) {
-        // first line whose start is >= chunkBytes past this chunk's start
-        const uint64_t target = offsets[lo] + chunkBytes;
-        uint64_t a = lo + 1, b = n;
-        while (a < b) {
-          const uint64_t mid = (a + b) / 2;
-          if (offsets[mid] >= target) b = mid; else a = mid + 1;
-        }
-        lo = a;
-        if (lo < n) cuts.push_back(lo);
-      }
-    }
-  }
-  cuts.push_back(n);
-  return cuts;
-}
+// (the chunk plan of a host-buffer batch, chunkCuts: host_stage_plan.h)
 
 // host-buffer form: the batch is cut into chunks of ~32 MiB of input that alternate between the
 // thread's two private streams - copy in, kernel, copy out per chunk - so that with pinned
@@ -2085,6 +2058,8 @@ void redgpu_host_route_counts(uint64_t counts[4]) { if (counts) hostRouteCounts(
 
 uint64_t redgpu_scratch_entries(void) { return scratchEntries(); }
 
+uint64_t redgpu_host_pins_held(void) { return hostStageHeld(); }
+
 int redgpu_dfa_tune_dev(redgpu_dfa *dfa, const uint8_t *data, const uint64_t *offsets,
                         uint64_t stride, uint64_t n, void *stream) {
   if (int rc = checkHandle(dfa)) return rc;
@@ -2148,9 +2123,10 @@ int redgpu_dfa_tune(redgpu_dfa *dfa, const uint8_t *data, const uint64_t *offset
   uint64_t *dOff = offsets ? call.buf<uint64_t>(kSlOff, n + 1, "offsets") : nullptr;
   if (offsets) call.upload(dOff, offsets, n + 1, "offsets");
   call.upload(dData, data, total, "data");
-  // (tune_dev synchronises)
+  // tune_dev returns early for a fused u8 table, with the uploads still in flight: like every
+  // host form, drain the stream and release the call's registrations on every path
   call.run([&] { return redgpu_dfa_tune_dev(dfa, dData, dOff, stride, n, call.stream()); });
-  return call.rc();
+  return call.wait();
 }
 
 int redgpu_advance_batch_dev(const redgpu_dfa *dfa, const uint8_t *data, const uint64_t *offsets,

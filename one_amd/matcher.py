@@ -1683,3 +1683,62 @@ def match(exe, text: bytes, style, do_leader=True):
 def search(exe, text: bytes, style, do_leader=True):
     r, s, e = search_batch(exe, text, style, do_leader, offsets=[0, len(text)])
     return int(r[0]), int(s[0]), int(e[0])
+
+
+# the host-buffer staging: caller-pinned memory and the diagnostics of include/redgpu.h ----------
+
+def _span(buf, nbytes):
+    """(address, bytes) of a numpy array, or of a plain address with nbytes"""
+    if isinstance(buf, np.ndarray):
+        if not buf.flags.c_contiguous:
+            raise RedExceptApi("a buffer to pin must be contiguous")
+        return buf.ctypes.data, buf.nbytes if nbytes is None else int(nbytes)
+    return buf, 0 if nbytes is None else int(nbytes)
+
+
+def host_register(buf, nbytes=None) -> int:
+    """redgpu_host_register: pin caller memory (a contiguous numpy array, or an address with
+    nbytes) so that the host-buffer forms copy it as it is.  Returns the C-ABI's code, REDGPU_OK
+    or an error (nothing is raised: the refusals are part of the interface)."""
+    p, n = _span(buf, nbytes)
+    return int(_lib.lib().redgpu_host_register(p, n))
+
+
+def host_unregister(buf) -> int:
+    """redgpu_host_unregister of what host_register pinned; returns the C-ABI's code."""
+    p, _ = _span(buf, None)
+    return int(_lib.lib().redgpu_host_unregister(p))
+
+
+class pinned_host:
+    """with pinned_host(array): the array's bytes are registered inside the block"""
+
+    def __init__(self, buf):
+        self.buf = buf
+
+    def __enter__(self):
+        _check(host_register(self.buf))
+        return self.buf
+
+    def __exit__(self, *exc):
+        _check(host_unregister(self.buf))
+        return False
+
+
+def host_route_counts():
+    """redgpu_host_route_counts: transfers of caller memory so far, process-wide, by route -
+    (caller-pinned, through a pinned arena, registered for the call, handed over pageable)"""
+    c = (C.c_uint64 * 4)()
+    _lib.lib().redgpu_host_route_counts(c)
+    return tuple(int(v) for v in c)
+
+
+def host_pins_held() -> int:
+    """redgpu_host_pins_held: the calling thread's registrations not yet released plus its
+    downloads not yet flushed - 0 whenever a host-buffer form has returned"""
+    return int(_lib.lib().redgpu_host_pins_held())
+
+
+def thread_release() -> None:
+    """redgpu_thread_release: free the calling thread's staging (streams, buffers, arena)"""
+    _lib.lib().redgpu_thread_release()
