@@ -69,6 +69,22 @@ inline void throwOnError(int rc) {
   }
 }
 
+namespace detail {
+// a size_t limit (SIZE_MAX = none) as the uint64_t count of the C calls
+inline uint64_t clampCount(size_t n) { return n > (1ull << 62) ? 1ull << 62 : uint64_t(n); }
+
+// `out` of a verb that assembles a text: call(out, cap) makes the C call with that output, which
+// leaves out_len in outLen.  A first call with (nullptr, 0) only sizes; the second one fetches, when
+// there are bytes or alsoFetch() - asked once, behind the first call - has something of its own.
+template <class F, class G = bool (*)()>
+void sizedText(std::string &out, const uint64_t &outLen, F &&call,
+               G alsoFetch = [] { return false; }) {
+  call(nullptr, 0);
+  out.resize(size_t(outLen));
+  if (alsoFetch() || outLen) call(reinterpret_cast<Byte *>(out.data()), outLen);
+}
+}  // namespace detail
+
 // tag types kept for source compatibility (include/Types.h:43-53); every constructor COPIES
 struct CopyTag {};
 constexpr CopyTag gCopyTag;
@@ -300,7 +316,7 @@ struct SumStats {
 inline SumStats sumText(const Executable &exec, std::string_view text, size_t nBins,
                         bool last = false, size_t maxPerLine = SIZE_MAX, char delim = '\n') {
   const size_t slots = nBins + 1;
-  const uint64_t most = maxPerLine > (uint64_t(1) << 62) ? uint64_t(1) << 62 : uint64_t(maxPerLine);
+  const uint64_t most = detail::clampCount(maxPerLine);
   std::vector<uint64_t> stats(4 * slots);
   SumStats out;
   throwOnError(redgpu_sum_text(exec.handle(), last ? REDGPU_SUM_LAST : REDGPU_SUM_FIRST,
@@ -361,16 +377,12 @@ inline size_t replaceText(const Executable &exec, Style style, bool doLeader,
                           size_t max = SIZE_MAX, bool onlyChanged = false, char delim = '\n') {
   const Byte *p = reinterpret_cast<const Byte *>(text.data());
   const Byte *r = reinterpret_cast<const Byte *>(repl.data());
-  const uint64_t most = max > (uint64_t(1) << 62) ? uint64_t(1) << 62 : uint64_t(max);
   uint64_t made = 0, outLen = 0;
-  throwOnError(redgpu_replace_text(exec.handle(), style, doLeader, onlyChanged, p, text.size(),
-                                   Byte(delim), r, repl.size(), most, nullptr, &made, &outLen,
-                                   nullptr, 0));
-  out.resize(size_t(outLen));
-  if (outLen)
+  detail::sizedText(out, outLen, [&](Byte *o, uint64_t cap) {
     throwOnError(redgpu_replace_text(exec.handle(), style, doLeader, onlyChanged, p, text.size(),
-                                     Byte(delim), r, repl.size(), most, nullptr, &made, &outLen,
-                                     reinterpret_cast<Byte *>(out.data()), outLen));
+                                     Byte(delim), r, repl.size(), detail::clampCount(max), nullptr,
+                                     &made, &outLen, o, cap));
+  });
   return size_t(made);
 }
 
@@ -384,16 +396,12 @@ inline size_t filterText(const Executable &exec, Style style, bool doLeader, std
                          size_t after = 0, size_t most = SIZE_MAX, char delim = '\n',
                          size_t *emitted = nullptr) {
   const Byte *p = reinterpret_cast<const Byte *>(text.data());
-  const uint64_t cnt = most > (uint64_t(1) << 62) ? uint64_t(1) << 62 : uint64_t(most);
   uint64_t selected = 0, lines = 0, outLen = 0;
-  throwOnError(redgpu_filter_text(exec.handle(), style, doLeader, invert, before, after, cnt, p,
-                                  text.size(), Byte(delim), nullptr, &selected, &lines, &outLen,
-                                  nullptr, 0));
-  out.resize(size_t(outLen));
-  if (outLen)
-    throwOnError(redgpu_filter_text(exec.handle(), style, doLeader, invert, before, after, cnt, p,
-                                    text.size(), Byte(delim), nullptr, &selected, &lines, &outLen,
-                                    reinterpret_cast<Byte *>(out.data()), outLen));
+  detail::sizedText(out, outLen, [&](Byte *o, uint64_t cap) {
+    throwOnError(redgpu_filter_text(exec.handle(), style, doLeader, invert, before, after,
+                                    detail::clampCount(most), p, text.size(), Byte(delim), nullptr,
+                                    &selected, &lines, &outLen, o, cap));
+  });
   if (emitted) *emitted = size_t(lines);
   return size_t(selected);
 }
@@ -414,15 +422,11 @@ inline size_t routeText(const Executable &exec, Style style, bool doLeader, std:
   binLines.assign(nBins + 1, 0);
   binOffsets.assign(nBins + 2, 0);
   uint64_t found = 0, routed = 0, outLen = 0;
-  throwOnError(redgpu_route_text(exec.handle(), style, doLeader, dropUnmatched, p, text.size(),
-                                 Byte(delim), nBins, &found, &routed, binLines.data(),
-                                 binOffsets.data(), &outLen, nullptr, 0));
-  out.resize(size_t(outLen));
-  if (outLen)
+  detail::sizedText(out, outLen, [&](Byte *o, uint64_t cap) {
     throwOnError(redgpu_route_text(exec.handle(), style, doLeader, dropUnmatched, p, text.size(),
                                    Byte(delim), nBins, &found, &routed, binLines.data(),
-                                   binOffsets.data(), &outLen,
-                                   reinterpret_cast<Byte *>(out.data()), outLen));
+                                   binOffsets.data(), &outLen, o, cap));
+  });
   if (lines) *lines = size_t(found);
   return size_t(routed);
 }
@@ -447,23 +451,19 @@ inline size_t rangeText(const Executable &exec, Style style, bool doLeader, std:
                         size_t most = SIZE_MAX, char delim = '\n',
                         std::vector<TextRange> *ranges = nullptr, size_t *emitted = nullptr) {
   const Byte *p = reinterpret_cast<const Byte *>(text.data());
-  const uint64_t cnt = most > (uint64_t(1) << 62) ? uint64_t(1) << 62 : uint64_t(most);
-  uint64_t found = 0, lines = 0, outLen = 0;
-  throwOnError(redgpu_range_text(exec.handle(), style, doLeader, openResult, closeResult, emitOpen,
-                                 emitClose, invert, cnt, p, text.size(), Byte(delim), nullptr,
-                                 &found, &lines, &outLen, nullptr, 0, 0, nullptr, nullptr, nullptr,
-                                 nullptr));
-  out.resize(size_t(outLen));
-  std::vector<uint64_t> rec(ranges ? size_t(found) * 4 : 0);
-  uint64_t *r = rec.empty() ? nullptr : rec.data();
-  const uint64_t n = rec.size() / 4;
-  if (outLen || n)
+  uint64_t found = 0, lines = 0, outLen = 0, n = 0;
+  std::vector<uint64_t> rec;  // the four columns, n each: sized behind the first call
+  detail::sizedText(out, outLen, [&](Byte *o, uint64_t cap) {
+    uint64_t *r = n ? rec.data() : nullptr;
     throwOnError(redgpu_range_text(exec.handle(), style, doLeader, openResult, closeResult,
-                                   emitOpen, emitClose, invert, cnt, p, text.size(), Byte(delim),
-                                   nullptr, &found, &lines, &outLen,
-                                   reinterpret_cast<Byte *>(out.data()), outLen, n, r,
-                                   r ? r + n : nullptr, r ? r + 2 * n : nullptr,
+                                   emitOpen, emitClose, invert, detail::clampCount(most), p,
+                                   text.size(), Byte(delim), nullptr, &found, &lines, &outLen, o,
+                                   cap, n, r, r ? r + n : nullptr, r ? r + 2 * n : nullptr,
                                    r ? r + 3 * n : nullptr));
+  }, [&] {
+    rec.resize(ranges ? size_t(found) * 4 : 0);
+    return (n = rec.size() / 4) != 0;
+  });
   if (ranges) {
     ranges->clear();
     for (uint64_t i = 0; i < n; ++i)
@@ -483,14 +483,12 @@ inline size_t extractText(const Executable &exec, std::string_view text, std::st
                           size_t maxPerLine = SIZE_MAX, char delim = '\n',
                           size_t *lines = nullptr) {
   const Byte *p = reinterpret_cast<const Byte *>(text.data());
-  const uint64_t most = maxPerLine > (uint64_t(1) << 62) ? uint64_t(1) << 62 : uint64_t(maxPerLine);
   uint64_t found = 0, nLines = 0, outLen = 0;
-  throwOnError(redgpu_extract_text(exec.handle(), p, text.size(), Byte(delim), most, &nLines,
-                                   &found, &outLen, nullptr, 0));
-  out.resize(size_t(outLen));
-  if (outLen)
-    throwOnError(redgpu_extract_text(exec.handle(), p, text.size(), Byte(delim), most, &nLines,
-                                     &found, &outLen, reinterpret_cast<Byte *>(out.data()), outLen));
+  detail::sizedText(out, outLen, [&](Byte *o, uint64_t cap) {
+    throwOnError(redgpu_extract_text(exec.handle(), p, text.size(), Byte(delim),
+                                     detail::clampCount(maxPerLine), &nLines, &found, &outLen, o,
+                                     cap));
+  });
   if (lines) *lines = size_t(nLines);
   return size_t(found);
 }
@@ -511,14 +509,11 @@ inline size_t fieldsText(const Executable &exec, std::string_view text, uint64_t
   for (size_t i = 0; i < sep.size(); ++i) sepWord |= uint64_t(Byte(sep[i])) << (8 * i);
   const uint32_t sepLen = uint32_t(sep.size());
   uint64_t nLines = 0, emitted = 0, nFields = 0, outLen = 0;
-  throwOnError(redgpu_fields_text(exec.handle(), p, text.size(), Byte(delim), select, maxFields,
-                                  onlyDelimited, sepWord, sepLen, &nLines, &emitted, &nFields,
-                                  &outLen, nullptr, 0));
-  out.resize(size_t(outLen));
-  if (outLen)
+  detail::sizedText(out, outLen, [&](Byte *o, uint64_t cap) {
     throwOnError(redgpu_fields_text(exec.handle(), p, text.size(), Byte(delim), select, maxFields,
                                     onlyDelimited, sepWord, sepLen, &nLines, &emitted, &nFields,
-                                    &outLen, reinterpret_cast<Byte *>(out.data()), outLen));
+                                    &outLen, o, cap));
+  });
   if (lines) *lines = size_t(nLines);
   if (fields) *fields = size_t(nFields);
   return size_t(emitted);

@@ -333,6 +333,27 @@ struct RecordCols {
   }
 };
 
+// The two phases of the host forms that assemble a text on the device (replace_long, replace_text,
+// filter_text, route_text, range_text, extract_text, fields_text), behind their uploads: phase 1
+// (sizes only), the nSizes size words into `sizes`, and - when out is given and put =
+// min(sizes[outLenAt], outCap) is not 0 - a device output of put bytes, phase 2, and the bytes on
+// their way to `out`.  dev(dOut, room, phases) is the verb's ...Dev call over the staged buffers.
+// The caller adds its own downloads, waits, and only then writes the caller's counts from `sizes`,
+// so a call that fails has changed none of them.
+template <class F>
+static void textOutHost(HostCall &call, const uint64_t *dSizes, uint64_t *sizes, uint64_t nSizes,
+                        uint64_t outLenAt, uint8_t *out, uint64_t outCap, F &&dev) {
+  call.run([&] { return dev(nullptr, 0, 1); });
+  call.download(sizes, dSizes, nSizes, "sizes");
+  if (call.wait()) return;
+  const uint64_t put = sizes[outLenAt] < outCap ? sizes[outLenAt] : outCap;
+  if (!out || !put) return;
+  // (the streams are drained: growing the slot waits for nothing)
+  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
+  call.run([&] { return dev(dOut, put, 2); });
+  call.download(out, dOut, put, "out");
+}
+
 // offsets of a chunk that does not start at byte 0, rebased to the chunk's own buffer: the
 // kernels may read data[0, offsets[n]) anywhere (lanes without a line re-read block 0), so a
 // chunk is always presented as a batch of its own
@@ -969,8 +990,8 @@ int redgpu_replace_long_dev(const redgpu_dfa *dfa, int style, int do_leader, con
                         count, out_len, out, out_cap, 3, static_cast<hipStream_t>(stream));
 }
 
-// the text goes up once; phase 1 leaves the records in the stream's scratch and the sizes, the
-// device output is sized from them, phase 2 assembles it: the text is walked once
+// the text and repl go up once, then textOutHost; phase 1 leaves the records in the stream's
+// scratch, phase 2 assembles the output from them: the text is walked once
 int redgpu_replace_long(const redgpu_dfa *dfa, int style, int do_leader, const uint8_t *data,
                         uint64_t len, uint32_t chunk_bytes, const uint8_t *repl, uint64_t repl_len,
                         uint64_t max_count, uint64_t *count, uint64_t *out_len, uint8_t *out,
@@ -983,25 +1004,16 @@ int redgpu_replace_long(const redgpu_dfa *dfa, int style, int do_leader, const u
   uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 2, "sizes");
   call.upload(dData, data, len, "data");
   call.upload(dRepl, repl, repl_len, "repl");
-  call.run([&] {
-    return replaceLongDev(dfa, style, do_leader, dData, len, chunk_bytes, dRepl, repl_len,
-                          max_count, dSizes, dSizes + 1, nullptr, 0, 1, call.stream());
-  });
   uint64_t sizes[2] = {0, 0};
-  call.download(sizes, dSizes, 2, "sizes");
+  textOutHost(call, dSizes, sizes, 2, 1, out, out_cap,
+              [&](uint8_t *dOut, uint64_t room, int phases) {
+    return replaceLongDev(dfa, style, do_leader, dData, len, chunk_bytes, dRepl, repl_len,
+                          max_count, dSizes, dSizes + 1, dOut, room, phases, call.stream());
+  });
   if (int rc = call.wait()) return rc;
   *count = sizes[0];
   *out_len = sizes[1];
-  const uint64_t put = sizes[1] < out_cap ? sizes[1] : out_cap;
-  if (!out || !put) return REDGPU_OK;
-  // (the streams are drained: growing the slot waits for nothing)
-  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
-  call.run([&] {
-    return replaceLongDev(dfa, style, do_leader, dData, len, chunk_bytes, dRepl, repl_len,
-                          max_count, dSizes, dSizes + 1, dOut, put, 2, call.stream());
-  });
-  call.download(out, dOut, put, "out");
-  return call.wait();
+  return REDGPU_OK;
 }
 
 static int checkSearchLong(const redgpu_dfa *dfa, int style, const uint8_t *data, uint64_t len,
@@ -1454,9 +1466,8 @@ int redgpu_replace_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int
                         static_cast<hipStream_t>(stream));
 }
 
-// host-buffer form: the text goes up once; phase 1 leaves the sizes, the bitmaps and the chunks'
-// output bases in the stream's scratch, the device output is sized from *out_len, phase 2
-// assembles it, and min(*out_len, out_cap) bytes come back
+// host-buffer form: the text and repl go up once, then textOutHost; phase 1 leaves the sizes, the
+// bitmaps and the chunks' output bases in the stream's scratch, phase 2 assembles the output
 int redgpu_replace_text(const redgpu_dfa *dfa, int style, int do_leader, int only_changed,
                         const uint8_t *data, uint64_t len, uint8_t delim, const uint8_t *repl,
                         uint64_t repl_len, uint64_t max_count, uint64_t *n_lines,
@@ -1468,26 +1479,18 @@ int redgpu_replace_text(const redgpu_dfa *dfa, int style, int do_leader, int onl
   uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 3, "sizes");
   call.upload(dData, data, len, "data");
   call.upload(dRepl, repl, repl_len, "repl");
-  call.run([&] {
-    return replaceTextDev(dfa, style, do_leader, only_changed, dData, len, delim, dRepl, repl_len,
-                          max_count, dSizes, dSizes + 1, dSizes + 2, nullptr, 0, 1, call.stream());
-  });
   uint64_t sizes[3] = {0, 0, 0};
-  call.download(sizes, dSizes, 3, "sizes");
+  textOutHost(call, dSizes, sizes, 3, 2, out, out_cap,
+              [&](uint8_t *dOut, uint64_t room, int phases) {
+    return replaceTextDev(dfa, style, do_leader, only_changed, dData, len, delim, dRepl, repl_len,
+                          max_count, dSizes, dSizes + 1, dSizes + 2, dOut, room, phases,
+                          call.stream());
+  });
   if (int rc = call.wait()) return rc;
   if (n_lines) *n_lines = sizes[0];
   if (n_replaced) *n_replaced = sizes[1];
   *out_len = sizes[2];
-  const uint64_t put = sizes[2] < out_cap ? sizes[2] : out_cap;
-  if (!out || !put) return REDGPU_OK;
-  // (the streams are drained: growing the slot waits for nothing)
-  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
-  call.run([&] {
-    return replaceTextDev(dfa, style, do_leader, only_changed, dData, len, delim, dRepl, repl_len,
-                          max_count, dSizes, dSizes + 1, dSizes + 2, dOut, put, 2, call.stream());
-  });
-  call.download(out, dOut, put, "out");
-  return call.wait();
+  return REDGPU_OK;
 }
 
 // raw text -> the selected lines and their context, as a text (k_filter_text.h): everything on
@@ -1517,9 +1520,8 @@ int redgpu_filter_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int 
                        static_cast<hipStream_t>(stream));
 }
 
-// host-buffer form, as redgpu_replace_text: the text goes up once; phase 1 leaves the sizes, the
-// bitmaps and the chunks' output bases in the stream's scratch, the device output is sized from
-// *out_len, phase 2 copies the runs, and min(*out_len, out_cap) bytes come back
+// host-buffer form: the text goes up once, then textOutHost; phase 1 leaves the sizes, the bitmaps
+// and the chunks' output bases in the stream's scratch, phase 2 copies the runs
 int redgpu_filter_text(const redgpu_dfa *dfa, int style, int do_leader, int invert, uint64_t before,
                        uint64_t after, uint64_t max_count, const uint8_t *data, uint64_t len,
                        uint8_t delim, uint64_t *n_lines, uint64_t *n_selected, uint64_t *n_emitted,
@@ -1530,27 +1532,19 @@ int redgpu_filter_text(const redgpu_dfa *dfa, int style, int do_leader, int inve
   uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
   uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 4, "sizes");
   call.upload(dData, data, len, "data");
-  call.run([&] {
-    return filterTextDev(dfa, style, do_leader, invert, before, after, max_count, dData, len, delim,
-                         dSizes, dSizes + 1, dSizes + 2, dSizes + 3, nullptr, 0, 1, call.stream());
-  });
   uint64_t sizes[4] = {0, 0, 0, 0};
-  call.download(sizes, dSizes, 4, "sizes");
+  textOutHost(call, dSizes, sizes, 4, 3, out, out_cap,
+              [&](uint8_t *dOut, uint64_t room, int phases) {
+    return filterTextDev(dfa, style, do_leader, invert, before, after, max_count, dData, len, delim,
+                         dSizes, dSizes + 1, dSizes + 2, dSizes + 3, dOut, room, phases,
+                         call.stream());
+  });
   if (int rc = call.wait()) return rc;
   if (n_lines) *n_lines = sizes[0];
   if (n_selected) *n_selected = sizes[1];
   if (n_emitted) *n_emitted = sizes[2];
   *out_len = sizes[3];
-  const uint64_t put = sizes[3] < out_cap ? sizes[3] : out_cap;
-  if (!out || !put) return REDGPU_OK;
-  // (the streams are drained: growing the slot waits for nothing)
-  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
-  call.run([&] {
-    return filterTextDev(dfa, style, do_leader, invert, before, after, max_count, dData, len, delim,
-                         dSizes, dSizes + 1, dSizes + 2, dSizes + 3, dOut, put, 2, call.stream());
-  });
-  call.download(out, dOut, put, "out");
-  return call.wait();
+  return REDGPU_OK;
 }
 
 // the arguments of both route_text forms
@@ -1586,9 +1580,8 @@ int redgpu_route_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int d
                       static_cast<hipStream_t>(stream));
 }
 
-// host-buffer form, as redgpu_filter_text: the text goes up once; phase 1 leaves the sizes, the
-// bitmaps and the (bucket, chunk) output bases in the stream's scratch, the device output is sized
-// from *out_len, phase 2 copies the runs, and min(*out_len, out_cap) bytes come back
+// host-buffer form: the text goes up once, then textOutHost; phase 1 leaves the sizes, the bitmaps
+// and the (bucket, chunk) output bases in the stream's scratch, phase 2 copies the runs
 int redgpu_route_text(const redgpu_dfa *dfa, int style, int do_leader, int drop_unmatched,
                       const uint8_t *data, uint64_t len, uint8_t delim, uint64_t n_bins,
                       uint64_t *n_lines, uint64_t *n_routed, uint64_t *bin_lines,
@@ -1602,27 +1595,19 @@ int redgpu_route_text(const redgpu_dfa *dfa, int style, int do_leader, int drop_
   uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, nSizes, "sizes");
   uint64_t *dLines = dSizes + 3, *dOffsets = dLines + n_bins + 1;
   call.upload(dData, data, len, "data");
-  call.run([&] {
+  textOutHost(call, dSizes, sizes, nSizes, 2, out, out_cap,
+              [&](uint8_t *dOut, uint64_t room, int phases) {
     return routeTextDev(dfa, style, do_leader, drop_unmatched, dData, len, delim, n_bins, dSizes,
-                        dSizes + 1, dLines, dOffsets, dSizes + 2, nullptr, 0, 1, call.stream());
+                        dSizes + 1, dLines, dOffsets, dSizes + 2, dOut, room, phases,
+                        call.stream());
   });
-  call.download(sizes, dSizes, nSizes, "sizes");
   if (int rc = call.wait()) return rc;
   if (n_lines) *n_lines = sizes[0];
   if (n_routed) *n_routed = sizes[1];
   *out_len = sizes[2];
   for (uint64_t i = 0; i <= n_bins && bin_lines; ++i) bin_lines[i] = sizes[3 + i];
   for (uint64_t i = 0; i <= n_bins + 1; ++i) bin_offsets[i] = sizes[3 + n_bins + 1 + i];
-  const uint64_t put = sizes[2] < out_cap ? sizes[2] : out_cap;
-  if (!out || !put) return REDGPU_OK;
-  // (the streams are drained: growing the slot waits for nothing)
-  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
-  call.run([&] {
-    return routeTextDev(dfa, style, do_leader, drop_unmatched, dData, len, delim, n_bins, dSizes,
-                        dSizes + 1, dLines, dOffsets, dSizes + 2, dOut, put, 2, call.stream());
-  });
-  call.download(out, dOut, put, "out");
-  return call.wait();
+  return REDGPU_OK;
 }
 
 // the arguments of both range_text forms
@@ -1667,10 +1652,9 @@ int redgpu_range_text_dev(const redgpu_dfa *dfa, int style, int do_leader, int32
                       static_cast<hipStream_t>(stream));
 }
 
-// host-buffer form, as redgpu_filter_text: the text goes up once; phase 1 leaves the sizes, the
-// bitmaps, the chunks' output bases and the records on the device, the device output is sized from
-// *out_len, phase 2 copies the runs, and min(*out_len, out_cap) bytes and the records that exist
-// come back
+// host-buffer form: the text goes up once, then textOutHost; phase 1 leaves the sizes, the bitmaps,
+// the chunks' output bases and the records on the device, phase 2 copies the runs (and reads no
+// record argument), and the records that exist come back behind the output
 int redgpu_range_text(const redgpu_dfa *dfa, int style, int do_leader, int32_t open_result,
                       int32_t close_result, int emit_open, int emit_close, int invert,
                       uint64_t max_ranges, const uint8_t *data, uint64_t len, uint8_t delim,
@@ -1691,28 +1675,15 @@ int redgpu_range_text(const redgpu_dfa *dfa, int style, int do_leader, int32_t o
   for (int i = 0; i < 4 && dRec; ++i)
     if (host[i]) dev[i] = dRec + uint64_t(i) * rec_cap;
   call.upload(dData, data, len, "data");
-  call.run([&] {
+  uint64_t sizes[4] = {0, 0, 0, 0};
+  textOutHost(call, dSizes, sizes, 4, 3, out, out_cap,
+              [&](uint8_t *dOut, uint64_t room, int phases) {
     return rangeTextDev(dfa, style, do_leader, open_result, close_result, emit_open, emit_close,
                         invert, max_ranges, dData, len, delim, dSizes, dSizes + 1, dSizes + 2,
-                        dSizes + 3, nullptr, 0, rec_cap, dev[0], dev[1], dev[2], dev[3], 1,
+                        dSizes + 3, dOut, room, rec_cap, dev[0], dev[1], dev[2], dev[3], phases,
                         call.stream());
   });
-  uint64_t sizes[4] = {0, 0, 0, 0};
-  call.download(sizes, dSizes, 4, "sizes");
-  if (int rc = call.wait()) return rc;
   const uint64_t got = sizes[1] < rec_cap ? sizes[1] : rec_cap;
-  const uint64_t put = sizes[3] < out_cap ? sizes[3] : out_cap;
-  if (out && put) {
-    // (the streams are drained: growing the slot waits for nothing)
-    uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
-    call.run([&] {
-      return rangeTextDev(dfa, style, do_leader, open_result, close_result, emit_open, emit_close,
-                          invert, max_ranges, dData, len, delim, dSizes, dSizes + 1, dSizes + 2,
-                          dSizes + 3, dOut, put, 0, nullptr, nullptr, nullptr, nullptr, 2,
-                          call.stream());
-    });
-    call.download(out, dOut, put, "out");
-  }
   for (int i = 0; i < 4 && got; ++i)
     if (dev[i]) call.download(host[i], dev[i], got, "records");
   if (int rc = call.wait()) return rc;
@@ -1831,9 +1802,8 @@ int redgpu_extract_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t
                         out_cap, 3, static_cast<hipStream_t>(stream));
 }
 
-// host-buffer form, as redgpu_filter_text: the text goes up once; phase 1 leaves the sizes, the
-// bitmaps and the chunks' output bases in the stream's scratch, the device output is sized from
-// *out_len, phase 2 assembles the pieces, and min(*out_len, out_cap) bytes come back
+// host-buffer form: the text goes up once, then textOutHost; phase 1 leaves the sizes, the bitmaps
+// and the chunks' output bases in the stream's scratch, phase 2 assembles the pieces
 int redgpu_extract_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                         uint64_t max_per_line, uint64_t *n_lines, uint64_t *n_matches,
                         uint64_t *out_len, uint8_t *out, uint64_t out_cap) {
@@ -1843,26 +1813,17 @@ int redgpu_extract_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len
   uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
   uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 3, "sizes");
   call.upload(dData, data, len, "data");
-  call.run([&] {
-    return extractTextDev(dfa, dData, len, delim, max_per_line, dSizes, dSizes + 1, dSizes + 2,
-                          nullptr, 0, 1, call.stream());
-  });
   uint64_t sizes[3] = {0, 0, 0};
-  call.download(sizes, dSizes, 3, "sizes");
+  textOutHost(call, dSizes, sizes, 3, 2, out, out_cap,
+              [&](uint8_t *dOut, uint64_t room, int phases) {
+    return extractTextDev(dfa, dData, len, delim, max_per_line, dSizes, dSizes + 1, dSizes + 2,
+                          dOut, room, phases, call.stream());
+  });
   if (int rc = call.wait()) return rc;
   if (n_lines) *n_lines = sizes[0];
   if (n_matches) *n_matches = sizes[1];
   *out_len = sizes[2];
-  const uint64_t put = sizes[2] < out_cap ? sizes[2] : out_cap;
-  if (!out || !put) return REDGPU_OK;
-  // (the streams are drained: growing the slot waits for nothing)
-  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
-  call.run([&] {
-    return extractTextDev(dfa, dData, len, delim, max_per_line, dSizes, dSizes + 1, dSizes + 2,
-                          dOut, put, 2, call.stream());
-  });
-  call.download(out, dOut, put, "out");
-  return call.wait();
+  return REDGPU_OK;
 }
 
 // the arguments of both fields_text forms
@@ -1900,9 +1861,8 @@ int redgpu_fields_text_dev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t 
                        static_cast<hipStream_t>(stream));
 }
 
-// host-buffer form, as redgpu_extract_text: the text goes up once; phase 1 leaves the sizes, the
-// bitmaps and the chunks' output bases in the stream's scratch, the device output is sized from
-// *out_len, phase 2 assembles the lines, and min(*out_len, out_cap) bytes come back
+// host-buffer form: the text goes up once, then textOutHost; phase 1 leaves the sizes, the bitmaps
+// and the chunks' output bases in the stream's scratch, phase 2 assembles the lines
 int redgpu_fields_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,
                        uint64_t select, uint64_t max_fields, int only_delimited, uint64_t sep,
                        uint32_t sep_len, uint64_t *n_lines, uint64_t *n_emitted,
@@ -1912,27 +1872,19 @@ int redgpu_fields_text(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len,
   uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
   uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 4, "sizes");
   call.upload(dData, data, len, "data");
-  call.run([&] {
-    return fieldsTextDev(dfa, dData, len, delim, select, max_fields, only_delimited, sep, sep_len,
-                         dSizes, dSizes + 1, dSizes + 2, dSizes + 3, nullptr, 0, 1, call.stream());
-  });
   uint64_t sizes[4] = {0, 0, 0, 0};
-  call.download(sizes, dSizes, 4, "sizes");
+  textOutHost(call, dSizes, sizes, 4, 3, out, out_cap,
+              [&](uint8_t *dOut, uint64_t room, int phases) {
+    return fieldsTextDev(dfa, dData, len, delim, select, max_fields, only_delimited, sep, sep_len,
+                         dSizes, dSizes + 1, dSizes + 2, dSizes + 3, dOut, room, phases,
+                         call.stream());
+  });
   if (int rc = call.wait()) return rc;
   if (n_lines) *n_lines = sizes[0];
   if (n_emitted) *n_emitted = sizes[1];
   if (n_fields) *n_fields = sizes[2];
   *out_len = sizes[3];
-  const uint64_t put = sizes[3] < out_cap ? sizes[3] : out_cap;
-  if (!out || !put) return REDGPU_OK;
-  // (the streams are drained: growing the slot waits for nothing)
-  uint8_t *dOut = call.buf<uint8_t>(kSlAux3, put, "out");
-  call.run([&] {
-    return fieldsTextDev(dfa, dData, len, delim, select, max_fields, only_delimited, sep, sep_len,
-                         dSizes, dSizes + 1, dSizes + 2, dSizes + 3, dOut, put, 2, call.stream());
-  });
-  call.download(out, dOut, put, "out");
-  return call.wait();
+  return REDGPU_OK;
 }
 
 int redgpu_split_lines(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,

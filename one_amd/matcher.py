@@ -525,6 +525,52 @@ def _device_text(text):
     return text.device, torch.cuda.current_stream(text.device)
 
 
+def _delim_byte(delim) -> int:
+    """a raw-text verb's delim - bytes (the first one counts) or an int - as the C calls' byte"""
+    return delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+
+
+def _device_raw_text(data):
+    """a raw-text verb's device input, checked -> (device, its pointer or None when empty, its
+    length, the handle of torch's current stream on the device)"""
+    dev, stream = _device_text(data)
+    return dev, data.data_ptr() if data.numel() else None, data.numel(), stream.cuda_stream
+
+
+def _device_out_room(verb, data, out, out_cap):
+    """the output of a text-output verb's device form -> (out, room): out= is checked, out_cap
+    alone makes a tensor of that size; the room is out's size, or out_cap where that is smaller"""
+    import torch
+    if out is None and out_cap is None:
+        raise RedExceptApi("device %s needs out or out_cap (room for the output)" % verb)
+    if out is None:
+        out = torch.empty(int(out_cap), dtype=torch.uint8, device=data.device)
+    elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
+          not out.is_contiguous() or out.device != data.device):
+        raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
+    return out, out.numel() if out_cap is None else min(int(out_cap), out.numel())
+
+
+def _host_text_only(out, out_cap):
+    """a text-output verb with a host text takes neither out= nor out_cap="""
+    if out is not None or out_cap is not None:
+        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+
+
+def _host_text_out(cap, call):
+    """the output of a text-output verb's host form: call(buffer pointer, cap) -> out_len with a
+    buffer of cap bytes, once more with the exact size when that was too small (never, where cap
+    is the text's length and the output no longer than the text) -> the output's bytes"""
+    cap = int(cap)
+    for _ in range(2):
+        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+        out_len = int(call(buf.ctypes.data, cap))
+        if out_len <= cap:
+            break
+        cap = out_len
+    return buf[:out_len].tobytes()
+
+
 def _long_records(entry, head, text, cap, chunk_bytes):
     """collect_long / match_all_long: redgpu_<entry>[_dev](*head, data, len, chunk_bytes, room,
     count, result, start, end[, stream]) over a host or a device text; with cap=None once more
@@ -784,9 +830,7 @@ def replace_long(exe, text, repl: bytes, style=styLast, do_leader=True, max_coun
             return [int(v) for v in sizes.tolist()]
 
         if out is not None:
-            if (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
-                    not out.is_contiguous() or out.device != dev):
-                raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
+            _device_out_room("replace_long", text, out, None)
             count, out_len = call(out)
             return count, out[:min(out_len, out.numel())], out_len
         count, out_len = call(None)
@@ -799,18 +843,17 @@ def replace_long(exe, text, repl: bytes, style=styLast, do_leader=True, max_coun
     a = _host_u8(text)
     cnt = C.c_uint64(0)
     olen = C.c_uint64(0)
-    # first guess: output about as long as the input; once more with the exact size otherwise
-    cap = int(a.size + 64)
-    for _ in range(2):
-        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+
+    def host_call(buf, cap):
         _check(l.redgpu_replace_long(
             exe._h, int(style), 1 if do_leader else 0, a.ctypes.data if a.size else None, a.size,
             int(chunk_bytes), r.ctypes.data if r.size else None, r.size, int(max_count),
-            C.byref(cnt), C.byref(olen), buf.ctypes.data, cap))
-        if int(olen.value) <= cap:
-            break
-        cap = int(olen.value)
-    return int(cnt.value), buf[:int(olen.value)].tobytes()
+            C.byref(cnt), C.byref(olen), buf, cap))
+        return olen.value
+
+    # first guess: output about as long as the input
+    rewritten = _host_text_out(a.size + 64, host_call)
+    return int(cnt.value), rewritten
 
 
 def search_long(exe, text, style=styLast, do_leader=True, *, chunk_bytes=0):
@@ -848,18 +891,16 @@ def split_lines(exe, data, delim=b"\n", cap=None):
     for host input; for a CUDA uint8 tensor, an int64 tensor of cap+1 entries and a 1-element
     int64 tensor, both on the device, asynchronously on the current stream."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev, _, _, stream = _device_raw_text(data)
         if cap is None:
             raise RedExceptApi("device split_lines needs cap (room in the offsets tensor)")
-        offs = torch.empty(cap + 1, dtype=torch.int64, device=data.device)
-        cnt = torch.empty(1, dtype=torch.int64, device=data.device)
+        offs = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+        cnt = torch.empty(1, dtype=torch.int64, device=dev)
         _check(l.redgpu_split_lines_dev(exe._h, data.data_ptr(), data.numel(), d, offs.data_ptr(),
-                                        cap, cnt.data_ptr(),
-                                        torch.cuda.current_stream(data.device).cuda_stream))
+                                        cap, cnt.data_ptr(), stream))
         return offs, cnt
     a = _host_u8(data)
     cnt = C.c_uint64(0)
@@ -884,20 +925,17 @@ def match_text(exe, data, style, do_leader=True, *, delim=b"\n", cap=None, want_
     tensors, asynchronously on the current stream; entries from min(count, cap) on are untouched.
     want_start = want_end = False is check<style,doLeader>."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev, _, _, stream = _device_raw_text(data)
         if cap is None:
             raise RedExceptApi("device match_text needs cap (room in the output tensors)")
-        dev = data.device
         offs = torch.empty(cap + 1, dtype=torch.int64, device=dev)
         cnt = torch.empty(1, dtype=torch.int64, device=dev)
         res = torch.empty(cap, dtype=torch.int32, device=dev)
         st = torch.empty(cap, dtype=torch.int64, device=dev) if want_start else None
         en = torch.empty(cap, dtype=torch.int64, device=dev) if want_end else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
         if st is None and en is None:
             _check(l.redgpu_check_text_dev(exe._h, int(style), 1 if do_leader else 0,
                                            data.data_ptr(), data.numel(), d, offs.data_ptr(), cap,
@@ -947,27 +985,24 @@ def grep_text(exe, data, style=styInstant, do_leader=True, *, invert=False, deli
     1-element int64 tensors, asynchronously on the current stream and without any read-back;
     entries from min(n_selected, cap) on are untouched."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     style, lead, inv = int(style), 1 if do_leader else 0, 1 if invert else 0
     max_count = int(max_count)
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev, ptr, size, stream = _device_raw_text(data)
         if cap is None:
             raise RedExceptApi("device grep_text needs cap (room in the output tensors)")
-        dev = data.device
         cnt = torch.empty(2, dtype=torch.int64, device=dev)
         ln, bg, fn = (torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(3))
         res = torch.empty(cap, dtype=torch.int32, device=dev) if want_outcome else None
         st = torch.empty(cap, dtype=torch.int64, device=dev) if want_outcome else None
         en = torch.empty(cap, dtype=torch.int64, device=dev) if want_outcome else None
         _check(l.redgpu_grep_text_dev(
-            exe._h, style, lead, inv, data.data_ptr() if data.numel() else None, data.numel(), d,
-            max_count, cap, cnt.data_ptr(), cnt.data_ptr() + 8, ln.data_ptr(), bg.data_ptr(),
-            fn.data_ptr(), res.data_ptr() if want_outcome else None,
-            st.data_ptr() if want_outcome else None, en.data_ptr() if want_outcome else None,
-            torch.cuda.current_stream(dev).cuda_stream))
+            exe._h, style, lead, inv, ptr, size, d, max_count, cap, cnt.data_ptr(),
+            cnt.data_ptr() + 8, ln.data_ptr(), bg.data_ptr(), fn.data_ptr(),
+            res.data_ptr() if want_outcome else None, st.data_ptr() if want_outcome else None,
+            en.data_ptr() if want_outcome else None, stream))
         return cnt[0:1], cnt[1:2], ln, bg, fn, res, st, en
     a = _host_u8(data)
     dp = a.ctypes.data if a.size else None
@@ -1011,24 +1046,21 @@ def collect_text(exe, data, *, delim=b"\n", cap=None, want_positions=True):
     1-element int64 tensors, asynchronously on the current stream and without any read-back;
     entries from min(n_matches, cap) on are untouched."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
+        dev, ptr, size, stream = _device_raw_text(data)
         if cap is None:
             raise RedExceptApi("device collect_text needs cap (room in the output tensors)")
-        dev = data.device
         cnt = torch.empty(2, dtype=torch.int64, device=dev)
         ln, bg = (torch.empty(cap, dtype=torch.int64, device=dev) for _ in range(2))
         res = torch.empty(cap, dtype=torch.int32, device=dev)
         st = torch.empty(cap, dtype=torch.int64, device=dev) if want_positions else None
         en = torch.empty(cap, dtype=torch.int64, device=dev) if want_positions else None
         _check(l.redgpu_collect_text_dev(
-            exe._h, data.data_ptr() if data.numel() else None, data.numel(), d, cap,
-            cnt.data_ptr(), cnt.data_ptr() + 8, ln.data_ptr(), bg.data_ptr(), res.data_ptr(),
-            st.data_ptr() if want_positions else None, en.data_ptr() if want_positions else None,
-            torch.cuda.current_stream(dev).cuda_stream))
+            exe._h, ptr, size, d, cap, cnt.data_ptr(), cnt.data_ptr() + 8, ln.data_ptr(),
+            bg.data_ptr(), res.data_ptr(), st.data_ptr() if want_positions else None,
+            en.data_ptr() if want_positions else None, stream))
         return cnt[0:1], cnt[1:2], ln, bg, res, st, en
     a = _host_u8(data)
     dp = a.ctypes.data if a.size else None
@@ -1077,7 +1109,7 @@ def tally_text(exe, data, n_bins=None, *, matches=True, style=styInstant, do_lea
     tensors and bins as int64 (into= an int64 CUDA tensor of n_bins + 1), asynchronously on the
     current stream and without any read-back."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     what = TALLY_MATCHES if matches else TALLY_LINES
     style, lead = int(style), 1 if do_leader else 0
     n_bins = int(exe.info["max_result"]) + 1 if n_bins is None else int(n_bins)
@@ -1085,9 +1117,7 @@ def tally_text(exe, data, n_bins=None, *, matches=True, style=styInstant, do_lea
         raise RedExceptApi("n_bins must not be negative")
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = data.device
+        dev, ptr, size, stream = _device_raw_text(data)
         if into is None:
             bins = torch.empty(n_bins + 1, dtype=torch.int64, device=dev)
         else:
@@ -1099,9 +1129,8 @@ def tally_text(exe, data, n_bins=None, *, matches=True, style=styInstant, do_lea
             bins = into
         cnt = torch.empty(2, dtype=torch.int64, device=dev)
         _check(l.redgpu_tally_text_dev(
-            exe._h, what, style, lead, data.data_ptr() if data.numel() else None, data.numel(), d,
-            n_bins, 0 if into is None else 1, cnt.data_ptr(), cnt.data_ptr() + 8, bins.data_ptr(),
-            torch.cuda.current_stream(dev).cuda_stream))
+            exe._h, what, style, lead, ptr, size, d, n_bins, 0 if into is None else 1,
+            cnt.data_ptr(), cnt.data_ptr() + 8, bins.data_ptr(), stream))
         return cnt[0:1], cnt[1:2], bins
     a = _host_u8(data)
     dp = a.ctypes.data if a.size else None
@@ -1139,7 +1168,7 @@ def sum_text(exe, data, n_bins=None, *, which="first", max_per_line=1 << 62, del
     on the current stream and without any read-back.  The words are unsigned: an empty slot's min
     reads -1 there, and stats.cpu().numpy().view(numpy.uint64) gives the values as they are."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     if which not in _SUM_WHICH:
         raise RedExceptApi('which must be "first" or "last"')
     w, per = _SUM_WHICH[which], int(max_per_line)
@@ -1148,9 +1177,7 @@ def sum_text(exe, data, n_bins=None, *, which="first", max_per_line=1 << 62, del
         raise RedExceptApi("n_bins and max_per_line must not be negative")
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = data.device
+        dev, ptr, size, stream = _device_raw_text(data)
         if into is None:
             stats = torch.empty((4, n_bins + 1), dtype=torch.int64, device=dev)
         else:
@@ -1162,9 +1189,8 @@ def sum_text(exe, data, n_bins=None, *, which="first", max_per_line=1 << 62, del
             stats = into
         cnt = torch.empty(3, dtype=torch.int64, device=dev)
         _check(l.redgpu_sum_text_dev(
-            exe._h, w, data.data_ptr() if data.numel() else None, data.numel(), d, per, n_bins,
-            0 if into is None else 1, cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 16,
-            stats.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            exe._h, w, ptr, size, d, per, n_bins, 0 if into is None else 1, cnt.data_ptr(),
+            cnt.data_ptr() + 8, cnt.data_ptr() + 16, stats.data_ptr(), stream))
         return cnt[0:1], cnt[1:2], cnt[2:3], stats
     a = _host_u8(data)
     dp = a.ctypes.data if a.size else None
@@ -1201,7 +1227,7 @@ def uniq_text(exe, data, *, matches=True, style=styInstant, do_leader=True, max_
     which the first min(n_distinct, cap) are written, asynchronously on the current stream and
     without any read-back."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     what = UNIQ_MATCHES if matches else UNIQ_LINES
     style, lead, per = int(style), 1 if do_leader else 0, int(max_per_line)
     max_distinct = int(max_distinct)
@@ -1214,18 +1240,15 @@ def uniq_text(exe, data, *, matches=True, style=styInstant, do_leader=True, max_
         slots *= 2
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = data.device
+        dev, ptr, size, stream = _device_raw_text(data)
         rows = max_distinct if cap is None else int(cap)
         cnt = torch.empty(4, dtype=torch.int64, device=dev)
         rec = torch.empty((3, rows), dtype=torch.int64, device=dev)
         _check(l.redgpu_uniq_text_dev(
-            exe._h, what, style, lead, data.data_ptr() if data.numel() else None, data.numel(), d,
-            per, slots, rows, cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 16,
-            cnt.data_ptr() + 24, rec[0].data_ptr() if rows else None,
-            rec[1].data_ptr() if rows else None, rec[2].data_ptr() if rows else None,
-            torch.cuda.current_stream(dev).cuda_stream))
+            exe._h, what, style, lead, ptr, size, d, per, slots, rows, cnt.data_ptr(),
+            cnt.data_ptr() + 8, cnt.data_ptr() + 16, cnt.data_ptr() + 24,
+            rec[0].data_ptr() if rows else None, rec[1].data_ptr() if rows else None,
+            rec[2].data_ptr() if rows else None, stream))
         return cnt[0:1], cnt[1:2], cnt[3:4], cnt[2:3], rec[0], rec[1], rec[2]
     a = _host_u8(data)
     # no more records than slots, nor than bytes
@@ -1256,22 +1279,13 @@ def replace_text(exe, data, repl, style=styLast, do_leader=True, max_count=1 << 
     read-back; out_len may exceed the room, bytes of out from min(out_len, room) on are untouched.
     repl is bytes or, for the device form, a uint8 CUDA tensor too."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     style, lead, oc = int(style), 1 if do_leader else 0, 1 if only_changed else 0
     max_count = int(max_count)
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = data.device
-        if out is None and out_cap is None:
-            raise RedExceptApi("device replace_text needs out or out_cap (room for the output)")
-        if out is None:
-            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
-        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
-              not out.is_contiguous() or out.device != dev):
-            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
-        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        dev, ptr, size, stream = _device_raw_text(data)
+        out, room = _device_out_room("replace_text", data, out, out_cap)
         if _is_torch(repl):
             if (not repl.is_cuda or repl.dtype != torch.uint8 or not repl.is_contiguous() or
                     repl.device != dev):
@@ -1282,28 +1296,25 @@ def replace_text(exe, data, repl, style=styLast, do_leader=True, max_count=1 << 
             drepl = torch.from_numpy(r.copy()).to(dev)
         cnt = torch.empty(3, dtype=torch.int64, device=dev)
         _check(l.redgpu_replace_text_dev(
-            exe._h, style, lead, oc, data.data_ptr() if data.numel() else None, data.numel(), d,
-            drepl.data_ptr() if drepl.numel() else None, drepl.numel(), max_count, cnt.data_ptr(),
-            cnt.data_ptr() + 8, cnt.data_ptr() + 16, out.data_ptr() if room else None, room,
-            torch.cuda.current_stream(dev).cuda_stream))
+            exe._h, style, lead, oc, ptr, size, d, drepl.data_ptr() if drepl.numel() else None,
+            drepl.numel(), max_count, cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 16,
+            out.data_ptr() if room else None, room, stream))
         return cnt[0:1], cnt[1:2], cnt[2:3], out
-    if out is not None or out_cap is not None:
-        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    _host_text_only(out, out_cap)
     a = _host_u8(data)
     r = np.frombuffer(bytes(repl), dtype=np.uint8)
     nl, nr, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    # first guess: output about as long as the input; once more with the exact size otherwise
-    cap = int(a.size + 64)
-    for _ in range(2):
-        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+
+    def call(buf, cap):
         _check(l.redgpu_replace_text(
             exe._h, style, lead, oc, a.ctypes.data if a.size else None, a.size, d,
             r.ctypes.data if r.size else None, r.size, max_count, C.byref(nl), C.byref(nr),
-            C.byref(olen), buf.ctypes.data, cap))
-        if int(olen.value) <= cap:
-            break
-        cap = int(olen.value)
-    return int(nl.value), int(nr.value), buf[:int(olen.value)].tobytes()
+            C.byref(olen), buf, cap))
+        return olen.value
+
+    # first guess: output about as long as the input
+    text = _host_text_out(a.size + 64, call)
+    return int(nl.value), int(nr.value), text
 
 
 def filter_text(exe, data, style=styInstant, do_leader=True, *, invert=False, before=0, after=0,
@@ -1320,40 +1331,32 @@ def filter_text(exe, data, style=styInstant, do_leader=True, *, invert=False, be
     any read-back; out_len may exceed the room, bytes of out from min(out_len, room) on are
     untouched.  The output is a raw text that every text verb accepts."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     style, lead, inv = int(style), 1 if do_leader else 0, 1 if invert else 0
     before, after, max_count = int(before), int(after), int(max_count)
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = data.device
-        if out is None and out_cap is None:
-            raise RedExceptApi("device filter_text needs out or out_cap (room for the output)")
-        if out is None:
-            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
-        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
-              not out.is_contiguous() or out.device != dev):
-            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
-        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        dev, ptr, size, stream = _device_raw_text(data)
+        out, room = _device_out_room("filter_text", data, out, out_cap)
         cnt = torch.empty(4, dtype=torch.int64, device=dev)
         _check(l.redgpu_filter_text_dev(
-            exe._h, style, lead, inv, before, after, max_count,
-            data.data_ptr() if data.numel() else None, data.numel(), d, cnt.data_ptr(),
+            exe._h, style, lead, inv, before, after, max_count, ptr, size, d, cnt.data_ptr(),
             cnt.data_ptr() + 8, cnt.data_ptr() + 16, cnt.data_ptr() + 24,
-            out.data_ptr() if room else None, room, torch.cuda.current_stream(dev).cuda_stream))
+            out.data_ptr() if room else None, room, stream))
         return cnt[0:1], cnt[1:2], cnt[2:3], cnt[3:4], out
-    if out is not None or out_cap is not None:
-        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    _host_text_only(out, out_cap)
     a = _host_u8(data)
     nl, ns, ne, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+
+    def call(buf, cap):
+        _check(l.redgpu_filter_text(
+            exe._h, style, lead, inv, before, after, max_count, a.ctypes.data if a.size else None,
+            a.size, d, C.byref(nl), C.byref(ns), C.byref(ne), C.byref(olen), buf, cap))
+        return olen.value
+
     # the output is no longer than the text
-    cap = int(a.size)
-    buf = np.zeros(max(cap, 1), dtype=np.uint8)
-    _check(l.redgpu_filter_text(
-        exe._h, style, lead, inv, before, after, max_count, a.ctypes.data if a.size else None,
-        a.size, d, C.byref(nl), C.byref(ns), C.byref(ne), C.byref(olen), buf.ctypes.data, cap))
-    return int(nl.value), int(ns.value), int(ne.value), buf[:int(olen.value)].tobytes()
+    text = _host_text_out(a.size, call)
+    return int(nl.value), int(ns.value), int(ne.value), text
 
 
 def route_text(exe, data, n_bins=None, style=styInstant, do_leader=True, *, drop_unmatched=False,
@@ -1375,7 +1378,7 @@ def route_text(exe, data, n_bins=None, style=styInstant, do_leader=True, *, drop
     any read-back; out_len may exceed the room, bytes of out from min(out_len, room) on are
     untouched.  Every section of the output is a raw text that every text verb accepts."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     style, lead, drop = int(style), 1 if do_leader else 0, 1 if drop_unmatched else 0
     n_bins = min(int(exe.info["max_result"]) + 1, 255) if n_bins is None else int(n_bins)
     if n_bins < 0:
@@ -1384,41 +1387,32 @@ def route_text(exe, data, n_bins=None, style=styInstant, do_leader=True, *, drop
         raise RedExceptLimit("n_bins must not exceed 255")
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = data.device
-        if out is None and out_cap is None:
-            raise RedExceptApi("device route_text needs out or out_cap (room for the output)")
-        if out is None:
-            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
-        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
-              not out.is_contiguous() or out.device != dev):
-            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
-        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        dev, ptr, size, stream = _device_raw_text(data)
+        out, room = _device_out_room("route_text", data, out, out_cap)
         # n_lines, n_routed, out_len, bin_lines[n_bins + 1], bin_offsets[n_bins + 2]
         cnt = torch.empty(3 + 2 * n_bins + 3, dtype=torch.int64, device=dev)
         lines_at, offs_at = 3, 3 + n_bins + 1
         _check(l.redgpu_route_text_dev(
-            exe._h, style, lead, drop, data.data_ptr() if data.numel() else None, data.numel(), d,
-            n_bins, cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 8 * lines_at,
-            cnt.data_ptr() + 8 * offs_at, cnt.data_ptr() + 16, out.data_ptr() if room else None,
-            room, torch.cuda.current_stream(dev).cuda_stream))
+            exe._h, style, lead, drop, ptr, size, d, n_bins, cnt.data_ptr(), cnt.data_ptr() + 8,
+            cnt.data_ptr() + 8 * lines_at, cnt.data_ptr() + 8 * offs_at, cnt.data_ptr() + 16,
+            out.data_ptr() if room else None, room, stream))
         return cnt[0:1], cnt[1:2], cnt[lines_at:offs_at], cnt[offs_at:], cnt[2:3], out
-    if out is not None or out_cap is not None:
-        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    _host_text_only(out, out_cap)
     a = _host_u8(data)
     nl, nr, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     bin_lines = np.zeros(n_bins + 1, dtype=np.uint64)
     bin_offsets = np.zeros(n_bins + 2, dtype=np.uint64)
+
+    def call(buf, cap):
+        _check(l.redgpu_route_text(
+            exe._h, style, lead, drop, a.ctypes.data if a.size else None, a.size, d, n_bins,
+            C.byref(nl), C.byref(nr), bin_lines.ctypes.data, bin_offsets.ctypes.data,
+            C.byref(olen), buf, cap))
+        return olen.value
+
     # the output is no longer than the text
-    cap = int(a.size)
-    buf = np.zeros(max(cap, 1), dtype=np.uint8)
-    _check(l.redgpu_route_text(
-        exe._h, style, lead, drop, a.ctypes.data if a.size else None, a.size, d, n_bins,
-        C.byref(nl), C.byref(nr), bin_lines.ctypes.data, bin_offsets.ctypes.data, C.byref(olen),
-        buf.ctypes.data, cap))
-    return (int(nl.value), int(nr.value), bin_lines, bin_offsets,
-            buf[:int(olen.value)].tobytes())
+    text = _host_text_out(a.size, call)
+    return int(nl.value), int(nr.value), bin_lines, bin_offsets, text
 
 
 def range_text(exe, data, open_result, close_result=None, style=styInstant, do_leader=True, *,
@@ -1445,7 +1439,7 @@ def range_text(exe, data, open_result, close_result=None, style=styInstant, do_l
     bytes of out from min(out_len, room) on are untouched.  The output is a raw text that every
     text verb accepts."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     style, lead, inv = int(style), 1 if do_leader else 0, 1 if invert else 0
     eo, ec = 1 if emit_open else 0, 1 if emit_close else 0
     open_result = int(open_result)
@@ -1459,43 +1453,35 @@ def range_text(exe, data, open_result, close_result=None, style=styInstant, do_l
         raise RedExceptApi("max_ranges and rec_cap must not be negative")
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = data.device
-        if out is None and out_cap is None:
-            raise RedExceptApi("device range_text needs out or out_cap (room for the output)")
-        if out is None:
-            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
-        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
-              not out.is_contiguous() or out.device != dev):
-            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
-        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        dev, ptr, size, stream = _device_raw_text(data)
+        out, room = _device_out_room("range_text", data, out, out_cap)
         cnt = torch.empty(4, dtype=torch.int64, device=dev)
         rec = torch.empty((4, rec_cap), dtype=torch.int64, device=dev)
         at = [rec[k].data_ptr() if rec_cap else None for k in range(4)]
         _check(l.redgpu_range_text_dev(
-            exe._h, style, lead, open_result, close_result, eo, ec, inv, max_ranges,
-            data.data_ptr() if data.numel() else None, data.numel(), d, cnt.data_ptr(),
-            cnt.data_ptr() + 8, cnt.data_ptr() + 16, cnt.data_ptr() + 24,
-            out.data_ptr() if room else None, room, rec_cap, at[0], at[1], at[2], at[3],
-            torch.cuda.current_stream(dev).cuda_stream))
+            exe._h, style, lead, open_result, close_result, eo, ec, inv, max_ranges, ptr, size, d,
+            cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 16, cnt.data_ptr() + 24,
+            out.data_ptr() if room else None, room, rec_cap, at[0], at[1], at[2], at[3], stream))
         return cnt[0:1], cnt[1:2], cnt[2:3], cnt[3:4], out, rec[0], rec[1], rec[2], rec[3]
-    if out is not None or out_cap is not None:
-        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    _host_text_only(out, out_cap)
     a = _host_u8(data)
     nl, nr, ne, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    # the output is no longer than the text, and there are no more ranges than bytes
-    cap = int(a.size)
-    rec_cap = min(rec_cap, cap)
-    buf = np.zeros(max(cap, 1), dtype=np.uint8)
+    # there are no more ranges than bytes
+    rec_cap = min(rec_cap, int(a.size))
     rec = np.zeros((4, max(rec_cap, 1)), dtype=np.uint64)
-    _check(l.redgpu_range_text(
-        exe._h, style, lead, open_result, close_result, eo, ec, inv, max_ranges,
-        a.ctypes.data if a.size else None, a.size, d, C.byref(nl), C.byref(nr), C.byref(ne),
-        C.byref(olen), buf.ctypes.data, cap, rec_cap, rec[0].ctypes.data, rec[1].ctypes.data,
-        rec[2].ctypes.data, rec[3].ctypes.data))
+
+    def call(buf, cap):
+        _check(l.redgpu_range_text(
+            exe._h, style, lead, open_result, close_result, eo, ec, inv, max_ranges,
+            a.ctypes.data if a.size else None, a.size, d, C.byref(nl), C.byref(nr), C.byref(ne),
+            C.byref(olen), buf, cap, rec_cap, rec[0].ctypes.data, rec[1].ctypes.data,
+            rec[2].ctypes.data, rec[3].ctypes.data))
+        return olen.value
+
+    # the output is no longer than the text
+    text = _host_text_out(a.size, call)
     got = min(int(nr.value), rec_cap)
-    return (int(nl.value), int(nr.value), int(ne.value), buf[:int(olen.value)].tobytes(),
+    return (int(nl.value), int(nr.value), int(ne.value), text,
             rec[0, :got].copy(), rec[1, :got].copy(), rec[2, :got].copy(), rec[3, :got].copy())
 
 
@@ -1512,43 +1498,31 @@ def extract_text(exe, data, *, max_per_line=1 << 62, delim=b"\n", out=None, out_
     read-back; out_len may exceed the room, bytes of out from min(out_len, room) on are
     untouched.  The output is a raw text that every text verb accepts."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     max_per_line = int(max_per_line)
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = data.device
-        if out is None and out_cap is None:
-            raise RedExceptApi("device extract_text needs out or out_cap (room for the output)")
-        if out is None:
-            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
-        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
-              not out.is_contiguous() or out.device != dev):
-            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
-        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        dev, ptr, size, stream = _device_raw_text(data)
+        out, room = _device_out_room("extract_text", data, out, out_cap)
         cnt = torch.empty(3, dtype=torch.int64, device=dev)
         _check(l.redgpu_extract_text_dev(
-            exe._h, data.data_ptr() if data.numel() else None, data.numel(), d, max_per_line,
-            cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 16,
-            out.data_ptr() if room else None, room, torch.cuda.current_stream(dev).cuda_stream))
+            exe._h, ptr, size, d, max_per_line, cnt.data_ptr(), cnt.data_ptr() + 8,
+            cnt.data_ptr() + 16, out.data_ptr() if room else None, room, stream))
         return cnt[0:1], cnt[1:2], cnt[2:3], out
-    if out is not None or out_cap is not None:
-        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    _host_text_only(out, out_cap)
     a = _host_u8(data)
     nl, nm, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    # first guess: output about as long as the input (it can reach twice that: one-byte pieces
-    # and their delimiters); once more with the exact size otherwise
-    cap = int(a.size + 64)
-    for _ in range(2):
-        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+
+    def call(buf, cap):
         _check(l.redgpu_extract_text(
             exe._h, a.ctypes.data if a.size else None, a.size, d, max_per_line, C.byref(nl),
-            C.byref(nm), C.byref(olen), buf.ctypes.data, cap))
-        if int(olen.value) <= cap:
-            break
-        cap = int(olen.value)
-    return int(nl.value), int(nm.value), buf[:int(olen.value)].tobytes()
+            C.byref(nm), C.byref(olen), buf, cap))
+        return olen.value
+
+    # first guess: output about as long as the input (it can reach twice that: one-byte pieces
+    # and their delimiters)
+    text = _host_text_out(a.size + 64, call)
+    return int(nl.value), int(nm.value), text
 
 
 def fields_mask(fields) -> int:
@@ -1596,7 +1570,7 @@ def fields_text(exe, data, fields, *, sep=b" ", max_fields=0, only_delimited=Fal
     read-back; out_len may exceed the room, bytes of out from min(out_len, room) on are
     untouched.  The output is a raw text that every text verb accepts."""
     l = _lib.lib()
-    d = delim[0] if isinstance(delim, (bytes, bytearray)) else int(delim)
+    d = _delim_byte(delim)
     select = fields_mask(fields)
     sep = bytes(sep)
     if len(sep) > 8:
@@ -1606,41 +1580,28 @@ def fields_text(exe, data, fields, *, sep=b" ", max_fields=0, only_delimited=Fal
     only = 1 if only_delimited else 0
     if _is_torch(data):
         import torch
-        if not data.is_cuda or data.dtype != torch.uint8 or not data.is_contiguous():
-            raise RedExceptApi("device input must be a contiguous uint8 CUDA tensor")
-        dev = data.device
-        if out is None and out_cap is None:
-            raise RedExceptApi("device fields_text needs out or out_cap (room for the output)")
-        if out is None:
-            out = torch.empty(int(out_cap), dtype=torch.uint8, device=dev)
-        elif (not _is_torch(out) or not out.is_cuda or out.dtype != torch.uint8 or
-              not out.is_contiguous() or out.device != dev):
-            raise RedExceptApi("out must be a contiguous uint8 CUDA tensor on the text's device")
-        room = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+        dev, ptr, size, stream = _device_raw_text(data)
+        out, room = _device_out_room("fields_text", data, out, out_cap)
         cnt = torch.empty(4, dtype=torch.int64, device=dev)
         _check(l.redgpu_fields_text_dev(
-            exe._h, data.data_ptr() if data.numel() else None, data.numel(), d, select, max_fields,
-            only, sep_word, len(sep), cnt.data_ptr(), cnt.data_ptr() + 8, cnt.data_ptr() + 16,
-            cnt.data_ptr() + 24, out.data_ptr() if room else None, room,
-            torch.cuda.current_stream(dev).cuda_stream))
+            exe._h, ptr, size, d, select, max_fields, only, sep_word, len(sep), cnt.data_ptr(),
+            cnt.data_ptr() + 8, cnt.data_ptr() + 16, cnt.data_ptr() + 24,
+            out.data_ptr() if room else None, room, stream))
         return cnt[0:1], cnt[1:2], cnt[2:3], cnt[3:4], out
-    if out is not None or out_cap is not None:
-        raise RedExceptApi("out= and out_cap= go with a CUDA tensor text")
+    _host_text_only(out, out_cap)
     a = _host_u8(data)
     nl, ne, nf, olen = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    # first guess: output about as long as the input (a long sep between short fields makes it
-    # longer); once more with the exact size otherwise
-    cap = int(a.size + 64)
-    for _ in range(2):
-        buf = np.zeros(max(cap, 1), dtype=np.uint8)
+
+    def call(buf, cap):
         _check(l.redgpu_fields_text(
             exe._h, a.ctypes.data if a.size else None, a.size, d, select, max_fields, only,
-            sep_word, len(sep), C.byref(nl), C.byref(ne), C.byref(nf), C.byref(olen),
-            buf.ctypes.data, cap))
-        if int(olen.value) <= cap:
-            break
-        cap = int(olen.value)
-    return int(nl.value), int(ne.value), int(nf.value), buf[:int(olen.value)].tobytes()
+            sep_word, len(sep), C.byref(nl), C.byref(ne), C.byref(nf), C.byref(olen), buf, cap))
+        return olen.value
+
+    # first guess: output about as long as the input (a long sep between short fields makes it
+    # longer)
+    text = _host_text_out(a.size + 64, call)
+    return int(nl.value), int(ne.value), int(nf.value), text
 
 
 class StatefulMatcher:
