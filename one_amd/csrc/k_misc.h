@@ -228,6 +228,17 @@ k_scan_fill(const uint64_t *lens, uint64_t n, const uint64_t *partials, uint64_t
   }
 }
 
+// that scan's three launches: values[n] into out[n + 1], over partials[ceil(n / 1024)]
+__host__ inline void launchScan64(const uint64_t *values, uint64_t n, uint64_t *partials,
+                                  uint64_t *out, hipStream_t stream) {
+  const uint64_t nPart = (n + 1023) / 1024;
+  hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(nPart)), dim3(256), 0, stream, values, n,
+                     partials);
+  hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, partials, nPart);
+  hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(nPart)), dim3(256), 0, stream, values, n, partials,
+                     out);
+}
+
 // Visit histogram for redgpu_dfa_tune: the anchored walk of match<styLast,false> over every
 // line of a SAMPLE, hist[state] += 1 per byte consumed.  A profiling pass, not a hot path:
 // plain global atomics.

@@ -303,3 +303,16 @@ __host__ inline uint32_t textBlocks(uint64_t nChunks, size_t ldsBytes, int threa
   const uint64_t blocks = (nChunks + waves - 1) / waves;
   return uint32_t(blocks > most ? most : blocks);
 }
+
+// ... of a pass without a table: a wave per chunk, four to a workgroup, at most 8 per CU
+__host__ inline uint32_t smallBlocks(uint64_t nChunks, int numCUs) {
+  const uint64_t blocks = (nChunks + 3) / 4, most = uint64_t(numCUs) * 8;
+  return uint32_t(blocks > most ? most : blocks);
+}
+
+// ... and of a pass over `words` words (zeroing, the passes over uniq_text's table): 256 to a
+// workgroup, at most 8 per CU; 0 for no words
+__host__ inline uint32_t wordBlocks(uint64_t words, int numCUs) {
+  const uint64_t blocks = (words + 255) / 256, most = uint64_t(numCUs) * 8;
+  return uint32_t(blocks > most ? most : blocks);
+}

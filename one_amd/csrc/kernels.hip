@@ -39,7 +39,7 @@
 //                     order, the lowest success wins (atomic min), windows in text order and an
 //                     early exit, bounded attempts and a serial finish
 //   k_style_blocks.h  k_style_blocks: early-exit styles and odd strides over the block walk
-//   k_misc.h          k_advance, k_replace (+ scan), k_visits, k_walked
+//   k_misc.h          k_advance, k_replace (+ the 64-bit scan, launchScan64), k_visits, k_walked
 //   k_split.h         line splitting on the device
 //   k_text.h          what the raw-text verbs share: the bitmap views, the line index (k_gp_last,
 //                     k_gp_open), the line walk, the hit-line lookup, launch geometry
@@ -172,6 +172,47 @@ namespace {
          d.clsBytes <= (d.clsIndexForm ? kStreamBigLds : kStreamTabBytes + 1024);
 }
 
+// lines that are whole blocks of `unit` bytes at a fixed stride below 2 GiB, from a 16-byte
+// aligned base: what k_stream (unit 64) and k_fixed (unit 16) load
+[[maybe_unused]] static bool wholeBlocks(const Batch &b, uint64_t unit) {
+  return !b.offsets && b.stride >= unit && b.stride % unit == 0 && b.stride < (1ull << 31) &&
+         (reinterpret_cast<uintptr_t>(b.data) % 16) == 0;
+}
+
+[[maybe_unused]] static bool lastOrFull(int style) { return style == kStyLast || style == kStyFull; }
+
+// check / match under styLast / styFull: the whole-line walks of k_stream and k_ragged
+[[maybe_unused]] static bool wholeLineWalk(int verb, int style) {
+  return (verb == kCheck || verb == kMatch) && lastOrFull(style);
+}
+
+// the StreamMode of such a walk
+[[maybe_unused]] static int streamMode(int style, bool wantStart) {
+  return style == kStyLast ? (wantStart ? kSmLastStartEnd : kSmLastEnd)
+                           : (wantStart ? kSmFullStart : kSmFull);
+}
+
+// the batch as check's kernels see it: no positions to store
+[[maybe_unused]] static Batch withoutPositions(const Batch &b, int verb) {
+  Batch sb = b;
+  if (verb == kCheck) { sb.start = nullptr; sb.end = nullptr; }
+  return sb;
+}
+
+// return CALL(MODE) for the StreamMode `mode` in scope (kSmAdvance and kSmChunk have call sites of
+// their own)
+#define REDGPU_MODE_SWITCH(CALL)                                                          \
+  switch (mode) {                                                                         \
+  case kSmLastStartEnd: return CALL(kSmLastStartEnd);                                     \
+  case kSmLastEnd: return CALL(kSmLastEnd);                                               \
+  case kSmFullStart: return CALL(kSmFullStart);                                           \
+  default: return CALL(kSmFull);                                                          \
+  }
+
+// The kernel names, by StreamMode (2 is no mode) and by table form: kTabFused, kTabHot, kTabCls -
+// kTabClsBig runs under kTabCls's name (nameForm).
+[[maybe_unused]] static int nameForm(int tabk) { return tabk == kTabClsBig ? kTabCls : tabk; }
+
 #if REDGPU_TU_GENERIC
 bool fastPathEligible(const DevDfa &d) {
   return d.tableKind == REDGPU_TAB_LDS_FUSED_U8 && d.deadAbsorbing &&
@@ -180,52 +221,69 @@ bool fastPathEligible(const DevDfa &d) {
 #endif
 
 #if REDGPU_TU_STREAM
+static const char *const kStreamNames[5][3] = {
+    {"k_stream<last,start,end>", "k_stream<last,start,end,hot>", "k_stream<last,start,end,cls>"},
+    {"k_stream<last,end>", "k_stream<last,end,hot>", "k_stream<last,end,cls>"},
+    {},
+    {"k_stream<full,start>", "k_stream<full,start,hot>", "k_stream<full,start,cls>"},
+    {"k_stream<full>", "k_stream<full,hot>", "k_stream<full,cls>"}};
+static const char *const kStream4Names[5] = {"k_stream4<last,start,end>", "k_stream4<last,end>",
+                                             nullptr, "k_stream4<full,start>", "k_stream4<full>"};
+// ([mode][lean]; kSmFull has no lean step, launchStreamMultiT)
+static const char *const kStreamMultiNames[5][2] = {
+    {"k_stream_multi<last,start,end>", "k_stream_multi<last,start,end,lean>"},
+    {"k_stream_multi<last,end>", "k_stream_multi<last,end,lean>"},
+    {},
+    {"k_stream_multi<full,start>", "k_stream_multi<full,start,lean>"},
+    {"k_stream_multi<full>", "k_stream_multi<full>"}};
+
+// k_stream<mode> over the table form tabk
+static hipError_t launchStreamMode(int mode, int tabk, const DevDfa &d, const Batch &b,
+                                   const LaunchCfg &cfg, hipStream_t stream) {
+#define SM_FUSED(M) launchStreamT<M>(d, b, cfg, stream)
+#define SM_HOT(M) launchStreamHot<M, kTabHot>(d, b, cfg, stream)
+#define SM_CLS(M) launchStreamHot<M, kTabCls>(d, b, cfg, stream)
+#define SM_CLS_BIG(M) launchStreamHot<M, kTabClsBig>(d, b, cfg, stream)
+  switch (tabk) {
+  case kTabFused: REDGPU_MODE_SWITCH(SM_FUSED)
+  case kTabHot: REDGPU_MODE_SWITCH(SM_HOT)
+  case kTabCls: REDGPU_MODE_SWITCH(SM_CLS)
+  default: REDGPU_MODE_SWITCH(SM_CLS_BIG)
+  }
+#undef SM_CLS_BIG
+#undef SM_CLS
+#undef SM_HOT
+#undef SM_FUSED
+}
+
 // StatefulMatcher chunks the streaming kernels can take (k_stream<advance...>); *handled says so
 hipError_t launchAdvanceStream(const DevDfa &d, const Batch &b, uint32_t *state,
                                const LaunchCfg &cfg, hipStream_t stream, const char **kernelName,
                                bool *handled) {
   *handled = false;
   // chunks that are whole 64-byte blocks at a fixed stride: the streaming kernel
-  if (!cfg.forceGeneric && fastPathEligible(d) && !b.offsets && b.stride >= 64 &&
-      b.stride % 64 == 0 && b.stride < (1ull << 31) &&
-      (reinterpret_cast<uintptr_t>(b.data) % 16) == 0 && d.tableBytes <= kStreamTabBytes &&
-      d.nStates <= 256) {
+  if (cfg.forceGeneric || !wholeBlocks(b, 64)) return hipSuccess;
+  const bool fused = fastPathEligible(d) && d.tableBytes <= kStreamTabBytes && d.nStates <= 256;
+  const bool cls = !fused && clsStreamEligible(d);
+  if (!fused && !cls && !hotStreamEligible(d)) return hipSuccess;
+  Batch sb = b;
+  sb.state = state;
+  sb.start = nullptr;
+  sb.end = nullptr;
+  *handled = true;
+  if (fused) {
     *kernelName = "k_stream<advance>";
-    Batch sb = b;
-    sb.state = state;
-    sb.start = nullptr;
-    sb.end = nullptr;
-    *handled = true;
     return launchStreamT<kSmAdvance>(d, sb, cfg, stream);
   }
-  if (!cfg.forceGeneric && clsStreamEligible(d) && !b.offsets && b.stride >= 64 &&
-      b.stride % 64 == 0 && b.stride < (1ull << 31) &&
-      (reinterpret_cast<uintptr_t>(b.data) % 16) == 0) {
+  if (cls) {
     *kernelName = "k_stream<advance,cls>";
-    Batch sb = b;
-    sb.state = state;
-    sb.start = nullptr;
-    sb.end = nullptr;
-    *handled = true;
     return d.clsIndexForm ? launchStreamHot<kSmAdvance, kTabClsBig>(d, sb, cfg, stream)
                           : launchStreamHot<kSmAdvance, kTabCls>(d, sb, cfg, stream);
   }
-  if (!cfg.forceGeneric && hotStreamEligible(d) && !b.offsets && b.stride >= 64 &&
-      b.stride % 64 == 0 && b.stride < (1ull << 31) &&
-      (reinterpret_cast<uintptr_t>(b.data) % 16) == 0) {
-    *kernelName = "k_stream<advance,hot>";
-    Batch sb = b;
-    sb.state = state;
-    sb.start = nullptr;
-    sb.end = nullptr;
-    *handled = true;
-    return launchStreamHot<kSmAdvance>(d, sb, cfg, stream);
-  }
-  return hipSuccess;
+  *kernelName = "k_stream<advance,hot>";
+  return launchStreamHot<kSmAdvance>(d, sb, cfg, stream);
 }
-#endif  // REDGPU_TU_STREAM
 
-#if REDGPU_TU_STREAM
 // The fixed-stride family of launchBatch: speculative chunks, k_stream (fused / hot / class
 // table), k_fixed.  *handled = false: not this family's batch.
 hipError_t launchStreamBatches(const DevDfa &d, const Batch *bs, uint32_t nb, int verb, int style,
@@ -237,135 +295,75 @@ hipError_t launchFixedFamily(const DevDfa &d, const Batch &b, int verb, int styl
   *handled = true;
   const bool lead = doLeader && d.leaderLen > 0;
   const bool dying = d.earlyDeath && !cfg.forceStream;
+  const bool leadCheck = lead && verb == kCheck;
   // Fixed-stride hot path: check / match, whole 16-byte multiples, 16-byte aligned base.
   // check<.., true> consumes the leader and starts in the post-leader state at byte
   // leaderLen (Matcher.h:370-375); match only peeks it (Matcher.h:424-435).
-  const bool fixedOk = !cfg.forceGeneric && !dying && fastPathEligible(d) && !b.offsets &&
-                       (verb == kCheck || verb == kMatch) && b.stride >= 16 &&
-                       b.stride % 16 == 0 && b.stride < (1ull << 31) &&
-                       (reinterpret_cast<uintptr_t>(b.data) % 16) == 0 &&
-                       !(lead && verb == kCheck);
+  const bool fixedOk = !cfg.forceGeneric && !dying && fastPathEligible(d) &&
+                       (verb == kCheck || verb == kMatch) && wholeBlocks(b, 16) && !leadCheck;
   // ... and check<styLast / styFull, true> when the leader is the table's own forced chain
   // (dfa_image.h: leaderForced): the plain walk from the initial state, deaf to whatever accepts
   // up to the leader's end (a line that IS the leader would report the post-leader state's
-  // result: left to k_generic)
-  const bool leadCheckOk = lead && verb == kCheck && d.leaderForced && b.stride > d.leaderLen &&
-                           (style == kStyLast || style == kStyFull) && !cfg.forceGeneric && !dying &&
-                           fastPathEligible(d) && !b.offsets && b.stride % 64 == 0 &&
-                           b.stride < (1ull << 31) && (reinterpret_cast<uintptr_t>(b.data) % 16) == 0;
+  // result: left to k_generic).  (wholeBlocks' stride >= 64 says nothing new here: a multiple of
+  // 64 above leaderLen > 0.)
+  const bool leadCheckOk = leadCheck && d.leaderForced && b.stride > d.leaderLen &&
+                           lastOrFull(style) && !cfg.forceGeneric && !dying &&
+                           fastPathEligible(d) && wholeBlocks(b, 64);
   // Streaming kernel: styles Last / Full on lines that are whole 64-byte blocks.
-  const bool streamOk = (fixedOk || leadCheckOk) && (style == kStyLast || style == kStyFull) &&
-                        b.stride % 64 == 0 && d.tableBytes <= kStreamTabBytes && d.nStates <= 256;
+  const bool streamOk = (fixedOk || leadCheckOk) && lastOrFull(style) && b.stride % 64 == 0 &&
+                        d.tableBytes <= kStreamTabBytes && d.nStates <= 256;
   // The same streaming walk for DFAs too big for LDS: hot rows as a one-byte-indexed table,
   // cold excursions re-walked per 64-byte half-block (k_stream.h, HOT).
-  const bool hotStreamOk = !cfg.forceGeneric && !dying && hotStreamEligible(d) && !b.offsets &&
-                           (verb == kCheck || verb == kMatch) &&
-                           (style == kStyLast || style == kStyFull) && b.stride >= 64 &&
-                           b.stride % 64 == 0 && b.stride < (1ull << 31) &&
-                           (reinterpret_cast<uintptr_t>(b.data) % 16) == 0 &&
-                           !(lead && verb == kCheck);
+  const bool hotStreamOk = !cfg.forceGeneric && !dying && hotStreamEligible(d) &&
+                           wholeLineWalk(verb, style) && wholeBlocks(b, 64) && !leadCheck;
   // ... and for mid-size DFAs whose class table fits 64 KB of LDS (two lookups per byte)
-  const bool clsStreamOk = !cfg.forceGeneric && !dying && clsStreamEligible(d) && !b.offsets &&
-                           (verb == kCheck || verb == kMatch) &&
-                           (style == kStyLast || style == kStyFull) && b.stride >= 64 &&
-                           b.stride % 64 == 0 && b.stride < (1ull << 31) &&
-                           (reinterpret_cast<uintptr_t>(b.data) % 16) == 0 &&
-                           !(lead && verb == kCheck);
+  const bool clsStreamOk = !cfg.forceGeneric && !dying && clsStreamEligible(d) &&
+                           wholeLineWalk(verb, style) && wholeBlocks(b, 64) && !leadCheck;
   // Few long lines over a DFA that forgets its past: chunks of every line walked at once from
   // the initial state as a guess, wrong guesses re-walked (k_chunk.h)
-  const bool leadCheck = lead && verb == kCheck;  // (only ever true here with leadCheckOk)
+  // (leadCheck is only ever true here with leadCheckOk)
   if ((streamOk || hotStreamOk || clsStreamOk) && !cfg.noChunking && !leadCheck &&
       (d.forgetful || cfg.forceChunking) &&
       (fewLines(b, cfg) || cfg.forceChunking)) {
     const uint32_t m = chunksPerLine(b, cfg);
     if (m) {
-      Batch sb = b;
-      if (verb == kCheck) { sb.start = nullptr; sb.end = nullptr; }
       *kernelName = d.tableKind == REDGPU_TAB_HOT_ROWS ? "k_stream<chunk,hot>+k_chunk"
                     : d.tableKind == REDGPU_TAB_LDS_FUSED_U8 ? "k_stream<chunk>+k_chunk"
                                                              : "k_stream<chunk,cls>+k_chunk";
-      hipError_t e = launchChunked(d, sb, m, style, cfg, stream);
+      hipError_t e = launchChunked(d, withoutPositions(b, verb), m, style, cfg, stream);
       if (e != hipSuccess) return e;
-      if (lead) {
-        hipLaunchKernelGGL(k_leader_filter, dim3(uint32_t(cfg.numCUs) * 8), dim3(256), 0, stream,
-                           d, b);
-        return hipGetLastError();
+      return lead ? launchLeaderFilter(d, b, cfg, stream) : hipSuccess;
+    }
+  }
+  // k_stream over the fused table, else the hot rows, else the class table
+  if (streamOk || hotStreamOk || clsStreamOk) {
+    const int tabk = streamOk      ? kTabFused
+                     : hotStreamOk ? kTabHot
+                                   : (d.clsIndexForm ? kTabClsBig : kTabCls);
+    Batch sb = withoutPositions(b, verb);
+    const int mode = streamMode(style, sb.start != nullptr);
+    hipError_t e;
+    if (streamOk) {
+      if (leadCheck) sb.ignoreAcceptUpTo = d.leaderLen;
+      static const int labLean = multiLabInt("REDGPU_LEAN", 0, 1, 0);
+      static const int labSingle = multiLabInt("REDGPU_MULTI_SINGLE", 0, 1, 0);
+      if (cfg.forceLean || labLean || labSingle) {
+        // opt-in: k_stream_multi (its deferred-bookkeeping form for long lines) for a batch on its own
+        uint32_t taken = 0;
+        e = launchStreamBatches(d, &b, 1, verb, style, doLeader, cfg, stream, kernelName, &taken);
+        if (e != hipSuccess || taken) return e;
       }
-      return hipSuccess;
     }
-  }
-  if (streamOk) {
-    hipError_t e;
-    Batch sb = b;
-    if (verb == kCheck) { sb.start = nullptr; sb.end = nullptr; }
-    if (leadCheck) sb.ignoreAcceptUpTo = d.leaderLen;
-    static const int labLean = multiLabInt("REDGPU_LEAN", 0, 1, 0);
-    static const int labSingle = multiLabInt("REDGPU_MULTI_SINGLE", 0, 1, 0);
-    if (cfg.forceLean || labLean || labSingle) {
-      // opt-in: k_stream_multi (its deferred-bookkeeping form for long lines) for a batch on its own
-      uint32_t taken = 0;
-      e = launchStreamBatches(d, &b, 1, verb, style, doLeader, cfg, stream, kernelName, &taken);
-      if (e != hipSuccess || taken) return e;
-    }
-    if (!leadCheck && stream4Eligible(d, sb, cfg)) {
-      const int mode = style == kStyLast ? (sb.start ? kSmLastStartEnd : kSmLastEnd)
-                                         : (sb.start ? kSmFullStart : kSmFull);
-      *kernelName = style == kStyLast ? (sb.start ? "k_stream4<last,start,end>" : "k_stream4<last,end>")
-                                      : (sb.start ? "k_stream4<full,start>" : "k_stream4<full>");
+    if (streamOk && !leadCheck && stream4Eligible(d, sb, cfg)) {
+      *kernelName = kStream4Names[mode];
       e = launchStream4(mode, d, sb, cfg, stream);
-    } else
-    if (style == kStyLast) {
-      if (sb.start) { *kernelName = "k_stream<last,start,end>"; e = launchStreamT<kSmLastStartEnd>(d, sb, cfg, stream); }
-      else { *kernelName = "k_stream<last,end>"; e = launchStreamT<kSmLastEnd>(d, sb, cfg, stream); }
     } else {
-      if (sb.start) { *kernelName = "k_stream<full,start>"; e = launchStreamT<kSmFullStart>(d, sb, cfg, stream); }
-      else { *kernelName = "k_stream<full>"; e = launchStreamT<kSmFull>(d, sb, cfg, stream); }
+      *kernelName = kStreamNames[mode][nameForm(tabk)];
+      e = launchStreamMode(mode, tabk, d, sb, cfg, stream);
     }
     if (e != hipSuccess) return e;
-    if (lead && !leadCheck) {
-      hipLaunchKernelGGL(k_leader_filter, dim3(uint32_t(cfg.numCUs) * 8), dim3(256), 0, stream,
-                         d, b);
-      return hipGetLastError();
-    }
-    return hipSuccess;
-  }
-  if (hotStreamOk) {
-    hipError_t e;
-    Batch sb = b;
-    if (verb == kCheck) { sb.start = nullptr; sb.end = nullptr; }
-    if (style == kStyLast) {
-      if (sb.start) { *kernelName = "k_stream<last,start,end,hot>"; e = launchStreamHot<kSmLastStartEnd>(d, sb, cfg, stream); }
-      else { *kernelName = "k_stream<last,end,hot>"; e = launchStreamHot<kSmLastEnd>(d, sb, cfg, stream); }
-    } else {
-      if (sb.start) { *kernelName = "k_stream<full,start,hot>"; e = launchStreamHot<kSmFullStart>(d, sb, cfg, stream); }
-      else { *kernelName = "k_stream<full,hot>"; e = launchStreamHot<kSmFull>(d, sb, cfg, stream); }
-    }
-    if (e != hipSuccess) return e;
-    if (lead) {
-      hipLaunchKernelGGL(k_leader_filter, dim3(uint32_t(cfg.numCUs) * 8), dim3(256), 0, stream,
-                         d, b);
-      return hipGetLastError();
-    }
-    return hipSuccess;
-  }
-  if (clsStreamOk) {
-    hipError_t e;
-    Batch sb = b;
-    if (verb == kCheck) { sb.start = nullptr; sb.end = nullptr; }
-    if (style == kStyLast) {
-      if (sb.start) { *kernelName = "k_stream<last,start,end,cls>"; e = d.clsIndexForm ? launchStreamHot<kSmLastStartEnd, kTabClsBig>(d, sb, cfg, stream) : launchStreamHot<kSmLastStartEnd, kTabCls>(d, sb, cfg, stream); }
-      else { *kernelName = "k_stream<last,end,cls>"; e = d.clsIndexForm ? launchStreamHot<kSmLastEnd, kTabClsBig>(d, sb, cfg, stream) : launchStreamHot<kSmLastEnd, kTabCls>(d, sb, cfg, stream); }
-    } else {
-      if (sb.start) { *kernelName = "k_stream<full,start,cls>"; e = d.clsIndexForm ? launchStreamHot<kSmFullStart, kTabClsBig>(d, sb, cfg, stream) : launchStreamHot<kSmFullStart, kTabCls>(d, sb, cfg, stream); }
-      else { *kernelName = "k_stream<full,cls>"; e = d.clsIndexForm ? launchStreamHot<kSmFull, kTabClsBig>(d, sb, cfg, stream) : launchStreamHot<kSmFull, kTabCls>(d, sb, cfg, stream); }
-    }
-    if (e != hipSuccess) return e;
-    if (lead) {
-      hipLaunchKernelGGL(k_leader_filter, dim3(uint32_t(cfg.numCUs) * 8), dim3(256), 0, stream,
-                         d, b);
-      return hipGetLastError();
-    }
-    return hipSuccess;
+    // (check with the leader ran as the walk itself: nothing to filter)
+    return lead && !leadCheck ? launchLeaderFilter(d, b, cfg, stream) : hipSuccess;
   }
   if (fixedOk) {
     hipError_t e;
@@ -380,12 +378,7 @@ hipError_t launchFixedFamily(const DevDfa &d, const Batch &b, int verb, int styl
       e = launchFixedS<true, false>(style, d, b, 0, d.init, cfg, stream);
     }
     if (e != hipSuccess) return e;
-    if (lead) {
-      hipLaunchKernelGGL(k_leader_filter, dim3(uint32_t(cfg.numCUs) * 8), dim3(256), 0, stream,
-                         d, b);
-      return hipGetLastError();
-    }
-    return hipSuccess;
+    return lead ? launchLeaderFilter(d, b, cfg, stream) : hipSuccess;
   }
 
   *handled = false;
@@ -403,16 +396,15 @@ hipError_t launchStreamBatches(const DevDfa &d, const Batch *bs, uint32_t nb, in
   const bool lead = doLeader && d.leaderLen > 0;
   const bool dying = d.earlyDeath && !cfg.forceStream;
   if (cfg.forceGeneric || cfg.forceEarly || cfg.forceChunking || dying || !fastPathEligible(d) ||
-      !(verb == kCheck || verb == kMatch) || !(style == kStyLast || style == kStyFull) ||
-      (lead && verb == kCheck) || d.tableBytes > kStreamTabBytes || d.nStates > 256)
+      !wholeLineWalk(verb, style) || (lead && verb == kCheck) ||
+      d.tableBytes > kStreamTabBytes || d.nStates > 256)
     return hipSuccess;
   auto plain = [&](const Batch &b) {
     // (few long lines over a forgetful DFA are launchFixedFamily's speculative chunks)
     const bool chunky = fewLines(b, cfg) && d.forgetful && !cfg.noChunking && b.stride >= 4096 &&
                         !cfg.forceLean;
-    return !b.offsets && b.stride >= 64 && b.stride % 64 == 0 && b.stride < (1ull << 31) &&
-           (reinterpret_cast<uintptr_t>(b.data) % 16) == 0 && b.n > 0 && !chunky &&
-           b.n < (1ull << 40) && !stream4Eligible(d, b, cfg);
+    return wholeBlocks(b, 64) && b.n > 0 && !chunky && b.n < (1ull << 40) &&
+           !stream4Eligible(d, b, cfg);
   };
   const bool wantStart = verb == kMatch && bs[0].start;
   MultiIo m;
@@ -438,27 +430,21 @@ hipError_t launchStreamBatches(const DevDfa &d, const Batch *bs, uint32_t nb, in
   // (one batch on its own keeps k_stream - unless its lines are long enough for the lean step,
   // or the lab says otherwise: REDGPU_MULTI_SINGLE=1)
   static const int labSingle = multiLabInt("REDGPU_MULTI_SINGLE", 0, 1, 0);
-  const bool lean = leanWanted(m, cfg) && !(style == kStyFull && !wantStart);
+  const int mode = streamMode(style, wantStart);
+  const bool lean = leanWanted(m, cfg) && mode != kSmFull;
   if (m.nb < ((labSingle || lean) ? 1u : 2u) ||
       (m.tileStart[m.nb] < uint32_t(cfg.numCUs) && !(lean && cfg.forceLean)))
     return hipSuccess;
   for (uint32_t k = m.nb; k < uint32_t(kMultiMax); ++k) m.tileStart[k + 1] = m.tileStart[m.nb];
-  hipError_t e;
-  if (style == kStyLast) {
-    if (wantStart) { *kernelName = lean ? "k_stream_multi<last,start,end,lean>" : "k_stream_multi<last,start,end>"; e = launchStreamMultiT<kSmLastStartEnd>(d, m, cfg, stream); }
-    else { *kernelName = lean ? "k_stream_multi<last,end,lean>" : "k_stream_multi<last,end>"; e = launchStreamMultiT<kSmLastEnd>(d, m, cfg, stream); }
-  } else {
-    if (wantStart) { *kernelName = lean ? "k_stream_multi<full,start,lean>" : "k_stream_multi<full,start>"; e = launchStreamMultiT<kSmFullStart>(d, m, cfg, stream); }
-    else { *kernelName = "k_stream_multi<full>"; e = launchStreamMultiT<kSmFull>(d, m, cfg, stream); }
-  }
+  *kernelName = kStreamMultiNames[mode][lean ? 1 : 0];
+#define MU_CALL(M) launchStreamMultiT<M>(d, m, cfg, stream)
+  hipError_t e = [&]() -> hipError_t { REDGPU_MODE_SWITCH(MU_CALL) }();
+#undef MU_CALL
   if (e != hipSuccess) return e;
   if (lead) {
     // match<..., true> only peeks the leader (Matcher.h:424-435): lines that fail it report {0,0,0}
-    for (uint32_t k = 0; k < m.nb; ++k) {
-      hipLaunchKernelGGL(k_leader_filter, dim3(uint32_t(cfg.numCUs) * 8), dim3(256), 0, stream, d,
-                         bs[k]);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    for (uint32_t k = 0; k < m.nb; ++k)
+      if ((e = launchLeaderFilter(d, bs[k], cfg, stream)) != hipSuccess) return e;
   }
   *taken = m.nb;
   return hipSuccess;
@@ -466,80 +452,68 @@ hipError_t launchStreamBatches(const DevDfa &d, const Batch *bs, uint32_t nb, in
 #endif  // REDGPU_TU_STREAM
 
 #if REDGPU_TU_RAGGED
+static const char *const kRaggedNames[5][3] = {
+    {"k_ragged<last,start,end>", "k_ragged<last,start,end,hot>", "k_ragged<last,start,end,cls>"},
+    {"k_ragged<last,end>", "k_ragged<last,end,hot>", "k_ragged<last,end,cls>"},
+    {},
+    {"k_ragged<full,start>", "k_ragged<full,start,hot>", "k_ragged<full,start,cls>"},
+    {"k_ragged<full>", "k_ragged<full,hot>", "k_ragged<full,cls>"}};
+
+// k_ragged<mode> over the table form tabk
+static hipError_t launchRaggedMode(int mode, int tabk, const DevDfa &d, const Batch &b,
+                                   const LaunchCfg &cfg, hipStream_t stream) {
+#define RG_FUSED(M) launchRaggedT<M, kTabFused>(d, b, cfg, stream)
+#define RG_HOT(M) launchRaggedT<M, kTabHot>(d, b, cfg, stream)
+#define RG_CLS(M) launchRaggedT<M, kTabCls>(d, b, cfg, stream)
+#define RG_CLS_BIG(M) launchRaggedT<M, kTabClsBig>(d, b, cfg, stream)
+  switch (tabk) {
+  case kTabFused: REDGPU_MODE_SWITCH(RG_FUSED)
+  case kTabHot: REDGPU_MODE_SWITCH(RG_HOT)
+  case kTabCls: REDGPU_MODE_SWITCH(RG_CLS)
+  default: REDGPU_MODE_SWITCH(RG_CLS_BIG)
+  }
+#undef RG_CLS_BIG
+#undef RG_CLS
+#undef RG_HOT
+#undef RG_FUSED
+}
+
 // The ragged family of launchBatch: k_ragged over the fused, hot-row and class tables.
 hipError_t launchRaggedFamily(const DevDfa &d, const Batch &b, int verb, int style, int doLeader,
                               const LaunchCfg &cfg, hipStream_t stream, const char **kernelName,
                               bool *handled) {
-  *handled = true;
+  *handled = false;
   const bool lead = doLeader && d.leaderLen > 0;
   const bool dying = d.earlyDeath && !cfg.forceStream;
-  // Ragged lines, fused-u8 table, styles Last / Full of check / match, no leader to honour:
-  // k_ragged walks every line; blocks that would reach past the end of the buffer come from a
-  // padded copy of its last bytes.
-  const bool raggedOk = !cfg.forceGeneric && !dying && fastPathEligible(d) && b.offsets &&
-                        b.n < (1ull << 32) &&
-                        (verb == kCheck || verb == kMatch) &&
-                        (style == kStyLast || style == kStyFull) && !lead &&
-                        d.tableBytes <= kStreamTabBytes && d.nStates <= 256;
-  if (raggedOk) {
-    hipError_t e;
-    Batch sb = b;
-    if (verb == kCheck) { sb.start = nullptr; sb.end = nullptr; }
-    if (style == kStyLast) {
-      if (sb.start) { *kernelName = "k_ragged<last,start,end>"; e = launchRaggedT<kSmLastStartEnd>(d, sb, cfg, stream); }
-      else { *kernelName = "k_ragged<last,end>"; e = launchRaggedT<kSmLastEnd>(d, sb, cfg, stream); }
-    } else {
-      if (sb.start) { *kernelName = "k_ragged<full,start>"; e = launchRaggedT<kSmFullStart>(d, sb, cfg, stream); }
-      else { *kernelName = "k_ragged<full>"; e = launchRaggedT<kSmFull>(d, sb, cfg, stream); }
-    }
-    return e;
-  }
-
+  // Ragged lines, styles Last / Full of check / match, no leader to honour: k_ragged walks every
+  // line; blocks that would reach past the end of the buffer come from a padded copy of its last
+  // bytes.
+  if (cfg.forceGeneric || dying || !b.offsets || b.n >= (1ull << 32) ||
+      !wholeLineWalk(verb, style) || lead)
+    return hipSuccess;
+  // The fused-u8 table ...
+  const bool raggedOk =
+      fastPathEligible(d) && d.tableBytes <= kStreamTabBytes && d.nStates <= 256;
   // ... and the same for DFAs too big for LDS (hot rows, cold excursions re-walked per block).
   // On ragged text matches sit at any offset, so with the create-time ranking some lane of a
   // wave is in a cold excursion in nearly every block and the re-walks dominate (URI-V6 on
   // geometric-length text with a URL every ~8 lines: 128 GB/s untuned, 556 GB/s after
   // redgpu_dfa_tune) - still ahead of k_generic on the same lines (98 GB/s: its one-line-per-
   // lane walk also pays the wave-max of the line lengths); without URLs 629 vs 107 GB/s.
-  const bool hotRaggedOk = !cfg.forceGeneric && !dying && hotStreamEligible(d) && b.offsets &&
-                           b.n < (1ull << 32) &&
-                           (verb == kCheck || verb == kMatch) &&
-                           (style == kStyLast || style == kStyFull) && !lead;
-  if (hotRaggedOk) {
-    Batch sb = b;
-    if (verb == kCheck) { sb.start = nullptr; sb.end = nullptr; }
-    if (style == kStyLast) {
-      if (sb.start) { *kernelName = "k_ragged<last,start,end,hot>"; return launchRaggedT<kSmLastStartEnd, kTabHot>(d, sb, cfg, stream); }
-      *kernelName = "k_ragged<last,end,hot>";
-      return launchRaggedT<kSmLastEnd, kTabHot>(d, sb, cfg, stream);
-    }
-    if (sb.start) { *kernelName = "k_ragged<full,start,hot>"; return launchRaggedT<kSmFullStart, kTabHot>(d, sb, cfg, stream); }
-    *kernelName = "k_ragged<full,hot>";
-    return launchRaggedT<kSmFull, kTabHot>(d, sb, cfg, stream);
-  }
-
+  const bool hotRaggedOk = !raggedOk && hotStreamEligible(d);
   // ... and for mid-size DFAs with a class table of at most 64 KB
-  const bool clsRaggedOk = !cfg.forceGeneric && !dying && clsStreamEligible(d) && b.offsets &&
-                           b.n < (1ull << 32) &&
-                           (verb == kCheck || verb == kMatch) &&
-                           (style == kStyLast || style == kStyFull) && !lead;
-  if (clsRaggedOk) {
-    Batch sb = b;
-    if (verb == kCheck) { sb.start = nullptr; sb.end = nullptr; }
-    if (style == kStyLast) {
-      if (sb.start) { *kernelName = "k_ragged<last,start,end,cls>"; return d.clsIndexForm ? launchRaggedT<kSmLastStartEnd, kTabClsBig>(d, sb, cfg, stream) : launchRaggedT<kSmLastStartEnd, kTabCls>(d, sb, cfg, stream); }
-      *kernelName = "k_ragged<last,end,cls>";
-      return d.clsIndexForm ? launchRaggedT<kSmLastEnd, kTabClsBig>(d, sb, cfg, stream) : launchRaggedT<kSmLastEnd, kTabCls>(d, sb, cfg, stream);
-    }
-    if (sb.start) { *kernelName = "k_ragged<full,start,cls>"; return d.clsIndexForm ? launchRaggedT<kSmFullStart, kTabClsBig>(d, sb, cfg, stream) : launchRaggedT<kSmFullStart, kTabCls>(d, sb, cfg, stream); }
-    *kernelName = "k_ragged<full,cls>";
-    return d.clsIndexForm ? launchRaggedT<kSmFull, kTabClsBig>(d, sb, cfg, stream) : launchRaggedT<kSmFull, kTabCls>(d, sb, cfg, stream);
-  }
-
-  *handled = false;
-  return hipSuccess;
+  if (!raggedOk && !hotRaggedOk && !clsStreamEligible(d)) return hipSuccess;
+  const int tabk = raggedOk      ? kTabFused
+                   : hotRaggedOk ? kTabHot
+                                 : (d.clsIndexForm ? kTabClsBig : kTabCls);
+  const Batch sb = withoutPositions(b, verb);
+  const int mode = streamMode(style, sb.start != nullptr);
+  *handled = true;
+  *kernelName = kRaggedNames[mode][nameForm(tabk)];
+  return launchRaggedMode(mode, tabk, d, sb, cfg, stream);
 }
 #endif  // REDGPU_TU_RAGGED
+
 
 #if REDGPU_TU_GENERIC
 hipError_t launchCollect(const DevDfa &d, const Batch &b, uint64_t cap, uint64_t *counts,
@@ -825,11 +799,7 @@ hipError_t launchReplace(const DevDfa &d, const Batch &b, int style, int doLeade
   e = launchReplacePass(d, b, style, lead, repl, replLen, max, counts, lens, nullptr, nullptr, 0,
                         cfg, stream);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(nPart)), dim3(256), 0, stream, lens, b.n,
-                     partials);
-  hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, partials, nPart);
-  hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(nPart)), dim3(256), 0, stream, lens, b.n, partials,
-                     outOffsets);
+  launchScan64(lens, b.n, partials, outOffsets, stream);
   e = hipGetLastError();
   if (e != hipSuccess || !out) return e;
   return launchReplacePass(d, b, style, lead, repl, replLen, max, counts, lens, outOffsets, out,
@@ -873,10 +843,8 @@ hipError_t launchTextIndex(const uint8_t *data, uint64_t len, uint8_t delim, uin
   hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, counts, nChunks, bases,
                      nLines ? nLines : spare, spare + 1, uint64_t(0));
   if (nChunks) {
-    uint64_t small = (nChunks + 3) / 4;
-    if (small > uint64_t(numCUs) * 8) small = uint64_t(numCUs) * 8;
-    hipLaunchKernelGGL(k_gp_last, dim3(uint32_t(small)), dim3(256), 0, stream, masks, counts,
-                       nChunks, open, zeroMasks);
+    hipLaunchKernelGGL(k_gp_last, dim3(smallBlocks(nChunks, numCUs)), dim3(256), 0, stream, masks,
+                       counts, nChunks, open, zeroMasks);
     hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, open, nChunks);
   }
   return hipGetLastError();
@@ -988,6 +956,33 @@ hipError_t launchAdvance(const DevDfa &d, const Batch &b, uint32_t *state, const
     style = kStyLast;
 }
 
+// A line verb of the raw-text family (does this line match?): the leader flag, and search under the
+// call's style as normalizeVerbStyle leaves them - verb = kSearch or kMatch.  normalize = false: the
+// form at hand is no line verb (tally_text's and uniq_text's MATCHES), only the leader flag is wanted.
+struct LineVerb {
+  int lead, verb, style;
+};
+[[maybe_unused]] static LineVerb lineVerb(const DevDfa &d, const LaunchCfg &cfg, int doLeader,
+                                          int style, bool normalize = true) {
+  LineVerb v{doLeader && d.leaderLen > 0 ? 1 : 0, kSearch, style};
+  if (normalize) normalizeVerbStyle(d, cfg, v.lead != 0, v.verb, v.style);
+  return v;
+}
+
+// LAUNCH<K, kSearch>(args) or LAUNCH<K, kMatch>(args), by the LineVerb `v` in scope
+#define REDGPU_LINE_VERB(LAUNCH, K, ...) \
+  (v.verb == kSearch ? LAUNCH<K, kSearch>(__VA_ARGS__) : LAUNCH<K, kMatch>(__VA_ARGS__))
+
+// the DevDfa the LDS-room rules of tally_text, sum_text and uniq_text read
+[[maybe_unused]] static DevDfa ldsRoomDfa(uint32_t tableKind, uint32_t tableBytes,
+                                          uint32_t nStates) {
+  DevDfa d{};
+  d.tableKind = tableKind;
+  d.tableBytes = tableBytes;
+  d.nStates = nStates;
+  return d;
+}
+
 #if REDGPU_TU_GREP || REDGPU_TU_COLLECT_TEXT
 // the scratch of grep and of grep -o, for a text of nChunks split chunks: what launchTextIndex
 // fills, a count and a base per chunk for the records, four spare words, the two bitmaps
@@ -1031,19 +1026,15 @@ hipError_t launchGrepText(const DevDfa &d, int style, int doLeader, int invert, 
   const hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
                                        m.hitMasks, m.misc, cfg.numCUs, stream);
   if (e != hipSuccess) return e;
-  const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
-  int verb = kSearch;
-  normalizeVerbStyle(d, cfg, lead != 0, verb, style);
+  const LineVerb v = lineVerb(d, cfg, doLeader, style);
   const GpBufs b{m.masks, m.hitMasks, m.bases, m.open, m.recCounts, m.recBases, nChunks};
   const GpOut out{cap < maxCount ? cap : maxCount, line, begin, finish, result, start, end};
   const bool write = out.limit > 0 && (line || begin || finish || result || start || end);
-#define GP_ARGS d, data, b, style, lead, invert, out, write, total, maxCount, nSelected, m.recBases, \
-                dummy, cfg, stream
-#define GP_CALL(K) \
-  (verb == kSearch ? launchGrepK<K, kSearch>(GP_ARGS) : launchGrepK<K, kMatch>(GP_ARGS))
+#define GP_CALL(K)                                                                              \
+  REDGPU_LINE_VERB(launchGrepK, K, d, data, b, v.style, v.lead, invert, out, write, total,      \
+                   maxCount, nSelected, m.recBases, dummy, cfg, stream)
   REDGPU_KIND_SWITCH(GP_CALL)
 #undef GP_CALL
-#undef GP_ARGS
 }
 
 // grep's output over a raw text (k_filter_text.h): the line index (launchTextIndex), k_grep.h's
@@ -1094,38 +1085,28 @@ hipError_t launchFilterText(const DevDfa &d, int style, int doLeader, int invert
   const FilterScratch m(scratch, nChunks);
   uint64_t *dummy = m.misc + 1, *total = m.misc + 2;
   const GpBufs b{m.masks, m.selMasks, m.bases, m.open, m.selCounts, m.selBases, nChunks};
-  // the grid of the passes without a table: a wave per chunk, four to a workgroup
-  uint64_t small = (nChunks + 3) / 4;
-  if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
+  const uint32_t small = smallBlocks(nChunks, cfg.numCUs);
   if (phases & 1) {
     hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
                                    m.selMasks, m.misc, cfg.numCUs, stream);
     if (e != hipSuccess) return e;
-    const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
-    int verb = kSearch;
-    normalizeVerbStyle(d, cfg, lead != 0, verb, style);
+    const LineVerb v = lineVerb(d, cfg, doLeader, style);
     // k_gp_select, the scan of selCounts and k_gp_total; no records
     const GpOut none{};
-#define FT_ARGS d, data, b, style, lead, invert, none, false, total, maxCount,                     \
-                nSelected ? nSelected : m.misc + 3, m.selBases, dummy, cfg, stream
-#define FT_CALL(K) \
-  (verb == kSearch ? launchGrepK<K, kSearch>(FT_ARGS) : launchGrepK<K, kMatch>(FT_ARGS))
+#define FT_CALL(K)                                                                              \
+  REDGPU_LINE_VERB(launchGrepK, K, d, data, b, v.style, v.lead, invert, none, false, total,     \
+                   maxCount, nSelected ? nSelected : m.misc + 3, m.selBases, dummy, cfg, stream)
     e = [&]() -> hipError_t { REDGPU_KIND_SWITCH(FT_CALL) }();
 #undef FT_CALL
-#undef FT_ARGS
     if (e != hipSuccess) return e;
     if (nChunks) {
-      hipLaunchKernelGGL(k_ft_edges, dim3(uint32_t(small)), dim3(256), 0, stream, b, maxCount,
-                         m.prevSel, m.nextRev);
+      hipLaunchKernelGGL(k_ft_edges, dim3(small), dim3(256), 0, stream, b, maxCount, m.prevSel,
+                         m.nextRev);
       hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, m.prevSel, nChunks);
       hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, m.nextRev, nChunks);
-      hipLaunchKernelGGL(k_ft_mark, dim3(uint32_t(small)), dim3(256), 0, stream, b, maxCount, before,
-                         after, m.prevSel, m.nextRev, m.emitBytes, m.emitLines);
-      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream,
-                         m.emitBytes, nChunks, m.partials);
-      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
-      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.emitBytes,
-                         nChunks, m.partials, m.outBases);
+      hipLaunchKernelGGL(k_ft_mark, dim3(small), dim3(256), 0, stream, b, maxCount, before, after,
+                         m.prevSel, m.nextRev, m.emitBytes, m.emitLines);
+      launchScan64(m.emitBytes, nChunks, m.partials, m.outBases, stream);
     }
     hipLaunchKernelGGL(k_ft_totals, dim3(1), dim3(1024), 0, stream, m.emitLines, nChunks,
                        nChunks ? m.outBases + nChunks : nullptr, outLen,
@@ -1134,7 +1115,7 @@ hipError_t launchFilterText(const DevDfa &d, int style, int doLeader, int invert
     if (e != hipSuccess) return e;
   }
   if ((phases & 2) && out && outCap && nChunks) {
-    hipLaunchKernelGGL(k_ft_write, dim3(uint32_t(small)), dim3(256), 0, stream, data, b,
+    hipLaunchKernelGGL(k_ft_write, dim3(small), dim3(256), 0, stream, data, b,
                        m.emitBytes, m.outBases, out, outCap);
   }
   return hipGetLastError();
@@ -1200,10 +1181,7 @@ uint64_t tallyTextScratchBytes(uint64_t len) {
 }
 
 uint32_t tallyLdsBins(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates) {
-  DevDfa d{};
-  d.tableKind = tableKind;
-  d.tableBytes = tableBytes;
-  d.nStates = nStates;
+  const DevDfa d = ldsRoomDfa(tableKind, tableBytes, nStates);
 #define TL_BINS(K) tallyLdsBinsK<K>(d)
   REDGPU_KIND_SWITCH(TL_BINS)
 #undef TL_BINS
@@ -1221,27 +1199,23 @@ hipError_t launchTallyText(const DevDfa &d, int what, int style, int doLeader, c
                                  nullptr, m.misc, cfg.numCUs, stream);
   if (e != hipSuccess) return e;
   const uint64_t toZero = accumulate ? 0 : nBins + 1;
-  uint64_t zb = (toZero + 255) / 256;
-  if (zb > uint64_t(cfg.numCUs) * 8) zb = uint64_t(cfg.numCUs) * 8;
+  const uint32_t zb = wordBlocks(toZero, cfg.numCUs);
   TallyOut o{reinterpret_cast<unsigned long long *>(bins),
              reinterpret_cast<unsigned long long *>(nItems ? nItems : m.misc + 2), uint32_t(nBins),
              0};
-  hipLaunchKernelGGL(k_tl_zero, dim3(uint32_t(zb ? zb : 1)), dim3(256), 0, stream, o.bins, toZero,
-                     o.nItems);
+  hipLaunchKernelGGL(k_tl_zero, dim3(zb ? zb : 1), dim3(256), 0, stream, o.bins, toZero, o.nItems);
   e = hipGetLastError();
   if (e != hipSuccess || nChunks == 0) return e;
-  const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
-  int verb = kSearch;
-  if (what == REDGPU_TALLY_LINES) normalizeVerbStyle(d, cfg, lead != 0, verb, style);
+  const LineVerb v = lineVerb(d, cfg, doLeader, style, what == REDGPU_TALLY_LINES);
   // L: the leading bins kept in LDS.  32-bit counters hold a text below 4 GiB whatever it is
   // (k_tally_text.h: tallyAdd); a longer text counts in global memory alone
   const uint32_t room = len < (1ull << 32) ? tallyLdsBins(d.tableKind, d.tableBytes, d.nStates) : 0u;
   o.ldsBins = nBins + 1 < room ? uint32_t(nBins + 1) : room;
   const GpBufs b{m.masks, nullptr, m.bases, m.open, nullptr, nullptr, nChunks};
-#define TL_ARGS d, data, b, style, lead, plain, o, cfg, stream
+#define TL_ARGS d, data, b, v.style, v.lead, plain, o, cfg, stream
 #define TL_CALL(K)                                                                    \
   (what == REDGPU_TALLY_MATCHES ? launchTallyK<K, kTallyMatches>(TL_ARGS)             \
-   : verb == kSearch            ? launchTallyK<K, kTallyLines>(TL_ARGS)               \
+   : v.verb == kSearch          ? launchTallyK<K, kTallyLines>(TL_ARGS)               \
                                 : launchTallyK<K, kTallyLinesMatch>(TL_ARGS))
   REDGPU_KIND_SWITCH(TL_CALL)
 #undef TL_CALL
@@ -1258,10 +1232,7 @@ uint64_t sumTextScratchBytes(uint64_t len) {
 }
 
 uint32_t sumLdsBins(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates) {
-  DevDfa d{};
-  d.tableKind = tableKind;
-  d.tableBytes = tableBytes;
-  d.nStates = nStates;
+  const DevDfa d = ldsRoomDfa(tableKind, tableBytes, nStates);
 #define SM_BINS(K) sumLdsBinsK<K>(d)
   REDGPU_KIND_SWITCH(SM_BINS)
 #undef SM_BINS
@@ -1280,14 +1251,13 @@ hipError_t launchSumText(const DevDfa &d, int which, const uint8_t *data, uint64
                                  nullptr, m.misc, cfg.numCUs, stream);
   if (e != hipSuccess) return e;
   const uint64_t toZero = accumulate ? 0 : nBins + 1;
-  uint64_t zb = (toZero + 255) / 256;
-  if (zb > uint64_t(cfg.numCUs) * 8) zb = uint64_t(cfg.numCUs) * 8;
+  const uint32_t zb = wordBlocks(toZero, cfg.numCUs);
   SumOut o{reinterpret_cast<unsigned long long *>(stats),
            reinterpret_cast<unsigned long long *>(nItems ? nItems : m.misc + 2),
            reinterpret_cast<unsigned long long *>(nNumeric ? nNumeric : m.misc + 3),
            nBins + 1, uint32_t(nBins), 0};
-  hipLaunchKernelGGL(k_sm_zero, dim3(uint32_t(zb ? zb : 1)), dim3(256), 0, stream, o.stats, toZero,
-                     o.nItems, o.nNumeric);
+  hipLaunchKernelGGL(k_sm_zero, dim3(zb ? zb : 1), dim3(256), 0, stream, o.stats, toZero, o.nItems,
+                     o.nNumeric);
   e = hipGetLastError();
   if (e != hipSuccess || nChunks == 0 || maxPerLine == 0) return e;
   // L: the leading slots kept in LDS; 64-bit words, so a text of any length may use them
@@ -1362,11 +1332,7 @@ hipError_t launchReplaceText(const DevDfa &d, int style, int doLeader, int onlyC
     if (nChunks) {
       e = pass(true);
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream,
-                         m.outBytes, nChunks, m.partials);
-      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
-      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.outBytes,
-                         nChunks, m.partials, m.outBases);
+      launchScan64(m.outBytes, nChunks, m.partials, m.outBases, stream);
     }
     hipLaunchKernelGGL(k_rt_totals, dim3(1), dim3(1024), 0, stream, m.replCounts, nChunks,
                        nChunks ? m.outBases + nChunks : nullptr, m.masks, m.open, len, onlyChanged,
@@ -1416,11 +1382,7 @@ hipError_t launchExtractText(const DevDfa &d, const uint8_t *data, uint64_t len,
     if (nChunks) {
       e = pass(true);
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream,
-                         m.outBytes, nChunks, m.partials);
-      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
-      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.outBytes,
-                         nChunks, m.partials, m.outBases);
+      launchScan64(m.outBytes, nChunks, m.partials, m.outBases, stream);
     }
     hipLaunchKernelGGL(k_xt_totals, dim3(1), dim3(1024), 0, stream, m.replCounts, nChunks,
                        nChunks ? m.outBases + nChunks : nullptr, outLen,
@@ -1501,11 +1463,7 @@ hipError_t launchFieldsText(const DevDfa &d, const uint8_t *data, uint64_t len, 
     if (nChunks) {
       e = pass(true);
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream,
-                         m.outBytes, nChunks, m.partials);
-      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
-      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.outBytes,
-                         nChunks, m.partials, m.outBases);
+      launchScan64(m.outBytes, nChunks, m.partials, m.outBases, stream);
     }
     hipLaunchKernelGGL(k_fd_totals, dim3(1), dim3(1024), 0, stream, m.lineCounts, m.fieldCounts,
                        nChunks, nChunks ? m.outBases + nChunks : nullptr, outLen,
@@ -1576,9 +1534,7 @@ hipError_t launchRouteText(const DevDfa &d, int style, int doLeader, int dropUnm
   const GpBufs b{m.masks, m.masks, m.bases, m.open, nullptr, nullptr, nChunks};
   const RoBufs r{m.planes, nChunks * (kSplitChunk / 16), m.counts, m.sizes, m.lines, m.outBases,
                  uint32_t(nBins), m.nCodes, m.nPlanes, m.zeroCode, dropUnmatched ? 1 : 0};
-  // the grid of the passes without a table: a wave per chunk, four to a workgroup
-  uint64_t small = (nChunks + 3) / 4;
-  if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
+  const uint32_t small = smallBlocks(nChunks, cfg.numCUs);
   if (phases & 1) {
     // (no bitmap for k_gp_last to zero: the planes are zeroed here, all of them at once)
     hipError_t e = launchTextIndex(data, len, delim, m.misc, m.counts, m.bases, m.masks, m.open,
@@ -1589,22 +1545,14 @@ hipError_t launchRouteText(const DevDfa &d, int style, int doLeader, int dropUnm
         e = hipMemsetAsync(m.planes, 0, size_t(m.nPlanes) * nChunks * (kSplitChunk / 8), stream);
         if (e != hipSuccess) return e;
       }
-      const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
-      int verb = kSearch;
-      normalizeVerbStyle(d, cfg, lead != 0, verb, style);
-#define RO_ARGS d, data, b, style, lead, r, cfg, stream
+      const LineVerb v = lineVerb(d, cfg, doLeader, style);
 #define RO_CALL(K) \
-  (verb == kSearch ? launchRouteClassK<K, kSearch>(RO_ARGS) : launchRouteClassK<K, kMatch>(RO_ARGS))
+  REDGPU_LINE_VERB(launchRouteClassK, K, d, data, b, v.style, v.lead, r, cfg, stream)
       e = [&]() -> hipError_t { REDGPU_KIND_SWITCH(RO_CALL) }();
 #undef RO_CALL
-#undef RO_ARGS
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_ro_size, dim3(uint32_t(small)), dim3(256), 0, stream, b, r);
-      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.sizes,
-                         m.nCells, m.partials);
-      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
-      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.sizes,
-                         m.nCells, m.partials, m.outBases);
+      hipLaunchKernelGGL(k_ro_size, dim3(small), dim3(256), 0, stream, b, r);
+      launchScan64(m.sizes, m.nCells, m.partials, m.outBases, stream);
     }
     hipLaunchKernelGGL(k_ro_finish, dim3(m.nCodes), dim3(256), 0, stream, r, nChunks, m.misc, nLines,
                        nRouted, binLines, binOffsets, outLen);
@@ -1612,7 +1560,7 @@ hipError_t launchRouteText(const DevDfa &d, int style, int doLeader, int dropUnm
     if (e != hipSuccess) return e;
   }
   if ((phases & 2) && out && outCap && nChunks) {
-    hipLaunchKernelGGL(k_ro_write, dim3(uint32_t(small)), dim3(256), 0, stream, data, b, r, out,
+    hipLaunchKernelGGL(k_ro_write, dim3(small), dim3(256), 0, stream, data, b, r, out,
                        outCap);
   }
   return hipGetLastError();
@@ -1678,9 +1626,7 @@ hipError_t launchRangeText(const DevDfa &d, int style, int doLeader, int32_t ope
   const RgBufs r{m.openBits, m.closeBits, m.carry, m.events, m.starts, m.startBases, m.emitBytes,
                  m.emitLines, m.misc + 6, openResult, closeResult, toggle};
   const RgArgs a{emitOpen, emitClose, invert, maxRanges, recCap, firstLine, lastLine, begin, end};
-  // the grid of the passes without a table: a wave per chunk, four to a workgroup
-  uint64_t small = (nChunks + 3) / 4;
-  if (small > uint64_t(cfg.numCUs) * 8) small = uint64_t(cfg.numCUs) * 8;
+  const uint32_t small = smallBlocks(nChunks, cfg.numCUs);
   if (phases & 1) {
     // (no bitmap for k_gp_last to zero: the planes are zeroed here, both at once)
     hipError_t e = launchTextIndex(data, len, delim, m.misc, m.counts, m.bases, m.masks, m.open,
@@ -1689,32 +1635,24 @@ hipError_t launchRangeText(const DevDfa &d, int style, int doLeader, int32_t ope
     if (nChunks) {
       e = hipMemsetAsync(m.openBits, 0, size_t(toggle ? 1 : 2) * nChunks * (kSplitChunk / 8), stream);
       if (e != hipSuccess) return e;
-      const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
-      int verb = kSearch;
-      normalizeVerbStyle(d, cfg, lead != 0, verb, style);
-#define RG_ARGS d, data, b, style, lead, r, cfg, stream
+      const LineVerb v = lineVerb(d, cfg, doLeader, style);
 #define RG_CALL(K) \
-  (verb == kSearch ? launchRangeClassK<K, kSearch>(RG_ARGS) : launchRangeClassK<K, kMatch>(RG_ARGS))
+  REDGPU_LINE_VERB(launchRangeClassK, K, d, data, b, v.style, v.lead, r, cfg, stream)
       e = [&]() -> hipError_t { REDGPU_KIND_SWITCH(RG_CALL) }();
 #undef RG_CALL
-#undef RG_ARGS
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_rg_events, dim3(uint32_t(small)), dim3(256), 0, stream, r, nChunks);
+      hipLaunchKernelGGL(k_rg_events, dim3(small), dim3(256), 0, stream, r, nChunks);
       if (toggle) {
         hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, m.events, nChunks, m.carry,
                            m.misc + 5, m.misc + 4, uint64_t(0));
       } else {
         hipLaunchKernelGGL(k_gp_open, dim3(1), dim3(1024), 0, stream, m.carry, nChunks);
       }
-      hipLaunchKernelGGL(k_rg_starts, dim3(uint32_t(small)), dim3(256), 0, stream, r, nChunks);
+      hipLaunchKernelGGL(k_rg_starts, dim3(small), dim3(256), 0, stream, r, nChunks);
       hipLaunchKernelGGL(k_split_scan, dim3(1), dim3(1024), 0, stream, m.starts, nChunks,
                          m.startBases, m.misc + 3, m.misc + 4, uint64_t(0));
-      hipLaunchKernelGGL(k_rg_mark, dim3(uint32_t(small)), dim3(256), 0, stream, b, r, a);
-      hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream,
-                         m.emitBytes, nChunks, m.partials);
-      hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
-      hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.emitBytes,
-                         nChunks, m.partials, m.outBases);
+      hipLaunchKernelGGL(k_rg_mark, dim3(small), dim3(256), 0, stream, b, r, a);
+      launchScan64(m.emitBytes, nChunks, m.partials, m.outBases, stream);
     }
     hipLaunchKernelGGL(k_rg_totals, dim3(1), dim3(1024), 0, stream, r, a, nChunks,
                        nChunks ? m.outBases + nChunks : nullptr, m.misc + 3, m.misc, nLines, nRanges,
@@ -1723,7 +1661,7 @@ hipError_t launchRangeText(const DevDfa &d, int style, int doLeader, int32_t ope
     if (e != hipSuccess) return e;
   }
   if ((phases & 2) && out && outCap && nChunks) {
-    hipLaunchKernelGGL(k_ft_write, dim3(uint32_t(small)), dim3(256), 0, stream, data, b,
+    hipLaunchKernelGGL(k_ft_write, dim3(small), dim3(256), 0, stream, data, b,
                        m.emitBytes, m.outBases, out, outCap);
   }
   return hipGetLastError();
@@ -1770,10 +1708,7 @@ uint64_t uniqTextScratchBytes(uint64_t len, uint64_t tableSlots) {
 }
 
 uint32_t uniqLdsSlots(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates) {
-  DevDfa d{};
-  d.tableKind = tableKind;
-  d.tableBytes = tableBytes;
-  d.nStates = nStates;
+  const DevDfa d = ldsRoomDfa(tableKind, tableBytes, nStates);
 #define UQ_SLOTS(K) uniqLdsSlotsK<K>(d)
   REDGPU_KIND_SWITCH(UQ_SLOTS)
 #undef UQ_SLOTS
@@ -1795,46 +1730,35 @@ hipError_t launchUniqText(const DevDfa &d, int what, int style, int doLeader, co
   UqOut o{reinterpret_cast<unsigned long long *>(m.table), tableSlots,
           reinterpret_cast<unsigned long long *>(nItems ? nItems : m.misc + 3),
           reinterpret_cast<unsigned long long *>(nDropped ? nDropped : m.misc + 4), 0};
-  // the grid of the passes over the table
-  const uint64_t most = uint64_t(cfg.numCUs) * 8;
   // (an empty text needs no table: the counters alone are zeroed)
   const uint64_t words = nChunks ? 2 * tableSlots : 0;
-  uint64_t zb = (words + 255) / 256;
-  if (zb > most) zb = most;
-  hipLaunchKernelGGL(k_uq_zero, dim3(uint32_t(zb ? zb : 1)), dim3(256), 0, stream, o.table, words,
-                     o.nItems, o.nDropped, nDistinct);
+  const uint32_t zb = wordBlocks(words, cfg.numCUs);
+  hipLaunchKernelGGL(k_uq_zero, dim3(zb ? zb : 1), dim3(256), 0, stream, o.table, words, o.nItems,
+                     o.nDropped, nDistinct);
   e = hipGetLastError();
   if (e != hipSuccess || nChunks == 0) return e;
-  const int lead = doLeader && d.leaderLen > 0 ? 1 : 0;
-  int verb = kSearch;
-  if (what == REDGPU_UNIQ_LINES) normalizeVerbStyle(d, cfg, lead != 0, verb, style);
+  const LineVerb v = lineVerb(d, cfg, doLeader, style, what == REDGPU_UNIQ_LINES);
   // L: the front's slots.  32-bit counts hold a text below 4 GiB whatever it is (k_tally_text.h:
   // tallyAdd); a longer text, and the plain form, go to the global table alone
   if (!plain && len < (1ull << 32)) o.ldsSlots = uniqLdsSlots(d.tableKind, d.tableBytes, d.nStates);
   const GpBufs b{m.masks, nullptr, m.bases, m.open, nullptr, nullptr, nChunks};
-#define UQ_ARGS d, data, len, b, style, lead, maxPerLine, o, cfg, stream
+#define UQ_ARGS d, data, len, b, v.style, v.lead, maxPerLine, o, cfg, stream
 #define UQ_CALL(K)                                                              \
   (what == REDGPU_UNIQ_MATCHES ? launchUniqK<K, kUqMatches>(UQ_ARGS)            \
-   : verb == kSearch           ? launchUniqK<K, kUqLines>(UQ_ARGS)              \
+   : v.verb == kSearch         ? launchUniqK<K, kUqLines>(UQ_ARGS)              \
                                : launchUniqK<K, kUqLinesMatch>(UQ_ARGS))
   e = [&]() -> hipError_t { REDGPU_KIND_SWITCH(UQ_CALL) }();
 #undef UQ_CALL
 #undef UQ_ARGS
   if (e != hipSuccess) return e;
-  uint64_t tb = (tableSlots + 255) / 256;
-  if (tb > most) tb = most;
-  uint64_t small = (nChunks + 3) / 4;
-  if (small > most) small = most;
-  hipLaunchKernelGGL(k_uq_mark, dim3(uint32_t(tb)), dim3(256), 0, stream, o.table, tableSlots,
+  // the grid of the passes over the table
+  const uint32_t tb = wordBlocks(tableSlots, cfg.numCUs);
+  hipLaunchKernelGGL(k_uq_mark, dim3(tb), dim3(256), 0, stream, o.table, tableSlots,
                      reinterpret_cast<uint32_t *>(m.firsts));
-  hipLaunchKernelGGL(k_uq_pop, dim3(uint32_t(small)), dim3(256), 0, stream, m.firsts, nChunks,
-                     m.pops, m.lanePre);
-  hipLaunchKernelGGL(k_scan_partials, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.pops,
-                     nChunks, m.partials);
-  hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(1024), 0, stream, m.partials, m.nPart);
-  hipLaunchKernelGGL(k_scan_fill, dim3(uint32_t(m.nPart)), dim3(256), 0, stream, m.pops, nChunks,
-                     m.partials, m.popBases);
-  hipLaunchKernelGGL(k_uq_emit, dim3(uint32_t(tb)), dim3(256), 0, stream, o.table, tableSlots,
+  hipLaunchKernelGGL(k_uq_pop, dim3(smallBlocks(nChunks, cfg.numCUs)), dim3(256), 0, stream,
+                     m.firsts, nChunks, m.pops, m.lanePre);
+  launchScan64(m.pops, nChunks, m.partials, m.popBases, stream);
+  hipLaunchKernelGGL(k_uq_emit, dim3(tb), dim3(256), 0, stream, o.table, tableSlots,
                      reinterpret_cast<const uint32_t *>(m.firsts), m.popBases, m.lanePre, nChunks,
                      cap, first, length, count, nDistinct);
   return hipGetLastError();

@@ -262,6 +262,13 @@ hipError_t launchAdvanceK(const DevDfa &d, const Batch &b, uint32_t *state, cons
   return hipGetLastError();
 }
 
+// match<..., true> behind a whole-line walk: the lines that fail the leader report {0, 0, 0}
+inline hipError_t launchLeaderFilter(const DevDfa &d, const Batch &b, const LaunchCfg &cfg,
+                                     hipStream_t stream) {
+  hipLaunchKernelGGL(k_leader_filter, dim3(uint32_t(cfg.numCUs) * 8), dim3(256), 0, stream, d, b);
+  return hipGetLastError();
+}
+
 template <int STYLE, bool POS, bool WANT_START, int CHAINS>
 hipError_t launchFixedT(const DevDfa &d, const Batch &b, uint32_t startByte,
                         uint32_t startState, const LaunchCfg &cfg, hipStream_t stream) {
