@@ -1029,6 +1029,96 @@ int redgpu_uniq_text_dev(const redgpu_dfa *dfa, int what, int style, int do_lead
                          uint64_t *length, uint64_t *count, void *stream);
 uint32_t redgpu_uniq_lds_slots(const redgpu_dfa *dfa);
 
+/* awk '!seen[$k]++': raw text in, the lines CHOSEN BY CONTENT out as a text - the first line per
+ * session id, every line whose request id occurs once, a message without its repeats: sort -u -k in
+ * text order, uniq -u, uniq -d, and under invert awk 'seen[$k]++'.  redgpu_uniq_text returns the
+ * distinct strings as records; this verb returns the lines they stand in.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter (the tail) are not a line: never emitted, and they
+ *    contribute no key.
+ *  - Every line has at most ONE KEY, a byte range inside [line begin, delimiter]; a line without
+ *    one is UNKEYED.
+ *      what == REDGPU_DEDUP_WHOLE: the key is the line without its delimiter (an empty line has
+ *        the empty key).  The DFA is not walked; style, do_leader and key_index are not looked at.
+ *      what == REDGPU_DEDUP_LINES: the key is the line, if redgpu_grep_text selects it with
+ *        search<style,do_leader> and no invert - redgpu_uniq_text's REDGPU_UNIQ_LINES item, with its
+ *        verb and style normalisation; every other line is unkeyed.  key_index is not looked at.
+ *      what == REDGPU_DEDUP_MATCH: the key is the key_index-th (1-based) piece
+ *        redgpu_extract_text would emit for the line; a line with fewer pieces is unkeyed.  style
+ *        and do_leader are not looked at.
+ *      what == REDGPU_DEDUP_FIELD: the DFA is the SEPARATOR and the key is field key_index
+ *        (1-based) under redgpu_fields_text's field rule with every separator counted
+ *        (max_fields == 0).  A key may be EMPTY - the empty field at the very end of a line
+ *        included; a line with fewer than key_index fields is unkeyed.  The line is not walked
+ *        behind its key_index-th separator.  style and do_leader are not looked at.
+ *  - Two keys are equal iff their bytes are.  Among all keyed lines a line is MARKED iff it holds
+ *    the earliest occurrence of its key's string and min_count <= count <= max_count, count being
+ *    the string's exact number of occurrences.  min_count = 1, max_count = 2^64 - 1 is
+ *    awk '!seen[k]++'; 1, 1 is uniq -u in text order; 2, 2^64 - 1 is uniq -d in text order;
+ *    min_count > max_count marks nothing and is legal.
+ *  - Line i is EMITTED iff it is keyed and marked != (invert != 0), or it is unkeyed and
+ *    keep_unkeyed != 0.  With the default window, invert is awk 'seen[k]++': every later duplicate.
+ *  - The output is the emitted lines in text order, each once, each with its delimiter: a raw text
+ *    every text verb accepts (fields_text | dedup_text, dedup_text | tally_text).
+ *  - *n_lines = delimiters found, *n_keyed = keyed lines (dropped ones included), *n_distinct =
+ *    the strings that hold a table record, whatever their counts, *n_dropped = keyed lines whose
+ *    key got no record, *n_emitted = lines emitted, *out_len = the length of the whole output,
+ *    whatever out_cap is.  out_len is required; the other five may be NULL, each on its own.
+ *    While *n_dropped == 0: with the default window *n_emitted == *n_distinct, with invert beside
+ *    it *n_emitted == *n_keyed - *n_distinct, and *n_distinct is redgpu_uniq_text's on the same
+ *    items.
+ *  - out == NULL or out_cap == 0 gives the sizes only.  Otherwise exactly the first
+ *    min(*out_len, out_cap) bytes of the output are written - the cut may fall inside a line - and
+ *    bytes of out from there on are NOT written (redgpu_filter_text's rule).  out must not overlap
+ *    data.
+ *  - table_slots is the size of the hash table the strings are kept in, as redgpu_uniq_text's: a
+ *    power of two, 64 <= table_slots <= 2^32, 16 bytes each from the thread's scratch pool.
+ *  - A key is dropped in redgpu_uniq_text's two cases.  It is 2^24 bytes or longer: decided before
+ *    it is hashed, deterministic.  Or the table is full and does not hold its string.  A dropped
+ *    line is keyed and NOT marked.
+ *  - *n_dropped == 0: every output is bit-identical from run to run.  When the table overflows,
+ *    every marked line is still a correct mark (its record's count and first offset are exact), and
+ *    *n_distinct == table_slots; without invert the output is the exact output minus the lines
+ *    whose string got no record, and WHICH lines those are depends on scheduling.  The remedy is
+ *    the caller's: call again with a larger table.
+ *  - REDGPU_EAPI for a NULL handle, a NULL out_len, a NULL data with len > 0, a `what` other than
+ *    the four below, key_index == 0 under MATCH or FIELD, a table_slots that is no power of two in
+ *    [64, 2^32] - the message names the argument - (the argument checks run before the handle's
+ *    device is looked at) and for a REDGPU_DEVICE_NONE handle; REDGPU_EEXEC for a style that does
+ *    not exist (LINES only); REDGPU_ELIMIT for a text redgpu_split_lines refuses or one of 2^40 - 1
+ *    bytes or more.  In every error case nothing of the caller's is written.
+ *  - An empty text, or one without a delimiter: all six counts are 0 and nothing is written to out
+ *    (the _dev form writes the counts on the stream).
+ *  - A single line of megabytes is walked by one lane, the mark of a string whose first line is
+ *    that long scans the line's bits word by word, and a table near full is probed slot by slot:
+ *    correct, and slow.
+ * redgpu_last_kernel() says "k_dedup_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - nothing is read
+ * back, and no per-line array is needed from the caller or in scratch ("is keyed" and "is marked"
+ * live in two bitmaps of the delimiter bitmap's layout; scratch is 16 bytes per slot + 3 * len / 8
+ * for the bitmaps + 40 bytes per 16 KiB chunk + 8 bytes per 1,024 chunks + 72, rounded up to 16,
+ * from the thread's pool).  A text of 4 GiB or more runs without the on-chip front of the table,
+ * as redgpu_uniq_text's: the same output.
+ * redgpu_dedup_text: host buffers, as redgpu_filter_text - one upload of the text, a sizes pass
+ * that leaves the table and the bitmaps on the device, a device output sized from *out_len, and
+ * min(*out_len, out_cap) bytes downloaded. */
+#define REDGPU_DEDUP_WHOLE 0  /* every line is keyed by its own bytes; the DFA is not walked */
+#define REDGPU_DEDUP_LINES 1  /* the lines grep_text selects (search<style,do_leader>), keyed by their bytes */
+#define REDGPU_DEDUP_MATCH 2  /* key = piece number key_index of the line (extract_text's pieces) */
+#define REDGPU_DEDUP_FIELD 3  /* the DFA is the SEPARATOR; key = field number key_index (fields_text's fields, max_fields = 0) */
+int redgpu_dedup_text(const redgpu_dfa *dfa, int what, int style, int do_leader, uint64_t key_index,
+                      uint64_t min_count, uint64_t max_count, int invert, int keep_unkeyed,
+                      const uint8_t *data, uint64_t len, uint8_t delim, uint64_t table_slots,
+                      uint64_t *n_lines, uint64_t *n_keyed, uint64_t *n_distinct,
+                      uint64_t *n_dropped, uint64_t *n_emitted, uint64_t *out_len, uint8_t *out,
+                      uint64_t out_cap);
+int redgpu_dedup_text_dev(const redgpu_dfa *dfa, int what, int style, int do_leader,
+                          uint64_t key_index, uint64_t min_count, uint64_t max_count, int invert,
+                          int keep_unkeyed, const uint8_t *data, uint64_t len, uint8_t delim,
+                          uint64_t table_slots, uint64_t *n_lines, uint64_t *n_keyed,
+                          uint64_t *n_distinct, uint64_t *n_dropped, uint64_t *n_emitted,
+                          uint64_t *out_len, uint8_t *out, uint64_t out_cap, void *stream);
+
 /* awk '{ n[c]++; s[c] += $x; if ($x > m[c]) m[c] = $x }': raw text in, per result the count, sum,
  * minimum and maximum of the decimal numbers found in the matches out - Red::collect
  * (lib/Red.cpp:103-116) inside the line loop of tools/skim_red.cpp:36-46, over the lines

@@ -473,6 +473,45 @@ inline size_t rangeText(const Executable &exec, Style style, bool doLeader, std:
   return size_t(found);
 }
 
+// what dedupText says beside the text: redgpu_dedup_text's six counters and the emitted lines
+struct DedupResult {
+  uint64_t lines = 0, keyed = 0, distinct = 0, dropped = 0, emitted = 0, outLen = 0;
+  std::string text;
+};
+
+// which bytes of a line are its key (REDGPU_DEDUP_*)
+enum DedupWhat { dedupWhole = 0, dedupLines = 1, dedupMatch = 2, dedupField = 3 };
+
+// awk '!seen[$k]++' (redgpu_dedup_text): the lines of a text blob chosen by the content of their
+// keys - a line's key is the line (dedupWhole; the DFA is not walked), the line if
+// search<style,doLeader> selects it (dedupLines), piece keyIndex extractText emits for it
+// (dedupMatch) or its field keyIndex with the DFA as the separator (dedupField); a line without
+// one is unkeyed.  A keyed line is marked iff it holds the earliest occurrence of its key's string
+// and minCount <= count <= maxCount; the text gets the keyed lines with marked != invert and,
+// under keepUnkeyed, the unkeyed ones, in text order with their delimiters; the tail behind the
+// last delimiter is never emitted.  The hash table holds the power of two at or above
+// 2 * maxDistinct (at least 64) strings; dropped = the keyed lines whose key got no record (2^24
+// bytes or longer, or the table was full: call again with a larger maxDistinct).  The text is
+// sized from a first call that only sizes.
+inline DedupResult dedupText(const Executable &exec, std::string_view text,
+                             DedupWhat what = dedupWhole, size_t keyIndex = 1,
+                             uint64_t minCount = 1, uint64_t maxCount = UINT64_MAX,
+                             bool invert = false, bool keepUnkeyed = false,
+                             size_t maxDistinct = size_t(1) << 20, Style style = styInstant,
+                             bool doLeader = true, char delim = '\n') {
+  const Byte *p = reinterpret_cast<const Byte *>(text.data());
+  uint64_t slots = 64;
+  while (slots < 2 * uint64_t(maxDistinct) && slots < (1ull << 32)) slots *= 2;
+  DedupResult r;
+  detail::sizedText(r.text, r.outLen, [&](Byte *o, uint64_t cap) {
+    throwOnError(redgpu_dedup_text(exec.handle(), what, style, doLeader, keyIndex, minCount,
+                                   maxCount, invert, keepUnkeyed, p, text.size(), Byte(delim),
+                                   slots, &r.lines, &r.keyed, &r.distinct, &r.dropped, &r.emitted,
+                                   &r.outLen, o, cap));
+  });
+  return r;
+}
+
 // grep -o as a text (redgpu_extract_text): every match of every line of a text blob put in `out`,
 // one per line - the bytes replace<styLast,false> would substitute, each followed by the delimiter,
 // in text order; at most maxPerLine of a line (1 = its first match).  Output line j is the bytes of

@@ -107,6 +107,22 @@ __device__ __forceinline__ void ftStoreBits(uint16_t *bitmap, uint64_t chunk, ui
                     uint32_t(m.w[3] >> 32));
 }
 
+// a mark pass's tail (k_ft_mark, k_dedup_text.h: k_dd_emit): the lane's 256 EMIT bits stored, and
+// the wave's sums of the lanes' emitted bytes and lines left as emitBytes[chunk], emitLines[chunk]
+__device__ __forceinline__ void ftStoreEmit(uint16_t *bitmap, uint64_t chunk, uint32_t lane,
+                                            const GpBits &e, uint64_t bytes, uint32_t lines,
+                                            uint64_t *emitBytes, uint32_t *emitLines) {
+  ftStoreBits(bitmap, chunk, lane, e);
+  for (int o = 32; o; o >>= 1) {
+    bytes += __shfl_xor(bytes, o);
+    lines += __shfl_xor(lines, o);
+  }
+  if (lane == 0) {
+    emitBytes[chunk] = bytes;
+    emitLines[chunk] = lines;
+  }
+}
+
 // f(k, bit) over the set bits of m, from the lowest / from the highest: k = the word, as a
 // std::integral_constant (no register is indexed by a variable), bit = the bit's mask in it
 template <int K, class F>
@@ -231,15 +247,7 @@ k_ft_mark(GpBufs b, uint64_t maxCount, uint64_t before, uint64_t after, const ui
       }
       begin = behind;
     });
-    ftStoreBits(b.selMasks, ch, lane, e);
-    for (int o = 32; o; o >>= 1) {
-      bytes += __shfl_xor(bytes, o);
-      lines += __shfl_xor(lines, o);
-    }
-    if (lane == 0) {
-      emitBytes[ch] = bytes;
-      emitLines[ch] = lines;
-    }
+    ftStoreEmit(b.selMasks, ch, lane, e, bytes, lines, emitBytes, emitLines);
   }
 }
 

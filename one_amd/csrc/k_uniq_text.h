@@ -180,6 +180,25 @@ __device__ __forceinline__ bool uqFront(unsigned long long *keys, uint32_t *coun
   return false;
 }
 
+// the workgroup's front flushed through the global insert, weighted by its counts (every thread
+// calls, at workgroup end): the occurrences of this thread's slots that found no place
+template <int kThreads>
+__device__ __forceinline__ uint64_t uqFlush(const UqOut &o, const uint8_t *data, uint64_t len,
+                                            const unsigned long long *keys, const uint32_t *counts,
+                                            uint32_t L) {
+  uint64_t dropped = 0;
+  if (L) {  // (uniform)
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < L; i += kThreads) {
+      const unsigned long long k = keys[i];
+      if (!k) continue;
+      const uint64_t a = (k >> 24) - 1, n = k & (kUqMaxItem - 1);
+      if (!uqInsert(o, data, len, a, n, counts[L + i], counts[i])) dropped += counts[i];
+    }
+  }
+  return dropped;
+}
+
 // zeroes the table (two words per slot) and the four counters
 __global__ void __launch_bounds__(256)
 k_uq_zero(unsigned long long *table, uint64_t words, unsigned long long *nItems,
@@ -246,15 +265,7 @@ k_uniq_text(DevDfa d, const uint8_t *data, uint64_t len, GpBufs b, int style, in
   }
   for (int sh = 32; sh; sh >>= 1) items += __shfl_xor(items, sh);
   if (lane == 0 && items) atomicAdd(o.nItems, static_cast<unsigned long long>(items));
-  if (L) {  // (uniform)
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < L; i += kThreads) {
-      const unsigned long long k = keys[i];
-      if (!k) continue;
-      const uint64_t a = (k >> 24) - 1, n = k & (kUqMaxItem - 1);
-      if (!uqInsert(o, data, len, a, n, counts[L + i], counts[i])) dropped += counts[i];
-    }
-  }
+  dropped += uqFlush<kThreads>(o, data, len, keys, counts, L);
   for (int sh = 32; sh; sh >>= 1) dropped += __shfl_xor(dropped, sh);
   if (lane == 0 && dropped) atomicAdd(o.nDropped, static_cast<unsigned long long>(dropped));
 }

@@ -385,6 +385,29 @@ hipError_t launchUniqText(const DevDfa &dfa, int what, int style, int doLeader, 
                           uint64_t *length, uint64_t *count, void *scratch, const LaunchCfg &cfg,
                           hipStream_t stream, const char **kernelName);
 
+// a raw text's lines chosen by their keys' strings (k_dedup_text.h): a line's key is the line
+// (what = REDGPU_DEDUP_WHOLE), the line when launchGrepText selects it (LINES, its normalisation),
+// piece keyIndex launchExtractText would emit for it (MATCH) or field keyIndex launchFieldsText
+// cuts it into (FIELD); a line without one is unkeyed.  A keyed line is marked iff it holds the
+// earliest occurrence of its key's string and the string's count lies in [minCount, maxCount];
+// emitted are the keyed lines with marked != invert, and the unkeyed ones under keepUnkeyed, in
+// text order with their delimiters.  *nKeyed = keyed lines, *nDistinct = strings with a record,
+// *nDropped = keyed lines whose key got none (2^24 bytes or longer, or the table full),
+// *nEmitted = lines emitted, *outLen = the whole output's length, the first min(*outLen, outCap)
+// bytes in out and nothing behind them (out and every counter but outLen may be null).  tableSlots
+// a power of two; keyIndex >= 1.  plain = 1: no LDS front.  phases: 1 = index, walk, mark, emit and
+// scan, 2 = write out from what phase 1 left in scratch, 3 = both.  scratch:
+// dedupTextScratchBytes(len, tableSlots) bytes of device memory, 16-byte aligned.
+// *kernelName = "k_dedup_text".
+uint64_t dedupTextScratchBytes(uint64_t len, uint64_t tableSlots);
+hipError_t launchDedupText(const DevDfa &dfa, int what, int style, int doLeader, uint64_t keyIndex,
+                           uint64_t minCount, uint64_t maxCount, int invert, int keepUnkeyed,
+                           const uint8_t *data, uint64_t len, uint8_t delim, uint64_t tableSlots,
+                           int plain, uint64_t *nLines, uint64_t *nKeyed, uint64_t *nDistinct,
+                           uint64_t *nDropped, uint64_t *nEmitted, uint64_t *outLen, uint8_t *out,
+                           uint64_t outCap, int phases, void *scratch, const LaunchCfg &cfg,
+                           hipStream_t stream, const char **kernelName);
+
 // bench.py's read-bandwidth calibration: one streaming pass over `bytes` (16-byte aligned).
 hipError_t launchDiagRead(const void *data, uint64_t bytes, uint32_t *sink, int numCUs,
                           hipStream_t stream);

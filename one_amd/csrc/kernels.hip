@@ -72,6 +72,9 @@
 //   k_sum_text.h      k_sum_text: per result the count, sum, min and max of the numbers in a raw text's
 //                     matches - k_tally_text.h's walk, the digits read once a piece's span is known,
 //                     four 64-bit words per slot behind an LDS front
+//   k_dedup_text.h    k_dd_*: awk '!seen[$k]++' over a raw text - k_uniq_text.h's walk and table with one key
+//                     per line, a pass that turns table slots into line bits, the EMIT bitmap from
+//                     three bitmaps, and k_filter_text.h's run copy
 //   k_diag.h         bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
@@ -84,12 +87,12 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled thirteen times in parallel (Makefile: -DREDGPU_TU=1/2/.../13): the templates are
+// This file is compiled fourteen times in parallel (Makefile: -DREDGPU_TU=1/2/.../14): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
 // 3 = everything else and the dispatch, 4 = k_grep and k_filter_text (which runs k_grep's select), 5 = k_collect_text, 6 = k_replace_text,
 // 7 = k_tally_text, 8 = k_extract_text, 9 = k_route_text, 10 = k_uniq_text,
-// 11 = k_fields_text, 12 = k_sum_text, 13 = k_range_text.
+// 11 = k_fields_text, 12 = k_sum_text, 13 = k_range_text, 14 = k_dedup_text.
 // REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
@@ -107,6 +110,7 @@
 #define REDGPU_TU_FIELDS_TEXT (REDGPU_TU == 0 || REDGPU_TU == 11)
 #define REDGPU_TU_SUM_TEXT (REDGPU_TU == 0 || REDGPU_TU == 12)
 #define REDGPU_TU_RANGE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 13)
+#define REDGPU_TU_DEDUP_TEXT (REDGPU_TU == 0 || REDGPU_TU == 14)
 
 // return CALL(KIND) for the table kind of the DevDfa `d` in scope: a launcher's instantiation per kind
 #define REDGPU_KIND_SWITCH(CALL)                                                          \
@@ -157,6 +161,7 @@ namespace {
 #include "k_fields_text.h"
 #include "k_sum_text.h"
 #include "k_range_text.h"
+#include "k_dedup_text.h"
 
 } // namespace
 
@@ -1667,6 +1672,119 @@ hipError_t launchRangeText(const DevDfa &d, int style, int doLeader, int32_t ope
   return hipGetLastError();
 }
 #endif  // REDGPU_TU_RANGE_TEXT
+
+#if REDGPU_TU_DEDUP_TEXT
+// a raw text's lines chosen by their keys' strings (k_dedup_text.h): the line index (launchTextIndex),
+// k_uq_zero, the one pass of k_dedup_text, k_dd_mark over the table, k_dd_emit, k_misc.h's scan,
+// k_ft_totals and k_filter_text.h's write pass.  scratch: dedupTextScratchBytes(len, tableSlots)
+// bytes, 16-byte aligned: 16 bytes per slot, three bitmaps (len / 8 each), 40 bytes per chunk, 8 per
+// 1,024 chunks and 72, rounded up to 16.
+struct DedupScratch {
+  uint64_t *table;                    // [2 * slots]
+  uint64_t *bases, *open, *emitBytes; // [nChunks] each
+  uint64_t *outBases;                 // [nChunks + 1]
+  uint64_t *partials;                 // [nPart]
+  // [8]: lines, the index scan's two spare words, keyed, dropped, distinct, emitted, 1 spare
+  uint64_t *misc;
+  uint32_t *counts, *emitLines;       // [nChunks] each
+  uint16_t *masks, *keyedBits, *markBits;  // the delimiter bitmap, KEYED, MARK (then EMIT)
+  uint64_t nPart, bytes;
+  DedupScratch(void *scratch, uint64_t nChunks, uint64_t slots) : nPart((nChunks + 1023) / 1024) {
+    Carve c{static_cast<uint8_t *>(scratch)};
+    table = c.take<uint64_t>(2 * slots);
+    bases = c.take<uint64_t>(nChunks);
+    open = c.take<uint64_t>(nChunks);
+    emitBytes = c.take<uint64_t>(nChunks);
+    outBases = c.take<uint64_t>(nChunks + 1);
+    partials = c.take<uint64_t>(nPart);
+    misc = c.take<uint64_t>(8);
+    counts = c.take<uint32_t>(nChunks);
+    emitLines = c.take<uint32_t>(nChunks);
+    c.align(16);
+    masks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    keyedBits = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    markBits = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    bytes = c.at;
+  }
+};
+
+uint64_t dedupTextScratchBytes(uint64_t len, uint64_t tableSlots) {
+  return DedupScratch(nullptr, splitChunks(len), tableSlots).bytes;
+}
+
+hipError_t launchDedupText(const DevDfa &d, int what, int style, int doLeader, uint64_t keyIndex,
+                           uint64_t minCount, uint64_t maxCount, int invert, int keepUnkeyed,
+                           const uint8_t *data, uint64_t len, uint8_t delim, uint64_t tableSlots,
+                           int plain, uint64_t *nLines, uint64_t *nKeyed, uint64_t *nDistinct,
+                           uint64_t *nDropped, uint64_t *nEmitted, uint64_t *outLen, uint8_t *out,
+                           uint64_t outCap, int phases, void *scratch, const LaunchCfg &cfg,
+                           hipStream_t stream, const char **kernelName) {
+  *kernelName = "k_dedup_text";
+  const uint64_t nChunks = splitChunks(len);
+  const DedupScratch m(scratch, nChunks, tableSlots);
+  // (TextHits' verb bitmap is MARK, which k_dd_emit turns into the EMIT bitmap)
+  const GpBufs b{m.masks, m.markBits, m.bases, m.open, nullptr, nullptr, nChunks};
+  const uint32_t small = smallBlocks(nChunks, cfg.numCUs);
+  if (phases & 1) {
+    // (no bitmap for k_gp_last to zero: KEYED and MARK are zeroed here, both at once)
+    hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                   nullptr, m.misc, cfg.numCUs, stream);
+    if (e != hipSuccess) return e;
+    if (!nDistinct) nDistinct = m.misc + 5;
+    UqOut o{reinterpret_cast<unsigned long long *>(m.table), tableSlots,
+            reinterpret_cast<unsigned long long *>(nKeyed ? nKeyed : m.misc + 3),
+            reinterpret_cast<unsigned long long *>(nDropped ? nDropped : m.misc + 4), 0};
+    // (an empty text needs no table: the counters alone are zeroed)
+    const uint64_t words = nChunks ? 2 * tableSlots : 0;
+    const uint32_t zb = wordBlocks(words, cfg.numCUs);
+    hipLaunchKernelGGL(k_uq_zero, dim3(zb ? zb : 1), dim3(256), 0, stream, o.table, words, o.nItems,
+                       o.nDropped, nDistinct);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (nChunks) {
+      e = hipMemsetAsync(m.keyedBits, 0, size_t(2) * nChunks * (kSplitChunk / 8), stream);
+      if (e != hipSuccess) return e;
+      const LineVerb v = lineVerb(d, cfg, doLeader, style, what == REDGPU_DEDUP_LINES);
+      // L: the front's slots, by k_uniq_text.h's rule: none for a text of 4 GiB and more (32-bit
+      // counts) and under plain; WHOLE has the whole front, there is no table in front of it
+      if (!plain && len < (1ull << 32))
+        o.ldsSlots = what == REDGPU_DEDUP_WHOLE
+                         ? kUqLdsSlots
+                         : uniqLdsSlots(d.tableKind, d.tableBytes, d.nStates);
+      uint32_t *keyed = reinterpret_cast<uint32_t *>(m.keyedBits);
+#define DD_ARGS d, data, len, b, v.style, v.lead, keyIndex, o, keyed, cfg, stream
+#define DD_CALL(K)                                                           \
+  (what == REDGPU_DEDUP_MATCH   ? launchDedupK<K, kDdMatch>(DD_ARGS)         \
+   : what == REDGPU_DEDUP_FIELD ? launchDedupK<K, kDdField>(DD_ARGS)         \
+   : v.verb == kSearch          ? launchDedupK<K, kDdLines>(DD_ARGS)         \
+                                : launchDedupK<K, kDdLinesMatch>(DD_ARGS))
+      if (what == REDGPU_DEDUP_WHOLE) e = launchDedupK<REDGPU_TAB_GLOBAL_U32, kDdWhole>(DD_ARGS);
+      else e = [&]() -> hipError_t { REDGPU_KIND_SWITCH(DD_CALL) }();
+#undef DD_CALL
+#undef DD_ARGS
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_dd_mark, dim3(wordBlocks(tableSlots, cfg.numCUs)), dim3(256), 0, stream,
+                         o.table, tableSlots, minCount, maxCount,
+                         reinterpret_cast<const uint32_t *>(m.masks), nChunks * (kSplitChunk / 32),
+                         reinterpret_cast<uint32_t *>(m.markBits),
+                         reinterpret_cast<unsigned long long *>(nDistinct));
+      hipLaunchKernelGGL(k_dd_emit, dim3(small), dim3(256), 0, stream, b, m.keyedBits, invert,
+                         keepUnkeyed, m.emitBytes, m.emitLines);
+      launchScan64(m.emitBytes, nChunks, m.partials, m.outBases, stream);
+    }
+    hipLaunchKernelGGL(k_ft_totals, dim3(1), dim3(1024), 0, stream, m.emitLines, nChunks,
+                       nChunks ? m.outBases + nChunks : nullptr, outLen,
+                       nEmitted ? nEmitted : m.misc + 6);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if ((phases & 2) && out && outCap && nChunks) {
+    hipLaunchKernelGGL(k_ft_write, dim3(small), dim3(256), 0, stream, data, b, m.emitBytes,
+                       m.outBases, out, outCap);
+  }
+  return hipGetLastError();
+}
+#endif  // REDGPU_TU_DEDUP_TEXT
 
 #if REDGPU_TU_UNIQ_TEXT
 // a raw text's distinct items counted by their bytes (k_uniq_text.h): the line index

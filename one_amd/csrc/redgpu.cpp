@@ -1776,6 +1776,90 @@ uint32_t redgpu_uniq_lds_slots(const redgpu_dfa *dfa) {
   return uniqLdsSlots(img.tableKind, (img.primaryBytes + 15u) & ~15u, img.nStates);
 }
 
+// the arguments of both dedup_text forms
+static int checkDedupText(const redgpu_dfa *dfa, int what, int style, uint64_t keyIndex,
+                          const uint8_t *data, uint64_t len, uint64_t tableSlots,
+                          const uint64_t *outLen) {
+  const bool indexed = what == REDGPU_DEDUP_MATCH || what == REDGPU_DEDUP_FIELD;
+  const char *own = nullptr;
+  if (what < REDGPU_DEDUP_WHOLE || what > REDGPU_DEDUP_FIELD)
+    own = "what is none of REDGPU_DEDUP_WHOLE, _LINES, _MATCH, _FIELD";
+  else if (indexed && keyIndex == 0)
+    own = "key_index is 0";
+  else if (tableSlots < 64 || tableSlots > (1ull << 32) || (tableSlots & (tableSlots - 1)))
+    own = "table_slots is no power of two in [64, 2^32]";
+  // (a key packs offset + 1 above a 24-bit length, as uniq_text's)
+  return checkRawText(dfa, outLen, "null out_len buffer", data, len, own,
+                      what == REDGPU_DEDUP_LINES ? &style : nullptr, 0, 1ull << 31,
+                      (1ull << 40) - 1);
+}
+
+// raw text -> the lines chosen by their keys' strings, as a text (k_dedup_text.h): everything on
+// `stream`, nothing read back; phases as launchDedupText's
+static int dedupTextDev(const redgpu_dfa *dfa, int what, int style, int doLeader,
+                        uint64_t keyIndex, uint64_t minCount, uint64_t maxCount, int invert,
+                        int keepUnkeyed, const uint8_t *data, uint64_t len, uint8_t delim,
+                        uint64_t tableSlots, uint64_t *nLines, uint64_t *nKeyed,
+                        uint64_t *nDistinct, uint64_t *nDropped, uint64_t *nEmitted,
+                        uint64_t *outLen, uint8_t *out, uint64_t outCap, int phases,
+                        hipStream_t s) {
+  if (int rc = checkDedupText(dfa, what, style, keyIndex, data, len, tableSlots, outLen)) return rc;
+  // REDGPU_UNIQ_PLAIN=1: no LDS front, as uniq_text's (measurements)
+  const char *env = getenv("REDGPU_UNIQ_PLAIN");
+  const int plain = env && env[0] == '1';
+  return rawTextDev(dfa, s, dedupTextScratchBytes(len, tableSlots),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchDedupText(dfa->im->dev, what, style, doLeader ? 1 : 0, keyIndex, minCount,
+                           maxCount, invert ? 1 : 0, keepUnkeyed ? 1 : 0, data, len, delim,
+                           tableSlots, plain, nLines, nKeyed, nDistinct, nDropped, nEmitted, outLen,
+                           out, outCap, phases, scratch, cfg, s, name);
+  });
+}
+
+int redgpu_dedup_text_dev(const redgpu_dfa *dfa, int what, int style, int do_leader,
+                          uint64_t key_index, uint64_t min_count, uint64_t max_count, int invert,
+                          int keep_unkeyed, const uint8_t *data, uint64_t len, uint8_t delim,
+                          uint64_t table_slots, uint64_t *n_lines, uint64_t *n_keyed,
+                          uint64_t *n_distinct, uint64_t *n_dropped, uint64_t *n_emitted,
+                          uint64_t *out_len, uint8_t *out, uint64_t out_cap, void *stream) {
+  return dedupTextDev(dfa, what, style, do_leader, key_index, min_count, max_count, invert,
+                      keep_unkeyed, data, len, delim, table_slots, n_lines, n_keyed, n_distinct,
+                      n_dropped, n_emitted, out_len, out, out_cap, 3,
+                      static_cast<hipStream_t>(stream));
+}
+
+// host-buffer form: the text goes up once, then textOutHost; phase 1 leaves the sizes, the table,
+// the bitmaps and the chunks' output bases in the stream's scratch, phase 2 copies the runs
+int redgpu_dedup_text(const redgpu_dfa *dfa, int what, int style, int do_leader, uint64_t key_index,
+                      uint64_t min_count, uint64_t max_count, int invert, int keep_unkeyed,
+                      const uint8_t *data, uint64_t len, uint8_t delim, uint64_t table_slots,
+                      uint64_t *n_lines, uint64_t *n_keyed, uint64_t *n_distinct,
+                      uint64_t *n_dropped, uint64_t *n_emitted, uint64_t *out_len, uint8_t *out,
+                      uint64_t out_cap) {
+  if (int rc = checkDedupText(dfa, what, style, key_index, data, len, table_slots, out_len))
+    return rc;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dSizes = call.buf<uint64_t>(kSlAux1, 6, "sizes");
+  call.upload(dData, data, len, "data");
+  uint64_t sizes[6] = {0, 0, 0, 0, 0, 0};
+  textOutHost(call, dSizes, sizes, 6, 5, out, out_cap,
+              [&](uint8_t *dOut, uint64_t room, int phases) {
+    return dedupTextDev(dfa, what, style, do_leader, key_index, min_count, max_count, invert,
+                        keep_unkeyed, dData, len, delim, table_slots, dSizes, dSizes + 1,
+                        dSizes + 2, dSizes + 3, dSizes + 4, dSizes + 5, dOut, room, phases,
+                        call.stream());
+  });
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = sizes[0];
+  if (n_keyed) *n_keyed = sizes[1];
+  if (n_distinct) *n_distinct = sizes[2];
+  if (n_dropped) *n_dropped = sizes[3];
+  if (n_emitted) *n_emitted = sizes[4];
+  *out_len = sizes[5];
+  return REDGPU_OK;
+}
+
 // raw text -> every match of every line as bytes, one per output line (k_extract_text.h):
 // everything on `stream`, nothing read back; phases as launchExtractText's
 static int extractTextDev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,

@@ -1485,6 +1485,83 @@ def range_text(exe, data, open_result, close_result=None, style=styInstant, do_l
             rec[0, :got].copy(), rec[1, :got].copy(), rec[2, :got].copy(), rec[3, :got].copy())
 
 
+DEDUP_WHOLE, DEDUP_LINES, DEDUP_MATCH, DEDUP_FIELD = 0, 1, 2, 3
+_DEDUP_WHAT = {"whole": DEDUP_WHOLE, "lines": DEDUP_LINES, "match": DEDUP_MATCH,
+               "field": DEDUP_FIELD}
+
+
+def dedup_text(exe, data, *, what="whole", key_index=1, style=styInstant, do_leader=True,
+               min_count=1, max_count=None, invert=False, keep_unkeyed=False, delim=b"\n",
+               max_distinct=1 << 20, out=None, out_cap=None):
+    """redgpu_dedup_text[_dev]: awk '!seen[$k]++' - the delimiter-terminated lines of a raw text
+    buffer chosen by the CONTENT of their keys.  Every line has at most one key: the line itself
+    (what="whole", the DFA is not walked), the line if search<style,doLeader> selects it ("lines",
+    uniq_text's matches=False item), the key_index-th piece extract_text emits for it ("match"),
+    or its key_index-th field with the DFA as the separator ("field", fields_text's rule; a field
+    may be empty); a line without one is unkeyed.  A keyed line is marked iff it holds the earliest
+    occurrence of its key's string and min_count <= count <= max_count (None: no upper bound),
+    count being all the string's occurrences.  Emitted are the keyed lines with marked != invert
+    and, under keep_unkeyed, the unkeyed ones, in text order, each with its delimiter: the defaults
+    are awk '!seen[k]++', (1, 1) is uniq -u and (2, None) uniq -d in text order, invert=True is
+    awk 'seen[k]++'.  The hash table has the power of two at or above 2 * max_distinct (at least
+    64) slots of 16 bytes; n_dropped counts the keyed lines whose key got no record - keys of 2^24
+    bytes or more, and those that found the table full (then call again with a larger
+    max_distinct); they are not marked.  While n_dropped is 0 the output is bit-identical from run
+    to run.  The tail behind the last delimiter is not a line: never emitted, and no key.
+    Host input -> (n_lines, n_keyed, n_distinct, n_dropped, n_emitted, bytes).
+    A CUDA uint8 tensor needs out (a contiguous uint8 CUDA tensor to write into) or out_cap (one
+    of that size is made; 0 gives the sizes only) -> (n_lines, n_keyed, n_distinct, n_dropped,
+    n_emitted, out_len, out): the counts as 1-element int64 tensors, asynchronously on the current
+    stream and without any read-back; out_len may exceed the room, bytes of out from
+    min(out_len, room) on are untouched.  The output is a raw text that every text verb accepts."""
+    l = _lib.lib()
+    d = _delim_byte(delim)
+    if what not in _DEDUP_WHAT:
+        raise RedExceptApi('what must be "whole", "lines", "match" or "field"')
+    w = _DEDUP_WHAT[what]
+    style, lead = int(style), 1 if do_leader else 0
+    inv, keep = 1 if invert else 0, 1 if keep_unkeyed else 0
+    key_index, min_count = int(key_index), int(min_count)
+    max_count = (1 << 64) - 1 if max_count is None else int(max_count)
+    max_distinct = int(max_distinct)
+    if w in (DEDUP_MATCH, DEDUP_FIELD) and key_index < 1:
+        raise RedExceptApi("key_index must be at least 1")
+    if key_index < 0 or key_index >= 1 << 64:
+        raise RedExceptApi("key_index must fit 64 bits")
+    if not (0 <= min_count < 1 << 64 and 0 <= max_count < 1 << 64):
+        raise RedExceptApi("min_count and max_count must be in [0, 2^64)")
+    if max_distinct < 1 or max_distinct > 1 << 31:
+        raise RedExceptApi("max_distinct must be in [1, 2^31]")
+    slots = 64
+    while slots < 2 * max_distinct:
+        slots *= 2
+    if _is_torch(data):
+        import torch
+        dev, ptr, size, stream = _device_raw_text(data)
+        out, room = _device_out_room("dedup_text", data, out, out_cap)
+        cnt = torch.empty(6, dtype=torch.int64, device=dev)
+        at = [cnt.data_ptr() + 8 * k for k in range(6)]
+        _check(l.redgpu_dedup_text_dev(
+            exe._h, w, style, lead, key_index, min_count, max_count, inv, keep, ptr, size, d, slots,
+            at[0], at[1], at[2], at[3], at[4], at[5], out.data_ptr() if room else None, room,
+            stream))
+        return cnt[0:1], cnt[1:2], cnt[2:3], cnt[3:4], cnt[4:5], cnt[5:6], out
+    _host_text_only(out, out_cap)
+    a = _host_u8(data)
+    n = [C.c_uint64(0) for _ in range(6)]
+
+    def call(buf, cap):
+        _check(l.redgpu_dedup_text(
+            exe._h, w, style, lead, key_index, min_count, max_count, inv, keep,
+            a.ctypes.data if a.size else None, a.size, d, slots, C.byref(n[0]), C.byref(n[1]),
+            C.byref(n[2]), C.byref(n[3]), C.byref(n[4]), C.byref(n[5]), buf, cap))
+        return n[5].value
+
+    # the output is no longer than the text
+    text = _host_text_out(a.size, call)
+    return tuple(int(x.value) for x in n[:5]) + (text,)
+
+
 def extract_text(exe, data, *, max_per_line=1 << 62, delim=b"\n", out=None, out_cap=None):
     """redgpu_extract_text[_dev]: grep -o as a text - every match of every delimiter-terminated
     line of a raw text buffer (Red::collect's chain, collect_text's records), as bytes: the span

@@ -1,7 +1,7 @@
 """Differential fuzz on the GPU: random DFAs x random line shapes x every verb / style / leader x
 random placement and kernel-selection flags, against the CPU oracle.  Not part of the pytest
 suite (it is open-ended); a failure prints the case and exits non-zero.
-usage: fuzz_gpu.py [cases] [seed] [hot | cls | lists | blocks | long | text | lines | pieces] [dry]
+usage: fuzz_gpu.py [cases] [seed] [hot | cls | lists | blocks | long | text | lines | pieces | keys] [dry]
 long: the DFAs and placement flags of the general mode, one buffer of 2 KiB to 128 KiB as ONE
 text through collect_long, replace_long, search_long and match_all_long (random style, leader
 setting, chunk size, cap / max count and replacement).  Without a pure dead state an attempt that
@@ -34,7 +34,18 @@ of any cap: max_count, max_ranges, max_per_line, max_fields), a text
 longer than one 16 KiB chunk, an item in the overflow slot, a truncated output, a piece of 64
 bytes or more, a piece that begins in front of its record's start, a number from 2^64, a range or a
 merged context across a chunk border; and one `special` line for the inputs nobody designs.
-tests/test_text_rules.py holds the dry run of the smoke test's cases and seed to floors on these."""
+tests/test_text_rules.py holds the dry run of the smoke test's cases and seed to floors on these.
+keys: dedup_text alone, with cases of its own (the draws of lines and pieces are not touched: their
+dry runs print what they printed before) - a golden or a random DFA under random placement flags,
+a text of 0 to 1,000 lines of which almost half come from a pool of at most 8 strings, whole or with
+something behind them, so that keys repeat, now and then a tail that repeats the first line and
+under `whole` a long line twice; a random mode, key index, style, leader setting, count window,
+invert, keep_unkeyed and delimiter, through the host form one time in three, else the device form
+at a pointer offset of 0 to 15 into a 0x55-filled buffer at out_cap = exact, 0 or half - against
+tests/dedup_rule.py.  dry works as above and ends with one `cover keys dedup_text` line: how many
+cases ran each mode, held a string that occurs twice or more, an unkeyed line, a count window that
+changes the output, an empty key, more than one chunk, a truncated output;
+tests/test_dedup_rule.py holds it to floors."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -729,6 +740,131 @@ def pieces_case(desc, blob, exe, cpu, data):
             return what + shape + (kern,)
     return None
 
+
+# dedup_text: mode keys ----------------------------------------------------------------------------
+KEYS = len(sys.argv) > 3 and sys.argv[3] == "keys"
+KEYS_DRY = KEYS and len(sys.argv) > 4 and sys.argv[4] == "dry"
+WINDOWS = [(1, None), (1, 1), (2, None), (3, 2), (2, 2), (1, 3), (0, 1)]
+
+
+def keys_text(name, what):
+    """(lines, delim): 0 to 1,000 lines (one case in twenty none), almost half of them drawn from a pool
+    of at most 8 strings - whole, or with something behind them - so that keys repeat; where the
+    DFA is walked no line is longer than 230 bytes (a search that does not die is quadratic)"""
+    delim = [0x0A, 0x00, 0x3B][int(rng.integers(0, 3))]
+    n = 0 if rng.random() < 0.05 else int(rng.integers(1, 1001))
+    src = make_data_wide(max(64 * 1024, 1), name)
+    src = src[src != delim]
+    pool = []
+    for _ in range(int(rng.integers(1, 9))):
+        k = int(rng.choice([0, 0, 1, 3, 8, 20, 70]))
+        at = int(rng.integers(0, len(src) - k))
+        pool.append(src[at:at + k].tobytes())
+    if name == "num3" or rng.random() < 0.3:      # keys a number DFA finds, or cuts fields at
+        pool[0] = [b"ab 12 cd 345 ", b"7 up 7", b"12ab", b"x1y22z333"][int(rng.integers(0, 4))]
+    lines = []
+    for _ in range(n):
+        r = rng.random()
+        if r < 0.35:
+            lines.append(pool[int(rng.integers(0, len(pool)))])
+        elif r < 0.45:
+            k = int(rng.integers(1, 30))
+            at = int(rng.integers(0, len(src) - k))
+            lines.append(pool[int(rng.integers(0, len(pool)))] + src[at:at + k].tobytes())
+        else:
+            k = int(rng.choice([0, 1, 5, 30, 60, 120, 200]))
+            at = int(rng.integers(0, len(src) - k))
+            lines.append(src[at:at + k].tobytes())
+    if n and what == "whole" and rng.random() < 0.3:     # one long line, twice
+        k = int(rng.integers(3000, 40000))
+        at = int(rng.integers(0, len(src) - k))
+        for _ in range(2):
+            lines.insert(int(rng.integers(0, len(lines) + 1)), src[at:at + k].tobytes())
+    return lines, delim
+
+
+def keys_main():
+    import dedup_rule as DR
+    import text_rules as TR
+    global PLANTS_WIDE
+    from one_amd import workloads as W
+    PLANTS_WIDE = [b"error", b"an error: x", b"New York", b"123abcd ", b"aab", W.URI_PLANT,
+                   W.URI_USER_PLANT, W.URI_V6_PLANT] + W.log100_heads()[::9]
+    t0 = time.time()
+    stats = {}
+    row = dict(cases=0, whole=0, lines=0, match=0, field=0, repeated=0, unkeyed=0, window=0,
+               empty_key=0, chunk=0, truncated=0)
+    for case in range(cases):
+        if rng.random() < 0.35:
+            name = ["num3", "num3", "aab", "err"][int(rng.integers(0, 4))]
+            blob = load_dfa(name)
+        else:
+            name, blob = make_dfa_wide()
+        flags = {}
+        for f, p in (("force_global", 0.15), ("force_hot", 0.2)):
+            if rng.random() < p:
+                flags[f] = True
+        if rng.random() < 0.3:
+            flags["lds_table_max"] = int(rng.choice([8 * 256, 40 * 256, 100 * 256, 20000, 70000]))
+        try:
+            exe = one_amd.Executable(blob, **(dict(device="none") if KEYS_DRY else {}), **flags)
+        except one_amd.RedExcept as e:
+            print("create refused:", name, flags, e)
+            continue
+        cpu = O.CpuOracle(blob)
+        # (every second draw takes the modes in turn: none of them is rare under any seed)
+        what = DR.WHATS[case % 4 if rng.random() < 0.5 else int(rng.integers(0, 4))]
+        key_index = int(rng.choice([1, 1, 1, 2, 2, 3, 9]))
+        sty, lead = int(rng.integers(1, 6)), int(rng.integers(0, 2))
+        lo, hi = WINDOWS[int(rng.choice(len(WINDOWS), p=[0.25, 0.2, 0.2, 0.05, 0.1, 0.15, 0.05]))]
+        invert, keep = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+        lines, delim = keys_text(name, what)
+        d = bytes([delim])
+        tail = [b"", b"", lines[0] if lines else b"tail"][int(rng.integers(0, 3))]
+        data = np.frombuffer(b"".join(x + d for x in lines) + tail, dtype=np.uint8).copy()
+        desc = (case, name, flags, what, key_index, sty, lead, (lo, hi), invert, keep, delim,
+                len(data))
+        t = TR.Text(cpu, data.tobytes(), delim)
+        per = DR.keys(t, what, key_index, sty, lead)
+        kw = dict(min_count=lo, max_count=DR.MAX if hi is None else hi, invert=invert,
+                  keep_unkeyed=keep)
+        want = DR.dedup(t, what, key_index, sty, lead, **kw)
+        strings = [k[1] for k in per if k is not None]
+        plain = DR.dedup(t, what, key_index, sty, lead, invert=invert, keep_unkeyed=keep)
+        dev, shift, kind = draw_form(True)
+        row["cases"] += 1
+        row[what] += 1
+        row["repeated"] += len(set(strings)) < len(strings)
+        row["unkeyed"] += None in per
+        row["window"] += (lo, hi) != (1, None) and want != plain
+        row["empty_key"] += b"" in strings
+        row["chunk"] += len(data) > CHUNK
+        row["truncated"] += dev and kind != "exact" and len(want[5]) > 1
+        if not KEYS_DRY:
+            call = lambda x, **more: one_amd.dedup_text(      # noqa: E731
+                exe, x, what=what, key_index=key_index, style=sty, do_leader=bool(lead),
+                min_count=lo, max_count=hi, invert=invert, keep_unkeyed=keep, delim=d,
+                max_distinct=512, **more)
+            try:
+                ok = wrote(call, data, shift, kind, want, 5) if dev else call(data) == want
+            except one_amd.RedExcept as e:
+                print("ERROR", desc, e)
+                sys.exit(1)
+            kern = one_amd.last_kernel()
+            stats[kern] = stats.get(kern, 0) + 1
+            if not ok:
+                print("MISMATCH", desc, "dedup_text", "dev" if dev else "host", shift, kind)
+                sys.exit(1)
+        if case % 25 == 0:
+            print("case", case, "%.0fs" % (time.time() - t0), flush=True)
+    print("cover keys dedup_text", " ".join("%s=%d" % kv for kv in row.items()))
+    print("fuzz dry:" if KEYS_DRY else "fuzz ok:", cases, "cases; kernels:",
+          dict(sorted(stats.items())))
+
+
+if KEYS:
+    keys_main()
+    sys.exit(0)
 
 t0 = time.time()
 stats = {}
