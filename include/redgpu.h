@@ -1185,6 +1185,90 @@ int redgpu_sum_text_dev(const redgpu_dfa *dfa, int which, const uint8_t *data, u
                         void *stream);
 uint32_t redgpu_sum_lds_bins(const redgpu_dfa *dfa);
 
+/* awk '{ n[$k]++; s[$k] += $v; if ($v > m[$k]) m[$k] = $v }': raw text in, ONE RECORD PER KEY out -
+ * bytes served per client address, latency minimum and maximum per endpoint, rows and total per
+ * customer id.  redgpu_sum_text groups the numbers by result number and redgpu_uniq_text counts
+ * strings; this verb keeps redgpu_sum_text's four statistics per distinct key STRING.
+ *  - Lines are redgpu_split_lines' lines: [start, delimiter), the next one begins behind the
+ *    delimiter, bytes after the last delimiter (the tail) are not a line and contribute nothing.
+ *  - The ITEMS of a line, numbered from 1 (redgpu_dedup_text's key rule, word for word):
+ *      what == REDGPU_GROUP_MATCH: item j is the j-th piece redgpu_extract_text would emit for the
+ *        line.
+ *      what == REDGPU_GROUP_FIELD: the DFA is the SEPARATOR and item j is field j under
+ *        redgpu_fields_text's field rule with every separator counted (max_fields == 0).  A field
+ *        may be EMPTY - the empty field at the very end of a line included.
+ *  - key_index (>= 1) names the line's KEY item and value_index (0 = no value) its VALUE item;
+ *    value_index may be below, equal to or above key_index.  A line with fewer than key_index items
+ *    is UNKEYED and contributes nothing: its value is not looked at.  The line is not walked behind
+ *    its max(key_index, value_index)-th piece (MATCH) or separator (FIELD).
+ *  - The value's number follows redgpu_sum_text's rule on the value item's OWN bytes: its first
+ *    (which == REDGPU_SUM_FIRST) or last (REDGPU_SUM_LAST) maximal run of digits 0x30..0x39, read as
+ *    an unsigned decimal; leading zeros are allowed, and digits next to the item but outside it are
+ *    not seen.  A keyed line is NUMERIC iff its value item exists, has a run, and the run's value is
+ *    below 2^64.  With value_index == 0 no line is numeric.
+ *  - Two keys are equal iff their bytes are.  There is one record per distinct key string, in the
+ *    order of FIRST APPEARANCE (redgpu_uniq_text's order): first[j] is strictly ascending.
+ *      first[j], length[j]: the key is data[first[j], first[j] + length[j]), its earliest occurrence;
+ *      count[j]: the keyed lines with that key;
+ *      stats: four rows with row stride cap - stats[row * cap + j], the rows REDGPU_SUM_COUNT (the
+ *        key's numeric lines), REDGPU_SUM_SUM (modulo 2^64), REDGPU_SUM_MIN and REDGPU_SUM_MAX.  A key
+ *        without numeric lines has 0, 0, 2^64 - 1, 0.
+ *    Exactly min(*n_distinct, cap) records are written and nothing behind them in any array, no row
+ *    of stats excepted.  Each of the four arrays may be NULL on its own; cap == 0 gives the scalars
+ *    only.
+ *  - *n_lines = delimiters found; *n_keyed = keyed lines, dropped ones included; *n_numeric =
+ *    numeric lines whose key holds a record (the sum of the COUNT row over ALL records, whatever cap
+ *    is); *n_distinct = the strings that hold a record, whatever cap is; *n_dropped = keyed lines in
+ *    no record.  Over all records sum(count) + *n_dropped == *n_keyed.  Each of the five may be
+ *    NULL.
+ *  - table_slots is the size of the hash table the strings are kept in, as redgpu_uniq_text's: a
+ *    power of two, 64 <= table_slots <= 2^32; here a slot takes 16 + 32 bytes from the thread's
+ *    scratch pool.
+ *  - A key is dropped in redgpu_uniq_text's two cases: it is 2^24 bytes or longer (decided before it
+ *    is hashed, deterministic), or the table is full and does not hold its string.  A dropped line
+ *    enters no record, neither with its count nor with its number.  A record that exists is exact in
+ *    all seven values whatever was dropped: a line is either wholly in its key's record or dropped.
+ *  - *n_dropped == 0: every output is bit-identical from run to run - all operations are commutative
+ *    integer operations.  When the table overflows, *n_distinct == table_slots and WHICH strings
+ *    hold the records depends on scheduling; the remedy is the caller's: a larger table.
+ *  - REDGPU_EAPI for a NULL handle, a NULL data with len > 0, a `what` other than the two below, a
+ *    `which` other than redgpu_sum_text's two, key_index == 0, a table_slots that is no power of two
+ *    in [64, 2^32] - the message names the argument - (the argument checks run before the handle's
+ *    device is looked at) and for a REDGPU_DEVICE_NONE handle; REDGPU_ELIMIT for a text
+ *    redgpu_split_lines refuses or one of 2^40 - 1 bytes or more.  In every error case nothing of
+ *    the caller's is written.
+ *  - An empty text, or one without a delimiter: the five scalars are 0 and no record is written
+ *    (the _dev form writes the scalars on the stream).
+ *  - A single line of megabytes is walked by one lane and a table near full is probed slot by slot:
+ *    correct, and slow.
+ * redgpu_last_kernel() says "k_group_text": there is no other route.
+ * _dev: every pointer device memory; asynchronous on `stream` from end to end - nothing is read
+ * back, and there is no per-line array (scratch is 16 + 32 bytes per slot - the table and the
+ * statistics beside it - + len / 4 for the two bitmaps + 164 bytes per 16 KiB chunk + 8 bytes per
+ * 1,024 chunks + 72, rounded up to 16, from the thread's pool).  A text of 4 GiB or more runs
+ * without the on-chip front of the table, as redgpu_uniq_text's: the same output.
+ * redgpu_group_text: host buffers - one upload of the text, the table in the stream's scratch,
+ * device records of the call's own, then the five scalars and min(*n_distinct, cap) records back.
+ * redgpu_group_lds_slots: how many (string, count, statistics) slots a workgroup keeps in on-chip
+ * memory (LDS) for this handle: the largest power of two <= 256 that the table leaves room for in a
+ * workgroup's share of the LDS at 48 bytes a slot, or 0 when that is below 64.  The results do not
+ * depend on it; REDGPU_UNIQ_PLAIN=1 in the environment runs without the front.  A pure host
+ * function, valid for REDGPU_DEVICE_NONE handles too; 0 for a NULL handle. */
+#define REDGPU_GROUP_MATCH 0  /* item j = piece number j of the line (extract_text's pieces) */
+#define REDGPU_GROUP_FIELD 1  /* the DFA is the SEPARATOR; item j = field number j (fields_text's fields, max_fields = 0) */
+int redgpu_group_text(const redgpu_dfa *dfa, int what, uint64_t key_index, uint64_t value_index,
+                      int which, const uint8_t *data, uint64_t len, uint8_t delim,
+                      uint64_t table_slots, uint64_t cap, uint64_t *n_lines, uint64_t *n_keyed,
+                      uint64_t *n_numeric, uint64_t *n_distinct, uint64_t *n_dropped,
+                      uint64_t *first, uint64_t *length, uint64_t *count, uint64_t *stats);
+int redgpu_group_text_dev(const redgpu_dfa *dfa, int what, uint64_t key_index, uint64_t value_index,
+                          int which, const uint8_t *data, uint64_t len, uint8_t delim,
+                          uint64_t table_slots, uint64_t cap, uint64_t *n_lines, uint64_t *n_keyed,
+                          uint64_t *n_numeric, uint64_t *n_distinct, uint64_t *n_dropped,
+                          uint64_t *first, uint64_t *length, uint64_t *count, uint64_t *stats,
+                          void *stream);
+uint32_t redgpu_group_lds_slots(const redgpu_dfa *dfa);
+
 /* Measurement aid, no counterpart in the reference: one streaming read of `bytes` of device
  * memory (16-byte aligned) on the handle's device, asynchronous on `stream` - the read-bandwidth
  * calibration bench.py reports beside the roofline.  `sink` is a device uint32 the kernel may

@@ -512,6 +512,53 @@ inline DedupResult dedupText(const Executable &exec, std::string_view text,
   return r;
 }
 
+// one key of groupText: the key is text.substr(first, length), its earliest occurrence; count = the
+// keyed lines with that key; numeric / sum (modulo 2^64) / min / max over those of them that have a
+// number (0, 0, 2^64 - 1, 0 without any)
+struct GroupRecord {
+  uint64_t first, length, count, numeric, sum, min, max;
+};
+
+// what groupText says: the records in the order of first appearance and redgpu_group_text's scalars
+struct GroupResult {
+  std::vector<GroupRecord> records;
+  uint64_t lines = 0, keyed = 0, numeric = 0, distinct = 0, dropped = 0;
+};
+
+// which items a line is cut into (REDGPU_GROUP_*)
+enum GroupWhat { groupMatch = 0, groupField = 1 };
+
+// awk '{ n[$k]++; s[$k] += $v; if ($v > m[$k]) m[$k] = $v }' (redgpu_group_text): one GroupRecord
+// per distinct key string of a text blob's lines.  A line's items are the pieces extractText emits
+// for it (groupMatch) or its fields with the DFA as the separator (groupField), numbered from 1;
+// item keyIndex is the key - a line with fewer items is unkeyed - and item valueIndex (0 = none) the
+// value, whose number is sumText's: the first (last = false) or last run of digits 0-9 inside the
+// item.  The hash table holds the power of two at or above 2 * maxDistinct (at least 64) strings;
+// dropped = the keyed lines in no record (a key of 2^24 bytes or longer, or the table was full: call
+// again with a larger maxDistinct), which enter no record with either their count or their number.
+inline GroupResult groupText(const Executable &exec, std::string_view text,
+                             GroupWhat what = groupField, size_t keyIndex = 1,
+                             size_t valueIndex = 2, bool last = false,
+                             size_t maxDistinct = size_t(1) << 20, char delim = '\n') {
+  uint64_t slots = 64;
+  while (slots < 2 * uint64_t(maxDistinct) && slots < (1ull << 32)) slots *= 2;
+  const uint64_t rows = slots < text.size() ? slots : text.size();
+  std::vector<uint64_t> first(rows), length(rows), count(rows), stats(4 * rows);
+  GroupResult r;
+  throwOnError(redgpu_group_text(exec.handle(), what, keyIndex, valueIndex,
+                                 last ? REDGPU_SUM_LAST : REDGPU_SUM_FIRST,
+                                 reinterpret_cast<const Byte *>(text.data()), text.size(),
+                                 Byte(delim), slots, rows, &r.lines, &r.keyed, &r.numeric,
+                                 &r.distinct, &r.dropped, first.data(), length.data(),
+                                 count.data(), stats.data()));
+  r.records.resize(size_t(r.distinct < rows ? r.distinct : rows));
+  for (size_t j = 0; j < r.records.size(); ++j)
+    r.records[j] = GroupRecord{first[j], length[j], count[j],
+                               stats[REDGPU_SUM_COUNT * rows + j], stats[REDGPU_SUM_SUM * rows + j],
+                               stats[REDGPU_SUM_MIN * rows + j], stats[REDGPU_SUM_MAX * rows + j]};
+  return r;
+}
+
 // grep -o as a text (redgpu_extract_text): every match of every line of a text blob put in `out`,
 // one per line - the bytes replace<styLast,false> would substitute, each followed by the delimiter,
 // in text order; at most maxPerLine of a line (1 = its first match).  Output line j is the bytes of

@@ -211,6 +211,14 @@ def lib() -> C.CDLL:
                                            u64, u64, vp, vp, vp, vp, vp, vp, vp, vp]
         l.redgpu_uniq_lds_slots.restype = C.c_uint32
         l.redgpu_uniq_lds_slots.argtypes = [vp]
+        l.redgpu_group_text.restype = C.c_int
+        l.redgpu_group_text.argtypes = [vp, C.c_int, u64, u64, C.c_int, vp, u64, C.c_uint8, u64,
+                                        u64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        l.redgpu_group_text_dev.restype = C.c_int
+        l.redgpu_group_text_dev.argtypes = [vp, C.c_int, u64, u64, C.c_int, vp, u64, C.c_uint8,
+                                            u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        l.redgpu_group_lds_slots.restype = C.c_uint32
+        l.redgpu_group_lds_slots.argtypes = [vp]
         l.redgpu_dedup_text.restype = C.c_int
         l.redgpu_dedup_text.argtypes = [vp, C.c_int, C.c_int, C.c_int, u64, u64, u64, C.c_int,
                                         C.c_int, vp, u64, C.c_uint8, u64, vp, vp, vp, vp, vp, vp,

@@ -123,37 +123,49 @@ __device__ __forceinline__ unsigned long long uqKey(uint64_t a, uint64_t n) {
   return ((a + 1) << 24) | n;
 }
 
-// `weight` occurrences of data[a, a + n), hash h, the earliest of them at a: false = the table is
-// full and does not hold the string
-__device__ __forceinline__ bool uqInsert(const UqOut &o, const uint8_t *data, uint64_t len,
-                                         uint64_t a, uint64_t n, uint64_t h,
-                                         unsigned long long weight) {
+constexpr uint64_t kUqNoSlot = ~0ull;  // (no table has this many slots)
+
+// `weight` occurrences of data[a, a + n), hash h, the earliest of them at a: the slot that holds the
+// string now, or kUqNoSlot = the table is full and does not hold it
+__device__ __forceinline__ uint64_t uqInsertSlot(unsigned long long *table, uint64_t slots,
+                                                 const uint8_t *data, uint64_t len, uint64_t a,
+                                                 uint64_t n, uint64_t h,
+                                                 unsigned long long weight) {
   const unsigned long long mine = uqKey(a, n);
-  const uint64_t mask = o.slots - 1;
+  const uint64_t mask = slots - 1;
   uint64_t s = h & mask;
-  for (uint64_t probe = 0; probe < o.slots; ++probe, s = (s + 1) & mask) {
-    unsigned long long *slot = o.table + 2 * s;
+  for (uint64_t probe = 0; probe < slots; ++probe, s = (s + 1) & mask) {
+    unsigned long long *slot = table + 2 * s;
     unsigned long long k = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (k == 0) k = atomicCAS(slot, 0ull, mine);
     if (k == 0) {
       atomicAdd(slot + 1, weight);
-      return true;
+      return s;
     }
     if ((k & (kUqMaxItem - 1)) == n && uqEqual(data, len, (k >> 24) - 1, a, n)) {
       atomicAdd(slot + 1, weight);
       if (mine < k) atomicMin(slot, mine);
-      return true;
+      return s;
     }
   }
-  return false;
+  return kUqNoSlot;
 }
 
-// one occurrence of data[a, a + n) into the workgroup's front: false = no place within
-// kUqFrontProbes slots (or there is no front)
-__device__ __forceinline__ bool uqFront(unsigned long long *keys, uint32_t *counts, uint32_t L,
-                                        const uint8_t *data, uint64_t len, uint64_t a, uint64_t n,
-                                        uint64_t h) {
-  if (!L) return false;
+// the same for a caller that needs no slot: false = the table is full and does not hold the string
+__device__ __forceinline__ bool uqInsert(const UqOut &o, const uint8_t *data, uint64_t len,
+                                         uint64_t a, uint64_t n, uint64_t h,
+                                         unsigned long long weight) {
+  return uqInsertSlot(o.table, o.slots, data, len, a, n, h, weight) != kUqNoSlot;
+}
+
+constexpr uint32_t kUqNoFront = ~0u;
+
+// one occurrence of data[a, a + n) into the workgroup's front: the front's slot that counted it, or
+// kUqNoFront = no place within kUqFrontProbes slots (or there is no front)
+__device__ __forceinline__ uint32_t uqFrontSlot(unsigned long long *keys, uint32_t *counts,
+                                                uint32_t L, const uint8_t *data, uint64_t len,
+                                                uint64_t a, uint64_t n, uint64_t h) {
+  if (!L) return kUqNoFront;
   const unsigned long long mine = uqKey(a, n);
   // (the slot from the hash's high bits: the global slot takes the low ones)
   volatile uint32_t *tags = counts + L;
@@ -166,7 +178,7 @@ __device__ __forceinline__ bool uqFront(unsigned long long *keys, uint32_t *coun
       if (k == 0) {
         tags[s] = tag;
         atomicAdd(counts + s, 1u);
-        return true;
+        return s;
       }
     }
     const uint32_t t = tags[s];
@@ -174,10 +186,17 @@ __device__ __forceinline__ bool uqFront(unsigned long long *keys, uint32_t *coun
         uqEqual(data, len, (k >> 24) - 1, a, n)) {
       atomicAdd(counts + s, 1u);
       if (mine < k) atomicMin(keys + s, mine);
-      return true;
+      return s;
     }
   }
-  return false;
+  return kUqNoFront;
+}
+
+// the same for a caller that needs no slot: false = no place (or there is no front)
+__device__ __forceinline__ bool uqFront(unsigned long long *keys, uint32_t *counts, uint32_t L,
+                                        const uint8_t *data, uint64_t len, uint64_t a, uint64_t n,
+                                        uint64_t h) {
+  return uqFrontSlot(keys, counts, L, data, len, a, n, h) != kUqNoFront;
 }
 
 // the workgroup's front flushed through the global insert, weighted by its counts (every thread
@@ -297,8 +316,24 @@ k_uq_pop(const uint16_t *firstBits, uint64_t nChunks, uint64_t *pops, uint16_t *
   }
 }
 
-// per occupied slot: its record's rank = the strings that first appear in front of it, and the
-// record when the rank is below the cap; *nDistinct = the scan's total
+// the rank of the record whose string first appears at `at` = the strings that first appear in front
+// of it; a value at or above cap may be short of the rank (the caller writes nothing then)
+__device__ __forceinline__ uint64_t uqRank(uint64_t at, const uint32_t *firstBits,
+                                           const uint64_t *popBases, const uint16_t *lanePre,
+                                           uint64_t cap) {
+  uint64_t rank = popBases[at / kSplitChunk];
+  if (rank >= cap) return rank;
+  // the chunk's bits in front of the 256 the bit is among, those words in front of the bit's
+  // own, then the bits below it
+  rank += lanePre[at >> 8];
+  const uint64_t w0 = (at >> 8) << 3, w1 = at >> 5;
+  for (uint64_t w = w0; w < w1; ++w) rank += uint32_t(__popc(firstBits[w]));
+  rank += uint32_t(__popc(firstBits[w1] & ((1u << (at & 31u)) - 1u)));
+  return rank;
+}
+
+// per occupied slot: its record's rank (uqRank), and the record when the rank is below the cap;
+// *nDistinct = the scan's total
 __global__ void __launch_bounds__(256)
 k_uq_emit(const unsigned long long *table, uint64_t slots, const uint32_t *firstBits,
           const uint64_t *popBases, const uint16_t *lanePre, uint64_t nChunks, uint64_t cap,
@@ -311,15 +346,7 @@ k_uq_emit(const unsigned long long *table, uint64_t slots, const uint32_t *first
     const unsigned long long k = table[2 * s];
     if (!k) continue;
     const uint64_t at = (k >> 24) - 1;
-    const uint64_t ch = at / kSplitChunk;
-    uint64_t rank = popBases[ch];
-    if (rank >= cap) continue;
-    // the chunk's bits in front of the 256 the bit is among, those words in front of the bit's
-    // own, then the bits below it
-    rank += lanePre[at >> 8];
-    const uint64_t w0 = (at >> 8) << 3, w1 = at >> 5;
-    for (uint64_t w = w0; w < w1; ++w) rank += uint32_t(__popc(firstBits[w]));
-    rank += uint32_t(__popc(firstBits[w1] & ((1u << (at & 31u)) - 1u)));
+    const uint64_t rank = uqRank(at, firstBits, popBases, lanePre, cap);
     if (rank >= cap) continue;
     if (first) first[rank] = at;
     if (length) length[rank] = k & (kUqMaxItem - 1);

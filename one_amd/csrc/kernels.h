@@ -408,6 +408,29 @@ hipError_t launchDedupText(const DevDfa &dfa, int what, int style, int doLeader,
                            uint64_t outCap, int phases, void *scratch, const LaunchCfg &cfg,
                            hipStream_t stream, const char **kernelName);
 
+// a raw text's lines grouped by their keys' strings, with the numbers of a second item of the line
+// (k_group_text.h): an item is a piece launchExtractText would emit for the line (what =
+// REDGPU_GROUP_MATCH) or a field launchFieldsText cuts it into (FIELD); item keyIndex (>= 1) is the
+// key - a line without one is unkeyed - and item valueIndex (0 = none) the value, whose number is
+// launchSumText's under `which`.  Record j = distinct key string j in the order of first
+// appearance: first[j], length[j], count[j] = its keyed lines, stats[row * cap + j] = count, sum
+// (modulo 2^64), min, max of its numeric lines (0, 0, ~0, 0 without any); the first
+// min(*nDistinct, cap) records written and nothing behind them (each array may be null).
+// *nKeyed = keyed lines, *nNumeric = numeric lines whose key holds a record, *nDropped = keyed lines
+// in no record (a key of 2^24 bytes or more, or the table full); every counter may be null.
+// tableSlots a power of two.  plain = 1: no LDS front.  scratch: groupTextScratchBytes(len,
+// tableSlots) bytes of device memory, 16-byte aligned.  *kernelName = "k_group_text".
+// groupLdsSlots: the slots of the LDS front for a DFA of this table (0 = the table leaves no room).
+uint64_t groupTextScratchBytes(uint64_t len, uint64_t tableSlots);
+uint32_t groupLdsSlots(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates);
+hipError_t launchGroupText(const DevDfa &dfa, int what, uint64_t keyIndex, uint64_t valueIndex,
+                           int which, const uint8_t *data, uint64_t len, uint8_t delim,
+                           uint64_t tableSlots, uint64_t cap, int plain, uint64_t *nLines,
+                           uint64_t *nKeyed, uint64_t *nNumeric, uint64_t *nDistinct,
+                           uint64_t *nDropped, uint64_t *first, uint64_t *length, uint64_t *count,
+                           uint64_t *stats, void *scratch, const LaunchCfg &cfg,
+                           hipStream_t stream, const char **kernelName);
+
 // bench.py's read-bandwidth calibration: one streaming pass over `bytes` (16-byte aligned).
 hipError_t launchDiagRead(const void *data, uint64_t bytes, uint32_t *sink, int numCUs,
                           hipStream_t stream);

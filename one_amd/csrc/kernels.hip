@@ -75,6 +75,9 @@
 //   k_dedup_text.h    k_dd_*: awk '!seen[$k]++' over a raw text - k_uniq_text.h's walk and table with one key
 //                     per line, a pass that turns table slots into line bits, the EMIT bitmap from
 //                     three bitmaps, and k_filter_text.h's run copy
+//   k_group_text.h    k_gr_*: awk '{ s[$k] += $v }' over a raw text - k_dedup_text.h's walk with a key and a
+//                     value per line, k_uniq_text.h's table and front with four 64-bit statistics beside
+//                     each slot, and its ordering pass
 //   k_diag.h         bench.py's calibration kernels
 //   launchers.h       grid / LDS / instantiation per family; includes k_chunk.h (speculative
 //                     chunking of few long lines)
@@ -87,12 +90,13 @@
 
 #include "../../include/redgpu.h"
 
-// This file is compiled fourteen times in parallel (Makefile: -DREDGPU_TU=1/2/.../14): the templates are
+// This file is compiled fifteen times in parallel (Makefile: -DREDGPU_TU=1/2/.../15): the templates are
 // instantiated where their launchers are CALLED, so each translation unit only pays for one
 // family of kernels - 1 = the fixed-stride family (k_stream, k_chunk, k_fixed), 2 = k_ragged,
 // 3 = everything else and the dispatch, 4 = k_grep and k_filter_text (which runs k_grep's select), 5 = k_collect_text, 6 = k_replace_text,
 // 7 = k_tally_text, 8 = k_extract_text, 9 = k_route_text, 10 = k_uniq_text,
-// 11 = k_fields_text, 12 = k_sum_text, 13 = k_range_text, 14 = k_dedup_text.
+// 11 = k_fields_text, 12 = k_sum_text, 13 = k_range_text, 14 = k_dedup_text,
+// 15 = k_group_text.
 // REDGPU_TU undefined or 0 = all of it in one unit.
 #ifndef REDGPU_TU
 #define REDGPU_TU 0
@@ -111,6 +115,7 @@
 #define REDGPU_TU_SUM_TEXT (REDGPU_TU == 0 || REDGPU_TU == 12)
 #define REDGPU_TU_RANGE_TEXT (REDGPU_TU == 0 || REDGPU_TU == 13)
 #define REDGPU_TU_DEDUP_TEXT (REDGPU_TU == 0 || REDGPU_TU == 14)
+#define REDGPU_TU_GROUP_TEXT (REDGPU_TU == 0 || REDGPU_TU == 15)
 
 // return CALL(KIND) for the table kind of the DevDfa `d` in scope: a launcher's instantiation per kind
 #define REDGPU_KIND_SWITCH(CALL)                                                          \
@@ -162,6 +167,7 @@ namespace {
 #include "k_sum_text.h"
 #include "k_range_text.h"
 #include "k_dedup_text.h"
+#include "k_group_text.h"
 
 } // namespace
 
@@ -1882,6 +1888,110 @@ hipError_t launchUniqText(const DevDfa &d, int what, int style, int doLeader, co
   return hipGetLastError();
 }
 #endif  // REDGPU_TU_UNIQ_TEXT
+
+#if REDGPU_TU_GROUP_TEXT
+// a raw text's lines grouped by their keys' strings (k_group_text.h): the line index (launchTextIndex,
+// which also zeroes the FIRST bitmap), k_uq_zero, k_gr_zero, the one pass of k_group_text, and
+// k_uniq_text.h's ordering pass with k_gr_emit at its end.  scratch: groupTextScratchBytes(len,
+// tableSlots) bytes, 16-byte aligned: 16 + 32 bytes per slot, the two bitmaps (len / 4), 164 bytes
+// per chunk, 8 per 1,024 chunks and 72, rounded up to 16.
+struct GroupScratch {
+  uint64_t *table;          // [2 * slots]
+  uint64_t *side;           // [4][slots]: numeric count, sum, min, max
+  uint64_t *bases, *open;   // [nChunks] each
+  uint64_t *pops;           // [nChunks]
+  uint64_t *popBases;       // [nChunks + 1]
+  uint64_t *partials;       // [nPart]
+  // [8]: lines, the scan's two spare words, keyed, dropped, distinct, numeric, 1 spare
+  uint64_t *misc;
+  uint32_t *counts;         // [nChunks]
+  uint16_t *lanePre;        // [64 * nChunks]
+  uint16_t *masks, *firsts; // the delimiter bitmap, the FIRST bitmap
+  uint64_t nPart, bytes;
+  GroupScratch(void *scratch, uint64_t nChunks, uint64_t slots) : nPart((nChunks + 1023) / 1024) {
+    Carve c{static_cast<uint8_t *>(scratch)};
+    table = c.take<uint64_t>(2 * slots);
+    side = c.take<uint64_t>(4 * slots);
+    bases = c.take<uint64_t>(nChunks);
+    open = c.take<uint64_t>(nChunks);
+    pops = c.take<uint64_t>(nChunks);
+    popBases = c.take<uint64_t>(nChunks + 1);
+    partials = c.take<uint64_t>(nPart);
+    misc = c.take<uint64_t>(8);
+    counts = c.take<uint32_t>(nChunks);
+    lanePre = c.take<uint16_t>(64 * nChunks);
+    c.align(16);
+    masks = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    firsts = c.take<uint16_t>(nChunks * (kSplitChunk / 16));
+    bytes = c.at;
+  }
+};
+
+uint64_t groupTextScratchBytes(uint64_t len, uint64_t tableSlots) {
+  return GroupScratch(nullptr, splitChunks(len), tableSlots).bytes;
+}
+
+uint32_t groupLdsSlots(uint32_t tableKind, uint32_t tableBytes, uint32_t nStates) {
+  const DevDfa d = ldsRoomDfa(tableKind, tableBytes, nStates);
+#define GR_SLOTS(K) groupLdsSlotsK<K>(d)
+  REDGPU_KIND_SWITCH(GR_SLOTS)
+#undef GR_SLOTS
+}
+
+hipError_t launchGroupText(const DevDfa &d, int what, uint64_t keyIndex, uint64_t valueIndex,
+                           int which, const uint8_t *data, uint64_t len, uint8_t delim,
+                           uint64_t tableSlots, uint64_t cap, int plain, uint64_t *nLines,
+                           uint64_t *nKeyed, uint64_t *nNumeric, uint64_t *nDistinct,
+                           uint64_t *nDropped, uint64_t *first, uint64_t *length, uint64_t *count,
+                           uint64_t *stats, void *scratch, const LaunchCfg &cfg,
+                           hipStream_t stream, const char **kernelName) {
+  *kernelName = "k_group_text";
+  const uint64_t nChunks = splitChunks(len);
+  const GroupScratch m(scratch, nChunks, tableSlots);
+  hipError_t e = launchTextIndex(data, len, delim, nLines, m.counts, m.bases, m.masks, m.open,
+                                 m.firsts, m.misc, cfg.numCUs, stream);
+  if (e != hipSuccess) return e;
+  if (!nDistinct) nDistinct = m.misc + 5;
+  GrOut o{reinterpret_cast<unsigned long long *>(m.table),
+          reinterpret_cast<unsigned long long *>(m.side), tableSlots,
+          reinterpret_cast<unsigned long long *>(nKeyed ? nKeyed : m.misc + 3),
+          reinterpret_cast<unsigned long long *>(nDropped ? nDropped : m.misc + 4),
+          reinterpret_cast<unsigned long long *>(nNumeric ? nNumeric : m.misc + 6), 0};
+  // (an empty text needs no table: the counters alone are zeroed)
+  const uint64_t words = nChunks ? 2 * tableSlots : 0;
+  const uint32_t zb = wordBlocks(words, cfg.numCUs);
+  hipLaunchKernelGGL(k_uq_zero, dim3(zb ? zb : 1), dim3(256), 0, stream, o.table, words, o.nKeyed,
+                     o.nDropped, nDistinct);
+  const uint64_t cells = nChunks ? tableSlots : 0;
+  const uint32_t sb = wordBlocks(cells, cfg.numCUs);
+  hipLaunchKernelGGL(k_gr_zero, dim3(sb ? sb : 1), dim3(256), 0, stream, o.side, cells, o.nNumeric);
+  e = hipGetLastError();
+  if (e != hipSuccess || nChunks == 0) return e;
+  // L: the front's slots, by k_uniq_text.h's rule: none for a text of 4 GiB and more (32-bit counts)
+  // and under plain
+  if (!plain && len < (1ull << 32)) o.ldsSlots = groupLdsSlots(d.tableKind, d.tableBytes, d.nStates);
+  const GpBufs b{m.masks, nullptr, m.bases, m.open, nullptr, nullptr, nChunks};
+#define GR_ARGS d, data, len, b, keyIndex, valueIndex, which, o, cfg, stream
+#define GR_CALL(K)                                                      \
+  (what == REDGPU_GROUP_MATCH ? launchGroupK<K, kGrMatch>(GR_ARGS)      \
+                              : launchGroupK<K, kGrField>(GR_ARGS))
+  e = [&]() -> hipError_t { REDGPU_KIND_SWITCH(GR_CALL) }();
+#undef GR_CALL
+#undef GR_ARGS
+  if (e != hipSuccess) return e;
+  // the grid of the passes over the table
+  const uint32_t tb = wordBlocks(tableSlots, cfg.numCUs);
+  hipLaunchKernelGGL(k_uq_mark, dim3(tb), dim3(256), 0, stream, o.table, tableSlots,
+                     reinterpret_cast<uint32_t *>(m.firsts));
+  hipLaunchKernelGGL(k_uq_pop, dim3(smallBlocks(nChunks, cfg.numCUs)), dim3(256), 0, stream,
+                     m.firsts, nChunks, m.pops, m.lanePre);
+  launchScan64(m.pops, nChunks, m.partials, m.popBases, stream);
+  hipLaunchKernelGGL(k_gr_emit, dim3(tb), dim3(256), 0, stream, o.table, o.side, tableSlots,
+                     reinterpret_cast<const uint32_t *>(m.firsts), m.popBases, m.lanePre, nChunks,
+                     cap, first, length, count, stats, nDistinct);
+  return hipGetLastError();
+}
+#endif  // REDGPU_TU_GROUP_TEXT
 
 #if REDGPU_TU_GENERIC
 hipError_t launchBatches(const DevDfa &d, const Batch *bs, uint32_t nb, int verb, int style,

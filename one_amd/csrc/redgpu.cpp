@@ -1860,6 +1860,95 @@ int redgpu_dedup_text(const redgpu_dfa *dfa, int what, int style, int do_leader,
   return REDGPU_OK;
 }
 
+// the arguments of both group_text forms (every output may be NULL: the handle stands in for the
+// buffer checkRawText asks for)
+static int checkGroupText(const redgpu_dfa *dfa, int what, uint64_t keyIndex, int which,
+                          const uint8_t *data, uint64_t len, uint64_t tableSlots) {
+  const char *own = nullptr;
+  if (what != REDGPU_GROUP_MATCH && what != REDGPU_GROUP_FIELD)
+    own = "what is neither REDGPU_GROUP_MATCH nor REDGPU_GROUP_FIELD";
+  else if (which != REDGPU_SUM_FIRST && which != REDGPU_SUM_LAST)
+    own = "which is neither REDGPU_SUM_FIRST nor REDGPU_SUM_LAST";
+  else if (keyIndex == 0)
+    own = "key_index is 0";
+  else if (tableSlots < 64 || tableSlots > (1ull << 32) || (tableSlots & (tableSlots - 1)))
+    own = "table_slots is no power of two in [64, 2^32]";
+  // (a key packs offset + 1 above a 24-bit length, as uniq_text's)
+  return checkRawText(dfa, dfa, "", data, len, own, nullptr, 0, 1ull << 31, (1ull << 40) - 1);
+}
+
+// raw text -> one record per distinct key string with the statistics of its lines' numbers
+// (k_group_text.h): everything on `stream`, nothing read back
+int redgpu_group_text_dev(const redgpu_dfa *dfa, int what, uint64_t key_index, uint64_t value_index,
+                          int which, const uint8_t *data, uint64_t len, uint8_t delim,
+                          uint64_t table_slots, uint64_t cap, uint64_t *n_lines, uint64_t *n_keyed,
+                          uint64_t *n_numeric, uint64_t *n_distinct, uint64_t *n_dropped,
+                          uint64_t *first, uint64_t *length, uint64_t *count, uint64_t *stats,
+                          void *stream) {
+  if (int rc = checkGroupText(dfa, what, key_index, which, data, len, table_slots)) return rc;
+  // REDGPU_UNIQ_PLAIN=1: no LDS front, as uniq_text's (measurements)
+  const char *env = getenv("REDGPU_UNIQ_PLAIN");
+  const int plain = env && env[0] == '1';
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return rawTextDev(dfa, s, groupTextScratchBytes(len, table_slots),
+                    [&](void *scratch, const LaunchCfg &cfg, const char **name) {
+    return launchGroupText(dfa->im->dev, what, key_index, value_index, which, data, len, delim,
+                           table_slots, cap, plain, n_lines, n_keyed, n_numeric, n_distinct,
+                           n_dropped, first, length, count, stats, scratch, cfg, s, name);
+  });
+}
+
+// host-buffer form: one upload of the text, the table in the stream's scratch, device records of
+// the call's own (seven words a record, the four rows of stats at the device cap's stride), then
+// the five scalars and the records that exist back - stats row by row, at the caller's stride
+int redgpu_group_text(const redgpu_dfa *dfa, int what, uint64_t key_index, uint64_t value_index,
+                      int which, const uint8_t *data, uint64_t len, uint8_t delim,
+                      uint64_t table_slots, uint64_t cap, uint64_t *n_lines, uint64_t *n_keyed,
+                      uint64_t *n_numeric, uint64_t *n_distinct, uint64_t *n_dropped,
+                      uint64_t *first, uint64_t *length, uint64_t *count, uint64_t *stats) {
+  if (int rc = checkGroupText(dfa, what, key_index, which, data, len, table_slots)) return rc;
+  // no more records than slots, nor than lines, nor lines than bytes
+  uint64_t devCap = cap;
+  if (devCap > table_slots) devCap = table_slots;
+  if (devCap > len) devCap = len;
+  if (!first && !length && !count && !stats) devCap = 0;
+  HostCall call(dfa, len);
+  uint8_t *dData = call.buf<uint8_t>(kSlData, len, "data");
+  uint64_t *dN = call.buf<uint64_t>(kSlAux0, 5, "counts");
+  uint64_t *dFirst = first && devCap ? call.buf<uint64_t>(kSlAux1, devCap, "first") : nullptr;
+  uint64_t *dLength = length && devCap ? call.buf<uint64_t>(kSlAux2, devCap, "length") : nullptr;
+  uint64_t *dCount = count && devCap ? call.buf<uint64_t>(kSlAux3, devCap, "count") : nullptr;
+  uint64_t *dStats = stats && devCap ? call.buf<uint64_t>(kSlOff, 4 * devCap, "stats") : nullptr;
+  call.upload(dData, data, len, "data");
+  call.run([&] {
+    return redgpu_group_text_dev(dfa, what, key_index, value_index, which, dData, len, delim,
+                                 table_slots, devCap, dN, dN + 1, dN + 2, dN + 3, dN + 4, dFirst,
+                                 dLength, dCount, dStats, call.stream());
+  });
+  uint64_t counts[5] = {0, 0, 0, 0, 0};
+  call.download(counts, dN, 5, "counts");
+  if (int rc = call.wait()) return rc;
+  const uint64_t put = counts[3] < devCap ? counts[3] : devCap;
+  if (dFirst && put) call.download(first, dFirst, put, "first");
+  if (dLength && put) call.download(length, dLength, put, "length");
+  if (dCount && put) call.download(count, dCount, put, "count");
+  for (uint64_t row = 0; row < 4 && dStats && put; ++row)
+    call.download(stats + row * cap, dStats + row * devCap, put, "stats");
+  if (int rc = call.wait()) return rc;
+  if (n_lines) *n_lines = counts[0];
+  if (n_keyed) *n_keyed = counts[1];
+  if (n_numeric) *n_numeric = counts[2];
+  if (n_distinct) *n_distinct = counts[3];
+  if (n_dropped) *n_dropped = counts[4];
+  return REDGPU_OK;
+}
+
+uint32_t redgpu_group_lds_slots(const redgpu_dfa *dfa) {
+  if (!dfa) return 0;
+  const DfaImage &img = dfa->im->img;
+  return groupLdsSlots(img.tableKind, (img.primaryBytes + 15u) & ~15u, img.nStates);
+}
+
 // raw text -> every match of every line as bytes, one per output line (k_extract_text.h):
 // everything on `stream`, nothing read back; phases as launchExtractText's
 static int extractTextDev(const redgpu_dfa *dfa, const uint8_t *data, uint64_t len, uint8_t delim,

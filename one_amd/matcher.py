@@ -1562,6 +1562,85 @@ def dedup_text(exe, data, *, what="whole", key_index=1, style=styInstant, do_lea
     return tuple(int(x.value) for x in n[:5]) + (text,)
 
 
+GROUP_MATCH, GROUP_FIELD = 0, 1
+_GROUP_WHAT = {"match": GROUP_MATCH, "field": GROUP_FIELD}
+
+
+def group_text(exe, data, *, what="field", key_index=1, value_index=2, which="first",
+               delim=b"\n", max_distinct=1 << 20, cap=None):
+    """redgpu_group_text[_dev]: awk '{ n[$k]++; s[$k] += $v; if ($v > m[$k]) m[$k] = $v }' - one
+    record per distinct KEY string of a raw text's delimiter-terminated lines, with the statistics
+    of the lines' numbers.  The items of a line are the pieces extract_text emits for it
+    (what="match") or its fields with the DFA as the separator ("field", fields_text's rule; a
+    field may be empty), numbered from 1: item key_index is the key - a line with fewer items is
+    unkeyed and contributes nothing - and item value_index (0: none; below, at or above key_index)
+    the value, whose number is sum_text's: the first (which="first") or last ("last") run of digits
+    0-9 inside the item, read as an unsigned decimal.  A keyed line is numeric iff its value item
+    exists, has a run, and the run is below 2^64.  Record j, in the order of first appearance, is
+    (first[j], length[j], count[j], stats[:, j]): the key is data[first[j] : first[j] + length[j]]
+    (first strictly ascending), count[j] its keyed lines, stats' rows SUM_COUNT (its numeric lines),
+    SUM_SUM (modulo 2^64), SUM_MIN, SUM_MAX; a key without numeric lines reads 0, 0, 2^64 - 1, 0.
+    The hash table has the power of two at or above 2 * max_distinct (at least 64) slots of 48
+    bytes; n_dropped counts the keyed lines in no record - keys of 2^24 bytes or more, and those
+    that found the table full (then call again with a larger max_distinct) - which enter no record
+    with either their count or their number; n_numeric counts the numeric lines in the records.
+    While n_dropped is 0 every output is bit-identical from run to run.
+    Host input -> (n_lines, n_keyed, n_numeric, n_dropped, first, length, count, stats): uint64
+    arrays of min(n_distinct, cap) records (stats of shape (4, that)), cap=None meaning all.
+    A CUDA uint8 tensor -> (n_lines, n_keyed, n_numeric, n_dropped, n_distinct, first, length,
+    count, stats): the counts as 1-element int64 tensors, the arrays int64 of cap records (cap=None:
+    max_distinct; stats of shape (4, cap)) of which the first min(n_distinct, cap) are written,
+    asynchronously on the current stream and without any read-back.  The words are unsigned:
+    stats.cpu().numpy().view(numpy.uint64) gives the values as they are."""
+    l = _lib.lib()
+    d = _delim_byte(delim)
+    if what not in _GROUP_WHAT:
+        raise RedExceptApi('what must be "match" or "field"')
+    if which not in _SUM_WHICH:
+        raise RedExceptApi('which must be "first" or "last"')
+    w, wh = _GROUP_WHAT[what], _SUM_WHICH[which]
+    key_index, value_index, max_distinct = int(key_index), int(value_index), int(max_distinct)
+    if key_index < 1 or key_index >= 1 << 64:
+        raise RedExceptApi("key_index must be in [1, 2^64)")
+    if value_index < 0 or value_index >= 1 << 64:
+        raise RedExceptApi("value_index must be in [0, 2^64)")
+    if max_distinct < 1 or max_distinct > 1 << 31:
+        raise RedExceptApi("max_distinct must be in [1, 2^31]")
+    if cap is not None and int(cap) < 0:
+        raise RedExceptApi("cap must not be negative")
+    slots = 64
+    while slots < 2 * max_distinct:
+        slots *= 2
+    if _is_torch(data):
+        import torch
+        dev, ptr, size, stream = _device_raw_text(data)
+        rows = max_distinct if cap is None else int(cap)
+        cnt = torch.empty(5, dtype=torch.int64, device=dev)
+        rec = torch.empty((3, rows), dtype=torch.int64, device=dev)
+        stats = torch.empty((4, rows), dtype=torch.int64, device=dev)
+        at = [cnt.data_ptr() + 8 * k for k in range(5)]
+        _check(l.redgpu_group_text_dev(
+            exe._h, w, key_index, value_index, wh, ptr, size, d, slots, rows, at[0], at[1], at[2],
+            at[3], at[4], rec[0].data_ptr() if rows else None, rec[1].data_ptr() if rows else None,
+            rec[2].data_ptr() if rows else None, stats.data_ptr() if rows else None, stream))
+        return cnt[0:1], cnt[1:2], cnt[2:3], cnt[4:5], cnt[3:4], rec[0], rec[1], rec[2], stats
+    a = _host_u8(data)
+    # no more records than slots, nor than bytes
+    rows = min(slots, int(a.size)) if cap is None else min(int(cap), slots, int(a.size))
+    wide = max(rows, 1)
+    rec = np.zeros((3, wide), dtype=np.uint64)
+    stats = np.zeros((4, wide), dtype=np.uint64)
+    n = [C.c_uint64(0) for _ in range(5)]
+    _check(l.redgpu_group_text(
+        exe._h, w, key_index, value_index, wh, a.ctypes.data if a.size else None, a.size, d, slots,
+        wide if rows else 0, C.byref(n[0]), C.byref(n[1]), C.byref(n[2]), C.byref(n[3]),
+        C.byref(n[4]), rec[0].ctypes.data, rec[1].ctypes.data, rec[2].ctypes.data,
+        stats.ctypes.data))
+    got = min(int(n[3].value), rows)
+    return (int(n[0].value), int(n[1].value), int(n[2].value), int(n[4].value),
+            rec[0, :got].copy(), rec[1, :got].copy(), rec[2, :got].copy(), stats[:, :got].copy())
+
+
 def extract_text(exe, data, *, max_per_line=1 << 62, delim=b"\n", out=None, out_cap=None):
     """redgpu_extract_text[_dev]: grep -o as a text - every match of every delimiter-terminated
     line of a raw text buffer (Red::collect's chain, collect_text's records), as bytes: the span

@@ -1,7 +1,8 @@
 """Differential fuzz on the GPU: random DFAs x random line shapes x every verb / style / leader x
 random placement and kernel-selection flags, against the CPU oracle.  Not part of the pytest
 suite (it is open-ended); a failure prints the case and exits non-zero.
-usage: fuzz_gpu.py [cases] [seed] [hot | cls | lists | blocks | long | text | lines | pieces | keys] [dry]
+usage: fuzz_gpu.py [cases] [seed] [hot | cls | lists | blocks | long | text | lines | pieces | keys | groups]
+       [dry]
 long: the DFAs and placement flags of the general mode, one buffer of 2 KiB to 128 KiB as ONE
 text through collect_long, replace_long, search_long and match_all_long (random style, leader
 setting, chunk size, cap / max count and replacement).  Without a pure dead state an attempt that
@@ -45,7 +46,14 @@ at a pointer offset of 0 to 15 into a 0x55-filled buffer at out_cap = exact, 0 o
 tests/dedup_rule.py.  dry works as above and ends with one `cover keys dedup_text` line: how many
 cases ran each mode, held a string that occurs twice or more, an unkeyed line, a count window that
 changes the output, an empty key, more than one chunk, a truncated output;
-tests/test_dedup_rule.py holds it to floors."""
+tests/test_dedup_rule.py holds it to floors.
+groups: group_text alone, likewise with cases of its own - a golden or a random DFA under random
+placement flags, a text of 0 to 1,000 lines of one to four tokens each, the tokens from a pool of at
+most 8 keys and one of at most 6 numbers (small ones, 2^64 - 1, 2^64, leading zeros, none), so that
+keys repeat and carry numbers; a random mode, key index, value index (0, below, at and above the
+key's), `which`, delimiter and cap, through the host form or the device form at an odd pointer
+offset - against tests/group_rule.py.  dry works as above and ends with one `cover groups
+group_text` line; tests/test_group_rule.py holds it to floors."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
@@ -864,6 +872,144 @@ def keys_main():
 
 if KEYS:
     keys_main()
+    sys.exit(0)
+
+
+# group_text: mode groups ---------------------------------------------------------------------------
+GROUPS = len(sys.argv) > 3 and sys.argv[3] == "groups"
+GROUPS_DRY = GROUPS and len(sys.argv) > 4 and sys.argv[4] == "dry"
+NUMBERS = [b"0", b"7", b"007", b"12", b"345", b"99999", b"18446744073709551615",
+           b"18446744073709551616", b"0" * 25 + b"7", b"3.14", b"x1y22z333", b"", b"none"]
+
+
+def groups_text(name):
+    """(lines, delim): 0 to 1,000 lines (one case in twenty none), each one to four tokens - a key
+    from a pool of at most 8 strings, a number from a pool of at most 6, now and then other bytes -
+    joined by one separator of the case's, so that keys repeat and carry numbers; no line is longer
+    than 230 bytes (a search that does not die is quadratic)"""
+    delim = [0x0A, 0x00, 0x3B][int(rng.integers(0, 3))]
+    n = 0 if rng.random() < 0.05 else int(rng.integers(1, 1001))
+    src = make_data_wide(64 * 1024, name)
+    src = src[src != delim]
+    keys = []
+    for _ in range(int(rng.integers(1, 9))):
+        k = int(rng.choice([0, 1, 3, 8, 20]))
+        at = int(rng.integers(0, len(src) - k))
+        keys.append(src[at:at + k].tobytes())
+    nums = [NUMBERS[int(rng.integers(0, len(NUMBERS)))] for _ in range(int(rng.integers(1, 7)))]
+    sep = [b" ", b"error", b" aab ", b",", b" 12 "][int(rng.integers(0, 5))]
+    if name == "num3":
+        keys = [b"k%c" % (0x61 + i) for i in range(len(keys))]    # (a number DFA cuts at digits)
+    lines = []
+    for _ in range(n):
+        toks = []
+        for _ in range(int(rng.integers(1, 5))):
+            r = rng.random()
+            if r < 0.45:
+                toks.append(keys[int(rng.integers(0, len(keys)))])
+            elif r < 0.85:
+                toks.append(nums[int(rng.integers(0, len(nums)))])
+            else:
+                k = int(rng.choice([0, 1, 5, 30, 60]))
+                at = int(rng.integers(0, len(src) - k))
+                toks.append(src[at:at + k].tobytes())
+        lines.append(sep.join(toks)[:230].replace(bytes([delim]), b"_"))
+    return lines, delim
+
+
+def groups_main():
+    import group_rule as GR
+    import text_rules as TR
+    global PLANTS_WIDE
+    from one_amd import workloads as W
+    PLANTS_WIDE = [b"error", b"an error: x", b"New York", b"123abcd ", b"aab", W.URI_PLANT,
+                   W.URI_USER_PLANT, W.URI_V6_PLANT] + W.log100_heads()[::9]
+    t0 = time.time()
+    stats = {}
+    row = dict(cases=0, match=0, field=0, first=0, last=0, repeated=0, unkeyed=0, numeric=0,
+               not_numeric=0, no_value=0, value_first=0, empty_key=0, chunk=0, capped=0, dev=0)
+    for case in range(cases):
+        if rng.random() < 0.5:
+            name = ["num3", "aab", "err", "err"][int(rng.integers(0, 4))]
+            blob = load_dfa(name)
+        else:
+            name, blob = make_dfa_wide()
+        flags = {}
+        for f, p in (("force_global", 0.15), ("force_hot", 0.2)):
+            if rng.random() < p:
+                flags[f] = True
+        if rng.random() < 0.3:
+            flags["lds_table_max"] = int(rng.choice([8 * 256, 40 * 256, 100 * 256, 20000, 70000]))
+        try:
+            exe = one_amd.Executable(blob, **(dict(device="none") if GROUPS_DRY else {}), **flags)
+        except one_amd.RedExcept as e:
+            print("create refused:", name, flags, e)
+            continue
+        cpu = O.CpuOracle(blob)
+        # (every second draw takes the modes in turn: neither is rare under any seed)
+        what = GR.WHATS[case % 2 if rng.random() < 0.5 else int(rng.integers(0, 2))]
+        key_index = int(rng.choice([1, 1, 1, 2, 2, 3, 9]))
+        value_index = int(rng.choice([0, 1, 1, 2, 2, 2, 3, 4, 9]))
+        which = ["first", "last"][int(rng.integers(0, 2))]
+        lines, delim = groups_text(name)
+        d = bytes([delim])
+        tail = [b"", b"", lines[0] if lines else b"tail"][int(rng.integers(0, 3))]
+        data = np.frombuffer(b"".join(x + d for x in lines) + tail, dtype=np.uint8).copy()
+        t = TR.Text(cpu, data.tobytes(), delim)
+        per = GR.numbers(t, what, key_index, value_index, which)
+        want = GR.group(t, what, key_index, value_index, which)
+        n = len(want[4])
+        dev, shift, _ = draw_form(False)
+        cap = [None, n, n // 2, 0, n + 3][int(rng.integers(0, 5))]
+        desc = (case, name, flags, what, key_index, value_index, which, delim, len(data), cap)
+        strings = [p[1] for p in per if p is not None]
+        row["cases"] += 1
+        row[what] += 1
+        row[which] += 1
+        row["repeated"] += len(set(strings)) < len(strings)
+        row["unkeyed"] += None in per
+        row["numeric"] += want[2] > 0
+        row["not_numeric"] += want[2] < want[1]
+        row["no_value"] += value_index == 0
+        row["value_first"] += 0 < value_index < key_index
+        row["empty_key"] += b"" in strings
+        row["chunk"] += len(data) > CHUNK
+        row["capped"] += cap is not None and cap < n
+        row["dev"] += dev
+        if not GROUPS_DRY:
+            verb = dict(what=what, key_index=key_index, value_index=value_index, which=which,
+                        delim=d, max_distinct=1024, cap=cap)
+            k = n if cap is None else min(n, cap)
+            cut = want[:4] + tuple(a[..., :k] for a in want[4:])
+            try:
+                if dev:
+                    import torch
+                    got = one_amd.group_text(exe, dev_text(data, shift), **verb)
+                    torch.cuda.synchronize()
+                    ok = [int(x.item()) for x in got[:5]] == list(want[:4]) + [n] and \
+                        same_arrays([x[..., :k].cpu().numpy().view(np.uint64) for x in got[5:]],
+                                    cut[4:])
+                else:
+                    got = one_amd.group_text(exe, data, **verb)
+                    ok = got[:4] == cut[:4] and same_arrays(got[4:], cut[4:]) and \
+                        all(g.shape == w.shape for g, w in zip(got[4:], cut[4:]))
+            except one_amd.RedExcept as e:
+                print("ERROR", desc, e)
+                sys.exit(1)
+            kern = one_amd.last_kernel()
+            stats[kern] = stats.get(kern, 0) + 1
+            if not ok:
+                print("MISMATCH", desc, "group_text", "dev" if dev else "host", shift)
+                sys.exit(1)
+        if case % 25 == 0:
+            print("case", case, "%.0fs" % (time.time() - t0), flush=True)
+    print("cover groups group_text", " ".join("%s=%d" % kv for kv in row.items()))
+    print("fuzz dry:" if GROUPS_DRY else "fuzz ok:", cases, "cases; kernels:",
+          dict(sorted(stats.items())))
+
+
+if GROUPS:
+    groups_main()
     sys.exit(0)
 
 t0 = time.time()
